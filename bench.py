@@ -12,14 +12,19 @@ fp8 correction sweep per GEMM, fp32 accumulate) unless MV_F16 passes too.  The o
 `precise` object with its own error stated.
 
     python bench.py                              # 1 GPU
+    python bench.py --full                       # + every other leg (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel:
-algorithmic FLOPs per launch / HIP-event duration on the engine's stream), `cpu_baseline` (the
-reference's CPU graph, oracle/hf_reference.py, timed on this box's host cores on a bounded sample, with and
+Prints ONE JSON line on rank 0 with `metric`, `value`, `unit`, `higher_is_better`, `dtype` and `ms_per_step` (wall time of one
+of the K timed steps).  A plain run does only that: set-up, W warm-up steps, the K timed steps, the line; without the CPU leg
+`--compute auto` is MV_F16X8 (MV_F16 misses the 1e-3 contract on trained-like weights by ~5x, so auto never hands it `value`).
+`--dump-outputs DIR` writes the last timed step's results as .npy files (seeded inputs: identical from run to run).
+`--full` adds `roofline` (dominant kernel: algorithmic FLOPs per launch / HIP-event duration on the engine's stream),
+`cpu_baseline` (the reference's CPU graph, oracle/hf_reference.py, timed on the host cores on a bounded sample, with and
 without the reference's per-batch host work), `contract` (both modes' trained-like logit errors and which mode carries `value`),
-and — N = 1 — `fast` (the other compute dtype on the same workload) and `cfg3` (BASELINE.json configs[2]: S 512, B 128).
+and — N = 1 — `fast` (the other compute dtype on the same workload) and `cfg3` (BASELINE.json configs[2]: S 512, B 128);
+N > 1 — `corpus_shard`.
 """
 from __future__ import annotations
 
@@ -117,6 +122,12 @@ def main():
     ap.add_argument("--anchors", type=int, default=124)
     ap.add_argument("--anchor-len", type=int, default=512)
     ap.add_argument("--layers", type=int, default=12)
+    ap.add_argument("--full", action="store_true", help="also run everything besides the headline: the trained-like error contract (CPU leg), the "
+                    "per-kernel HIP-event passes, the sustained rate, the matcher, the CPU baseline, cfg3 and the second compute dtype (N = 1), "
+                    "the corpus-shard leg (N > 1); --cpu-sample, --ab, --no-profile, --ragged, --no-precise, --sustain-s, --shard-irs and "
+                    "--matcher-anchors shape those legs and act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (its batch's "
+                    "`best` [B, 2] and `best_idx` [B]) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--cpu-sample", type=int, default=192, help="IRs timed on the CPU baseline (three batches of 64; bounded at ~30 s; 0 disables)")
     ap.add_argument("--ab", action="store_true", help="N = 1: also run the both-terms form of the precise mode (MEMVUL_CLS_ASIDE=0) on the same workload: the "
                     "`precise_cls_aside_off` object (ledger material, not part of the default line)")
@@ -125,9 +136,9 @@ def main():
                     "padded to seq_len and length-bucketed (each batch at its longest member); adds a `ragged` object")
     ap.add_argument("--streams", type=int, default=2, choices=(1, 2), help="batches of the resident sweep in flight at once")
     ap.add_argument("--compute", default="auto", choices=("auto", "f16", "fast", "f16x8", "precise"), help="compute dtype of the headline `value`; auto = "
-                    "the fastest mode whose trained-like logit error measured in this run is <= 1e-3 (precise when the CPU leg is off); precise = "
-                    "f16x8 = MV_F16X8 (+ one fp8 correction sweep per GEMM: holds 1e-3 on trained-like logits); f16 = fast = MV_F16; the "
-                    "default line carries the other mode as its `fast` / `precise` object either way")
+                    "the fastest mode whose trained-like logit error measured in this run is <= 1e-3 (precise when the CPU leg is off, as it is "
+                    "without --full); precise = f16x8 = MV_F16X8 (+ one fp8 correction sweep per GEMM: holds 1e-3 on trained-like logits); "
+                    "f16 = fast = MV_F16; the --full line carries the other mode as its `fast` / `precise` object either way")
     ap.add_argument("--no-precise", "--no-second", dest="no_second", action="store_true", help="N = 1: skip the second engine (the `fast` / "
                     "`precise` object of the mode that does not carry `value`) and the `cfg3` object")
     ap.add_argument("--sustain-s", type=float, default=3.0, help="N = 1: also report the rate over a run of at least this many seconds (0 disables)")
@@ -135,6 +146,11 @@ def main():
                     "8-GPU shard of the reference's corpus, README.md:8; -1 disables)")
     ap.add_argument("--matcher-anchors", type=int, default=1000, help="N = 1: anchors of the fused match + top-k measurement (configs[4]; 0 disables)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: set up, warm up, the timed steps, the headline line — nothing else
+        args.cpu_sample, args.no_profile, args.sustain_s, args.matcher_anchors = 0, True, 0.0, 0
+        args.no_second, args.ab, args.ragged, args.shard_irs = True, False, False, -1
 
     # `--gpus N` is a promise about the line's `n_gpus`: under a launcher WORLD_SIZE must say N too; WITHOUT a launcher this
     # process becomes the launcher of N ranks (self_launch) — it never runs one rank and reports it as N, or N as one
@@ -247,6 +263,9 @@ def main():
         mvdist.barrier()
     t1 = time.perf_counter()
     elapsed = mvdist.all_reduce_max(t1 - t0) if multi else (t1 - t0)
+    if args.dump_outputs and rank == 0:
+        last = ((W + K - 1) % n_batches) * B  # the corpus rows the last timed step scored
+        dump_outputs(args.dump_outputs, best=best[last:last + B], best_idx=idx[last:last + B])
     # roofline pass: the same K steps once more with one batch in flight and HIP events (engine stream) around the
     # dominant GEMM class only -> per-launch duration of that kernel alone, and the one-batch-in-flight rate
     prof, single_rate = {}, None
@@ -374,6 +393,14 @@ def main():
             out["precise_cls_aside_" + ("off" if other_cls == "0" else "on")] = precise_option_leg(args, dims, weights, aids, alens, ids, lens, S, {"MEMVUL_CLS_ASIDE": other_cls})
     print(json.dumps(out), flush=True)
     mvdist.shutdown()
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy, floats as float32, integers as float64 (exact for int32)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32 if a.dtype.kind == "f" else np.float64))
 
 
 def visible_gpus() -> int:

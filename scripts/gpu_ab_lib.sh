@@ -5,7 +5,7 @@ OTHER=$(readlink -f "$1"); R=${2:-2}
 for r in $(seq $R); do
   for which in other tree; do
     if [ $which = other ]; then export MEMVUL_HIP_LIB=$OTHER; else unset MEMVUL_HIP_LIB; fi
-    python bench.py --cpu-sample 0 --no-second --matcher-anchors 0 --sustain-s 0 2>/dev/null | python -c "
+    python bench.py --full --cpu-sample 0 --no-second --matcher-anchors 0 --sustain-s 0 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$which', d['value'], d['value_one_batch_in_flight'], {k: v['avg_us'] for k, v in d['kernels'].items() if k.startswith('gemm') or k in ('embed_ln', 'attention')})"

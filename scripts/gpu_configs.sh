@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 note() { echo "== $* ($(date +%H:%M:%S))"; }
 python -m memvul_amd.build > /dev/null || exit 1   # no-op when the binary that travelled matches the sources; never profile a stale one
-Q="--cpu-sample 0 --sustain-s 0 --no-precise"
+Q="--full --cpu-sample 0 --sustain-s 0 --no-precise"
 : > $O/other_configs_bench_lines.jsonl
 note "cfg 3: S=512, B=128 (f16, precise)"
 timeout 300 python bench.py --seq-len 512 --batch 128 --matcher-anchors 0 $Q 2>> $O/cfg.err | tail -1 >> $O/other_configs_bench_lines.jsonl
@@ -29,7 +29,7 @@ for l in open("gpurun_out/other_configs_bench_lines.jsonl"):
     except Exception as e:
         print("bad line", e, l[:200])
 PY
-COMMON="--cpu-sample 0 --sustain-s 0 --matcher-anchors 0 --streams 1 --no-precise --compute precise"
+COMMON="--full --cpu-sample 0 --sustain-s 0 --matcher-anchors 0 --streams 1 --no-precise --compute precise"
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE"
 rm -rf $O/px_stats $O/px_sq
 note "precise: kernel trace"

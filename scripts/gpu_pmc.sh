@@ -18,7 +18,7 @@ note() { echo "== $* ($(date +%H:%M:%S))"; }
 python -m memvul_amd.build > /dev/null || exit 1   # no-op when the binary that travelled matches the sources; never profile a stale one
 SHAPE=""
 [ "$CFG" = "cfg3" ] && SHAPE="--seq-len 512 --batch 128"
-COMMON="--compute $MODE --cpu-sample 0 --sustain-s 0 --matcher-anchors 0 --streams 1 --no-second $SHAPE"
+COMMON="--full --compute $MODE --cpu-sample 0 --sustain-s 0 --matcher-anchors 0 --streams 1 --no-second $SHAPE"
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE"
 P=$O/p_${MODE}_${CFG}
 rm -rf ${P}_stats ${P}_sq ${P}_fetch ${P}_write

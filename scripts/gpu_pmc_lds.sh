@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 note() { echo "== $* ($(date +%H:%M:%S))"; }
 python -m memvul_amd.build > /dev/null || exit 1
-COMMON="--cpu-sample 0 --sustain-s 0 --matcher-anchors 0 --streams 1 --no-precise --steps 2 --warmup 1 --no-profile"
+COMMON="--full --cpu-sample 0 --sustain-s 0 --matcher-anchors 0 --streams 1 --no-precise --steps 2 --warmup 1 --no-profile"
 rm -rf $O/p_lds $O/p_inst $O/p_l2
 note "LDS counters"
 ( cd /tmp && timeout 420 rocprofv3 --kernel-trace --pmc SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $R/$O/p_lds -o lds -- python $R/bench.py $COMMON > $R/$O/p_lds.log 2>&1 )

@@ -4,9 +4,9 @@
 # steps:
 #   suite[:K]    the GPU test suite (pytest -m gpu; K = a -k expression)
 #   smoke        __graft_entry__.smoke()
-#   bench        the default bench line            driver     the driver's form (--gpus 1 --steps 20 --warmup 5)
-#   quick        bench without the CPU leg / second engine (value + kernels only)
-#   ab           bench --ab (adds the both-terms form of the precise mode)
+#   bench        the full bench line (--full)      driver     the driver's form (--gpus 1 --steps 20 --warmup 5)
+#   quick        bench --full without the CPU leg / second engine (value + kernels only)
+#   ab           bench --full --ab (adds the both-terms form of the precise mode)
 #   pmc[:mode[:cfg]]  rocprofv3 kernel trace + counter passes (scripts/gpu_pmc.sh; mode precise|f16, cfg cfg2|cfg3) -> pmc_current.json
 #   errdist      24-draw trained-like error distribution (scripts/r05_error_distribution.py)
 #   envelope     matcher-norm / outlier envelope (scripts/r05_precision_envelope.py)        lengths  sequence-length axis (scripts/r05_length_envelope.py)
@@ -46,10 +46,10 @@ for step in "$@"; do
            else ( timeout 1500 python -m pytest tests -m gpu -q > $V/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $V/pytest_gpu.log ); fi
            grep -E "passed|failed|^FAILED|^ERROR|rc=" $V/pytest_gpu.log | tail -15 ;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $V/smoke.txt 2>&1; tail -2 $V/smoke.txt ;;
-    bench) ( T0=$(date +%s); timeout 600 python bench.py > $V/bench_line.json 2> $V/bench_line.err; echo "rc=$? wall $(( $(date +%s) - T0 )) s" >> $V/bench_line.err ); line $V/bench_line.json; tail -1 $V/bench_line.err ;;
+    bench) ( T0=$(date +%s); timeout 600 python bench.py --full > $V/bench_line.json 2> $V/bench_line.err; echo "rc=$? wall $(( $(date +%s) - T0 )) s" >> $V/bench_line.err ); line $V/bench_line.json; tail -1 $V/bench_line.err ;;
     driver) ( T0=$(date +%s); timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $V/bench_line_driver_form.json 2> $V/bench_line_driver_form.err; echo "rc=$? wall $(( $(date +%s) - T0 )) s" >> $V/bench_line_driver_form.err ); line $V/bench_line_driver_form.json; tail -1 $V/bench_line_driver_form.err ;;
-    quick) ( timeout 300 python bench.py --cpu-sample 0 --no-second --matcher-anchors 0 --sustain-s 0 $arg > $V/bench_quick.json 2> $V/bench_quick.err ); line $V/bench_quick.json ;;
-    ab) ( timeout 900 python bench.py --ab > $V/bench_line_ab.json 2> $V/bench_line_ab.err ); line $V/bench_line_ab.json ;;
+    quick) ( timeout 300 python bench.py --full --cpu-sample 0 --no-second --matcher-anchors 0 --sustain-s 0 $arg > $V/bench_quick.json 2> $V/bench_quick.err ); line $V/bench_quick.json ;;
+    ab) ( timeout 900 python bench.py --full --ab > $V/bench_line_ab.json 2> $V/bench_line_ab.err ); line $V/bench_line_ab.json ;;
     pmc) m=${arg%%:*}; c=cfg2; [ "$arg" != "$m" ] && c=${arg#*:}; [ -z "$m" ] && m=precise
          bash scripts/gpu_pmc.sh r06 $m $c > $V/pmc_${m}_${c}.log 2>&1; tail -3 $V/pmc_${m}_${c}.log ;;
     errdist) timeout 700 python scripts/r05_error_distribution.py --f16-seeds 0 --json $V/error_distribution.json > $V/error_distribution.txt 2>&1; tail -2 $V/error_distribution.txt ;;

@@ -188,7 +188,7 @@ def test_bench_two_ranks_control_flow_and_json_contract(tmp_path):
     port = 30400 + (os.getpid() % 200)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--batch", "32",
-           "--seq-len", "64", "--anchors", "8", "--anchor-len", "64", "--layers", "1", "--shard-irs", "700"]
+           "--seq-len", "64", "--anchors", "8", "--anchor-len", "64", "--layers", "1", "--shard-irs", "700", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -211,11 +211,11 @@ def test_bench_two_ranks_control_flow_and_json_contract(tmp_path):
     assert "cpu_baseline" not in d and "precise" not in d  # rank-0, N = 1 only
 
 
-def _stub_bench(extra, env_extra=None, timeout=300):
+def _stub_bench(extra, env_extra=None, timeout=300, full=True):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(OMP_NUM_THREADS="1", MEMVUL_BENCH_STUB_ENGINE="1", **(env_extra or {}))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "32", "--seq-len", "64",
-           "--anchors", "8", "--anchor-len", "64", "--layers", "1", "--shard-irs", "300"] + extra
+           "--anchors", "8", "--anchor-len", "64", "--layers", "1", "--shard-irs", "300"] + (["--full"] if full else []) + extra
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
 
 
@@ -275,6 +275,39 @@ def test_bench_single_rank_line_on_the_stand_in_engine():
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["value"] is None and d["data"] == "stub" and d["matcher"]["anchors"] == 1000
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line holds the headline and nothing that takes a run of its own; --dump-outputs writes the last timed
+    step's results (steps 4 + warmup 1 over 5 resident batches of 32: the last step scored corpus rows 128..159), the same on every run."""
+    import numpy as np
+
+    from bench_stub_engine import Engine
+    from memvul_amd import synth
+
+    dumps = []
+    for run in range(2):
+        out = tmp_path / str(run)
+        r = _stub_bench(["--dump-outputs", str(out)], full=False)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["config"]["compute"] == "precise"
+        for k in ("matcher", "value_sustained", "cpu_baseline", "contract", "cfg3", "fast", "roofline", "kernels", "ragged", "corpus_shard"):
+            assert k not in d, k
+        assert sorted(os.listdir(out)) == ["best.npy", "best_idx.npy"]
+        dumps.append({k: np.load(out / (k + ".npy")) for k in ("best", "best_idx")})
+    assert dumps[0]["best"].dtype == np.float32 and dumps[0]["best"].shape == (32, 2)
+    assert dumps[0]["best_idx"].dtype == np.float64 and dumps[0]["best_idx"].shape == (32,)
+    for k in ("best", "best_idx"):
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    ids, lens = synth.make_ids(5 * 32, 64, synth.BertDims(layers=1).vocab_size, seed=synth.SEED)
+    e = Engine(0)
+    e.corpus_upload(ids, lens)
+    e.corpus_run(0, 5 * 32, 32)
+    best, idx, _ = e.corpus_results(128, 32)
+    assert np.array_equal(dumps[0]["best"], best) and np.array_equal(dumps[0]["best_idx"], idx.astype(np.float64))
 
 
 def test_bench_refuses_a_world_that_is_not_what_gpus_says():

@@ -2,7 +2,7 @@
 # ENERGY-share ablations of the (power-bound) persistent GEMM, wrong results by construction:
 #   noread = fragment ds_reads only during the first two K-tiles of a workgroup (the registers keep their values afterwards)
 #   nodma  = no LDS-DMA after the prologue (the ring keeps its first contents)
-Q="--matcher-anchors 0 --cpu-sample 0 --sustain-s 0 --no-precise --streams 1"
+Q="--full --matcher-anchors 0 --cpu-sample 0 --sustain-s 0 --no-precise --streams 1"
 P=$PWD/tools/probe_energy
 one() { python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], {k: v['avg_us'] for k, v in d['kernels'].items() if k.startswith('gemm')})"; }
 for rep in 1 2; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B: order of the LDS-DMA issue against the fragment reads inside a barrier interval of gemm_pp (v1: DMA first in both wave groups,
 # v2: in the fragments-first group only, v3: in the matrix-pipe-first group only).  Functionally neutral; checked on v1.
-Q="--matcher-anchors 0 --cpu-sample 0 --sustain-s 0 --no-precise"
+Q="--full --matcher-anchors 0 --cpu-sample 0 --sustain-s 0 --no-precise"
 P=$PWD/tools/probe_order
 MEMVUL_HIP_LIB=$P/libpp_order_v1.so timeout 600 python -m pytest tests/test_gpu_kernels.py -q -x -k "persistent or layer0" 2>&1 | tail -2
 one() { python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['value_one_batch_in_flight'], {k: v['avg_us'] for k, v in d['kernels'].items() if k.startswith('gemm')})"; }

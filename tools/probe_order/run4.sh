@@ -1,5 +1,5 @@
 #!/bin/bash
-Q="--matcher-anchors 0 --cpu-sample 0 --sustain-s 0 --no-precise"
+Q="--full --matcher-anchors 0 --cpu-sample 0 --sustain-s 0 --no-precise"
 P=$PWD/tools/probe_order
 MEMVUL_HIP_LIB=$P/libpp_order_v4.so timeout 600 python -m pytest tests/test_gpu_kernels.py -q -x -k "persistent" 2>&1 | tail -1
 one() { python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['value_one_batch_in_flight'], {k: v['avg_us'] for k, v in d['kernels'].items() if k.startswith('gemm')})"; }
