@@ -51,7 +51,7 @@ NUM_KERNEL_CLASSES = 14
 ABI_SYMBOLS = [
     "mv_create", "mv_destroy", "mv_last_error", "mv_sync", "mv_load_tensor", "mv_finalize_weights",
     "mv_anchor_reset", "mv_anchor_append", "mv_anchor_count", "mv_anchor_get", "mv_anchor_set",
-    "mv_forward", "mv_forward_groups", "mv_forward_ragged", "mv_forward_ragged_begin", "mv_forward_ragged_end", "mv_encode", "mv_match", "mv_topk", "mv_corpus_upload", "mv_corpus_run", "mv_corpus_run_len",
+    "mv_forward", "mv_forward_ragged", "mv_forward_ragged_begin", "mv_forward_ragged_end", "mv_encode", "mv_match", "mv_topk", "mv_corpus_upload", "mv_corpus_run", "mv_corpus_run_len",
     "mv_corpus_results", "mv_x8_saturation", "mv_attention_concentration", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
     "mv_debug_encode", "mv_debug_read", "mv_test_gemm", "mv_test_gemm_pp", "mv_test_e4m3", "mv_format_records", "mv_comm_prepare", "mv_comm_unique_id", "mv_comm_init", "mv_comm_allgather",
     "mv_comm_destroy", "mv_comm_info", "mv_device_count",
@@ -102,7 +102,6 @@ def load_library(path: Optional[str] = None, dev: bool = False):
         "mv_anchor_get": (C.c_int, [vp, vp]),
         "mv_anchor_set": (C.c_int, [vp, vp, C.c_int]),
         "mv_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
-        "mv_forward_groups": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
         "mv_forward_ragged": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
         "mv_forward_ragged_begin": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int)]),
         "mv_forward_ragged_end": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
@@ -155,6 +154,12 @@ def _ptr(a: Optional[np.ndarray]):
 
 def _as(a, dtype) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _outputs(B: int, G: int, P: int, want_logits: bool, want_probs: bool, want_embed: bool) -> Dict[str, Optional[np.ndarray]]:
+    """The result arrays of the forward entry points (None = not asked for; best / best_idx always)."""
+    return {"logits": np.empty((B, G, 2), np.float32) if want_logits else None, "probs": np.empty((B, G, 2), np.float32) if want_probs else None,
+            "best": np.empty((B, 2), np.float32), "best_idx": np.empty((B,), np.int32), "embed": np.empty((B, P), np.float32) if want_embed else None}
 
 
 class Engine:
@@ -289,16 +294,11 @@ class Engine:
     def forward(self, ids: np.ndarray, lens: np.ndarray, want_logits=True, want_probs=True, want_embed=False):
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         B, S = ids.shape
-        G = self.n_anchors
-        logits = np.empty((B, G, 2), np.float32) if want_logits else None
-        probs = np.empty((B, G, 2), np.float32) if want_probs else None
-        best = np.empty((B, 2), np.float32)
-        idx = np.empty((B,), np.int32)
-        embed = np.empty((B, self.P), np.float32) if want_embed else None
-        self._check(self._lib.mv_forward(self._h, _ptr(ids), _ptr(lens), B, S, _ptr(logits), _ptr(probs), _ptr(best),
-                                         _ptr(idx), _ptr(embed)), "mv_forward")
+        out = _outputs(B, self.n_anchors, self.P, want_logits, want_probs, want_embed)
+        self._check(self._lib.mv_forward(self._h, _ptr(ids), _ptr(lens), B, S, _ptr(out["logits"]), _ptr(out["probs"]), _ptr(out["best"]),
+                                         _ptr(out["best_idx"]), _ptr(out["embed"])), "mv_forward")
         self._check_saturation()
-        return {"logits": logits, "probs": probs, "best": best, "best_idx": idx, "embed": embed}
+        return out
 
     # tokens below which one pad-to-longest pass is kept as it is (a pass of a few thousand tokens leaves most of the 256 persistent workgroups idle)
     BY_LENGTH_MIN_TOKENS = 16384
@@ -315,25 +315,20 @@ class Engine:
             min_tokens = self.BY_LENGTH_MIN_TOKENS
         if B == 0 or B * S < 2 * min_tokens:
             return self.forward(ids, lens, want_logits, want_probs, want_embed)
+        out = _outputs(B, self.n_anchors, self.P, want_logits, want_probs, want_embed)
         ragged = getattr(self, "_forward_ragged", None)  # (a stand-in engine of the tests has only `forward`)
-        if ragged is not None:
-            # everything below inside the library (mv_forward_ragged): ONE release of the interpreter lock per batch
-            out = {"logits": np.empty((B, self.n_anchors, 2), np.float32) if want_logits else None, "probs": np.empty((B, self.n_anchors, 2), np.float32) if want_probs else None,
-                   "best": np.empty((B, 2), np.float32), "best_idx": np.empty((B,), np.int32), "embed": np.empty((B, self.P), np.float32) if want_embed else None}
-            if ragged(ids, lens, min_tokens, out):
-                return out
+        if ragged is not None and ragged(ids, lens, min_tokens, out):
+            return out  # everything below inside the library (mv_forward_ragged): ONE release of the interpreter lock per batch
+        # a batch larger than one upload: the same grouping, one ``forward`` per group
         pl = np.where(lens <= 256, (np.maximum(lens, 1) + 63) // 64 * 64, (lens + 127) // 128 * 128).astype(np.int64)
         top = int(pl.max()) if B else 0
         if int(pl.min()) == top:  # one group: one call, at the group's own length
             return self.forward(np.ascontiguousarray(ids[:, :top]) if top < S else ids, lens, want_logits, want_probs, want_embed)
         # ONE gather into length order, the groups are then row slices of it and every pass writes its results straight into its slice of the
-        # length-ordered outputs (no per-group fancy indexing: that was 8 ms of the scorer thread's 15 ms per 512-report batch), ONE gather back
-        G = self.n_anchors
+        # length-ordered outputs (`out`; no per-group fancy indexing: that was 8 ms of the scorer thread's 15 ms per 512-report batch), ONE gather back
         order = np.argsort(pl, kind="stable")
         spl = pl[order]
         ids_s, lens_s = ids[order], lens[order]
-        bufs = {"logits": np.empty((B, G, 2), np.float32) if want_logits else None, "probs": np.empty((B, G, 2), np.float32) if want_probs else None,
-                "best": np.empty((B, 2), np.float32), "best_idx": np.empty((B,), np.int32), "embed": np.empty((B, self.P), np.float32) if want_embed else None}
         cuts = np.flatnonzero(np.diff(spl)) + 1  # group boundaries in the length order
         ends, widths, start = [], [], 0
         for end in list(cuts) + [B]:
@@ -342,29 +337,25 @@ class Engine:
                 continue  # too small a pass: these rows travel with the next longer group
             ends.append(int(end)); widths.append(min(S, width))
             start = end
-        groups = getattr(self, "_forward_groups", None)  # (a stand-in engine of the tests has only `forward`)
-        if groups is not None and groups(ids_s, lens_s, ends, widths, bufs):
-            pass  # ONE library call (mv_forward_groups): the passes back to back on the stream, one synchronisation, the GIL released once per batch
-        else:
-            start = 0
-            for end, width in zip(ends, widths):
-                sub = self.forward(np.ascontiguousarray(ids_s[start:end, :width]), lens_s[start:end], want_logits, want_probs, want_embed)
-                for k, v in sub.items():
-                    if v is not None and bufs.get(k) is not None:
-                        bufs[k][start:end] = v
-                start = end
+        start = 0
+        for end, width in zip(ends, widths):
+            sub = self.forward(np.ascontiguousarray(ids_s[start:end, :width]), lens_s[start:end], want_logits, want_probs, want_embed)
+            for k, v in sub.items():
+                if v is not None and out.get(k) is not None:
+                    out[k][start:end] = v
+            start = end
         inv = np.empty(B, np.int64)
         inv[order] = np.arange(B)
-        return {k: (v[inv] if v is not None else None) for k, v in bufs.items()}
+        return {k: (v[inv] if v is not None else None) for k, v in out.items()}
 
     def forward_by_length_begin(self, ids: np.ndarray, lens: np.ndarray, want_logits=True, want_probs=True, want_embed=False, min_tokens: Optional[int] = None):
         """``forward_by_length`` handed over without waiting for it (mv_forward_ragged_begin): returns a ticket for ``forward_by_length_end``.  One batch per
         workspace set may be in flight (two by default); collect in the order of the calls.  A batch the asynchronous entry cannot take (too small to be
-        worth grouping, too large for one upload, every workspace set busy) is scored at once and its ticket holds the results."""
+        worth grouping, too large for one upload, every workspace set busy: the library's MV_ERR_CAPACITY) is scored at once and its ticket holds the results."""
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         B, S = ids.shape
         mt = self.BY_LENGTH_MIN_TOKENS if min_tokens is None else min_tokens
-        if B > 0 and B * S >= 2 * mt and len(self._tickets) < 2:
+        if B > 0 and B * S >= 2 * mt:
             t = C.c_int(-1)
             rc = self._lib.mv_forward_ragged_begin(self._h, _ptr(ids), _ptr(lens), B, S, int(mt), int(want_logits), int(want_probs), int(want_embed), C.byref(t))
             if rc == 0:
@@ -375,14 +366,13 @@ class Engine:
         return ("done", self.forward_by_length(ids, lens, want_logits, want_probs, want_embed, min_tokens))
 
     def forward_by_length_end(self, ticket):
+        """The results of a ``forward_by_length_begin`` ticket.  Collecting consumes the ticket, also when this call raises."""
         if ticket[0] == "done":
             return ticket[1]
         _, t, B, want_logits, want_probs, want_embed = ticket
         if not self._tickets or self._tickets[0] != t:
             raise RuntimeError("forward_by_length_end: tickets are collected in the order they were issued")
-        G = self.n_anchors
-        out = {"logits": np.empty((B, G, 2), np.float32) if want_logits else None, "probs": np.empty((B, G, 2), np.float32) if want_probs else None,
-               "best": np.empty((B, 2), np.float32), "best_idx": np.empty((B,), np.int32), "embed": np.empty((B, self.P), np.float32) if want_embed else None}
+        out = _outputs(B, self.n_anchors, self.P, want_logits, want_probs, want_embed)
         self._tickets.pop(0)
         self._check(self._lib.mv_forward_ragged_end(self._h, t, _ptr(out["logits"]), _ptr(out["probs"]), _ptr(out["best"]), _ptr(out["best_idx"]), _ptr(out["embed"])),
                     "mv_forward_ragged_end")
@@ -398,19 +388,6 @@ class Engine:
         if rc == -5:  # MV_ERR_CAPACITY (checked before any GPU work)
             return False
         self._check(rc, "mv_forward_ragged")
-        self._check_saturation()
-        return True
-
-    def _forward_groups(self, ids: np.ndarray, lens: np.ndarray, ends, widths, out: Dict[str, Optional[np.ndarray]]) -> bool:
-        """mv_forward_groups into the caller's arrays (rows in length order); False = the batch does not fit one upload (max_batch / max_tokens): the caller
-        walks the groups with ``forward``."""
-        B, S = ids.shape
-        ge, gw = np.asarray(ends, np.int32), np.asarray(widths, np.int32)
-        rc = self._lib.mv_forward_groups(self._h, _ptr(ids), _ptr(lens), B, S, len(ge), _ptr(ge), _ptr(gw), _ptr(out.get("logits")), _ptr(out.get("probs")),
-                                         _ptr(out["best"]), _ptr(out["best_idx"]), _ptr(out.get("embed")))
-        if rc == -5:  # MV_ERR_CAPACITY (checked before any GPU work)
-            return False
-        self._check(rc, "mv_forward_groups")
         self._check_saturation()
         return True
 

@@ -148,6 +148,13 @@ struct Work {
   int32_t* tile_both = nullptr;  // cls_aside: per 256-row tile of the pass, non-zero = its sequence is shorter than cls_min_len (GemmArgs::tile_both)
 };
 
+// host staging of one by-length batch (mv_forward_ragged*): its rows gathered in length order, its results before they go back to the caller's row order
+// (NULL: an output not asked for)
+struct RaggedStage {
+  int32_t *ids = nullptr, *lens = nullptr, *idx = nullptr;
+  float *logits = nullptr, *probs = nullptr, *best = nullptr, *embed = nullptr;
+};
+
 struct mv_handle {
   int device = 0;
   mv_config cfg{};
@@ -184,17 +191,16 @@ struct mv_handle {
   // resident corpus
   int32_t *c_ids = nullptr, *c_lens = nullptr;
   std::vector<int32_t> c_lens_host;  // the lengths as uploaded (encode_dev's min_len of each pass)
-  struct {  // mv_forward_ragged: the batch in length order and its results before they go back to the caller's row order
+  struct {  // mv_forward_ragged: the storage of its staging
     std::vector<int32_t> ids, lens, idx;
     std::vector<float> logits, probs, best, embed;
   } ragged;
   struct RaggedSlot {  // mv_forward_ragged_begin / _end: one batch in flight per workspace set, its staging in PINNED host memory (the copies really are asynchronous)
     bool busy = false;
-    int B = 0, G = 0;
-    bool logits = false, probs = false, embed = false;
+    int G = 0;
     std::vector<int> order;
-    int32_t *ids = nullptr, *lens = nullptr, *idx = nullptr;   // [cap_tokens], [max_batch], [max_batch]
-    float *lg = nullptr, *pr = nullptr, *best = nullptr, *emb = nullptr;  // [max_batch][max_anchors][2] x 2, [max_batch][2], [max_batch][P]
+    RaggedStage pin;  // allocated once: [cap_tokens], [max_batch], [max_batch], [max_batch][max_anchors][2] x 2, [max_batch][2], [max_batch][P]
+    RaggedStage st;   // the batch in flight's: `pin` without the outputs it was not asked for
   } rslot[2];
   int rnext = 0;
   std::vector<void*> pinned;
@@ -1416,107 +1422,10 @@ int mv_forward(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int
   return MV_OK;
 } catch (...) { return on_exception(h); }
 
-// mv_forward over a batch whose rows are ordered by length and cut into groups: group g = rows [group_end[g - 1], group_end[g]) runs as ONE pass at
-// group_width[g] tokens per row (the rows' ids are read in place from the [B][S] upload: pitch S), all groups back to back on the handle's stream, one
-// synchronisation at the end (binding.Engine.forward_by_length: a pad-to-longest batch of unsorted reports without its padding, one library call per batch).
-int mv_forward_groups(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int n_groups, const int32_t* group_end,
-                      const int32_t* group_width, float* logits, float* probs, float* best, int32_t* best_idx, float* embed) try {
-  if (int rc = check_ready(h)) return rc;
-  if (!ids || !lens || !group_end || !group_width || B <= 0 || S <= 0 || S > h->cfg.max_pos || n_groups <= 0)
-    return fail(h, MV_ERR_INVALID, "mv_forward_groups: bad argument");
-  if (h->n_anchors <= 0) return fail(h, MV_ERR_STATE, "anchor bank is empty (call mv_anchor_append / mv_anchor_set first)");
-  if (B > h->cfg.max_batch || (int64_t)B * S > h->cap_tokens) return fail(h, MV_ERR_CAPACITY, "mv_forward_groups: the batch exceeds mv_config.max_batch / max_tokens");
-  int prev = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    const int nb = group_end[g] - prev, w = group_width[g];
-    if (nb <= 0 || w <= 0 || w > S) return fail(h, MV_ERR_INVALID, "mv_forward_groups: groups must be non-empty, in order, at most S tokens wide");
-    if (nb > max_rows_for(h, w)) return fail(h, MV_ERR_CAPACITY, "mv_forward_groups: a group exceeds one pass (mv_config.max_tokens)");
-    for (int i = prev; i < group_end[g]; ++i)
-      if (lens[i] > w) return fail(h, MV_ERR_INVALID, "mv_forward_groups: a row is longer than its group's width");
-    prev = group_end[g];
-  }
-  if (prev != B) return fail(h, MV_ERR_INVALID, "mv_forward_groups: the groups must cover the batch");
-  if (int rc = check_ids(h, ids, (int64_t)B * S, "mv_forward_groups")) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  const int G = h->n_anchors;
-  HIPCHK(h, hipMemcpyAsync(h->w->d_ids, ids, (size_t)B * S * 4, hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipMemcpyAsync(h->w->d_lens, lens, (size_t)B * 4, hipMemcpyHostToDevice, h->w->stream));
-  prev = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    const int nb = group_end[g] - prev;
-    float* u = h->w->u + (size_t)prev * h->P;
-    if (int rc = encode_dev(h, h->w->d_ids + (size_t)prev * S, h->w->d_lens + prev, pass_min_len(lens + prev, nb), nb, group_width[g], -1, u, false, S)) return rc;
-    if (int rc = match_dev(h, u, nb, logits ? h->w->logits + (size_t)prev * G * 2 : nullptr, probs ? h->w->probs + (size_t)prev * G * 2 : nullptr, nullptr, 1,
-                           h->w->best + (size_t)prev * 2, h->w->best_idx + prev)) return rc;
-    prev = group_end[g];
-  }
-  const size_t bg = (size_t)B * G;
-  if (logits) HIPCHK(h, hipMemcpyAsync(logits, h->w->logits, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
-  if (probs) HIPCHK(h, hipMemcpyAsync(probs, h->w->probs, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
-  if (best) HIPCHK(h, hipMemcpyAsync(best, h->w->best, (size_t)B * 8, hipMemcpyDeviceToHost, h->w->stream));
-  if (best_idx) HIPCHK(h, hipMemcpyAsync(best_idx, h->w->best_idx, (size_t)B * 4, hipMemcpyDeviceToHost, h->w->stream));
-  if (embed) HIPCHK(h, hipMemcpyAsync(embed, h->w->u, (size_t)B * h->P * 4, hipMemcpyDeviceToHost, h->w->stream));
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
-  return MV_OK;
-} catch (...) { return on_exception(h); }
-
-// mv_forward on a pad-to-longest batch of UNSORTED rows, all of binding.Engine.forward_by_length inside ONE call: the rows ordered (stably) by the padded length of
-// their own token count, cut into groups (a group of fewer than min_tokens padded tokens travels with the next longer one), gathered on the host, scored by
-// mv_forward_groups, and the results put back in the caller's row order.  One call = one release of the caller's interpreter lock per batch: next to two other
-// Python threads every release cost the scoring thread ~10 ms of waiting (profiles/r06_*_e2e_dropin.txt).
-int mv_forward_ragged(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int min_tokens, float* logits, float* probs, float* best,
-                      int32_t* best_idx, float* embed) try {
-  if (int rc = check_ready(h)) return rc;
-  if (!ids || !lens || B <= 0 || S <= 0 || S > h->cfg.max_pos || !best || !best_idx) return fail(h, MV_ERR_INVALID, "mv_forward_ragged: bad argument");
-  if (B > h->cfg.max_batch || (int64_t)B * S > h->cap_tokens) return fail(h, MV_ERR_CAPACITY, "mv_forward_ragged: the batch exceeds mv_config.max_batch / max_tokens");
-  const int G = h->n_anchors;
-  std::vector<int> pl(B), order(B);
-  for (int i = 0; i < B; ++i) {
-    if (lens[i] > S) return fail(h, MV_ERR_INVALID, "mv_forward_ragged: a row is longer than S");
-    pl[i] = padded_len(lens[i] < 1 ? 1 : lens[i]);
-    order[i] = i;
-  }
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pl[a] < pl[b]; });
-  std::vector<int32_t> ends, widths;
-  int start = 0;
-  for (int end = 1; end <= B; ++end) {
-    if (end < B && pl[order[end]] == pl[order[end - 1]]) continue;  // inside a run of one padded length
-    const int width = pl[order[end - 1]];
-    if (end < B && (int64_t)(end - start) * width < min_tokens) continue;  // too small a pass: these rows travel with the next longer group
-    ends.push_back(end);
-    widths.push_back(width < S ? width : S);
-    start = end;
-  }
-  auto& st = h->ragged;
-  st.ids.resize((size_t)B * S);
-  st.lens.resize(B);
-  for (int i = 0; i < B; ++i) {
-    std::memcpy(st.ids.data() + (size_t)i * S, ids + (size_t)order[i] * S, (size_t)S * 4);
-    st.lens[i] = lens[order[i]];
-  }
-  if (logits) st.logits.resize((size_t)B * G * 2);
-  if (probs) st.probs.resize((size_t)B * G * 2);
-  st.best.resize((size_t)B * 2);
-  st.idx.resize(B);
-  if (embed) st.embed.resize((size_t)B * h->P);
-  if (int rc = mv_forward_groups(h, st.ids.data(), st.lens.data(), B, S, (int)ends.size(), ends.data(), widths.data(), logits ? st.logits.data() : nullptr,
-                                 probs ? st.probs.data() : nullptr, st.best.data(), st.idx.data(), embed ? st.embed.data() : nullptr)) return rc;
-  const size_t g2 = (size_t)G * 2;
-  for (int i = 0; i < B; ++i) {
-    const size_t o = (size_t)order[i];
-    if (logits) std::memcpy(logits + o * g2, st.logits.data() + (size_t)i * g2, g2 * 4);
-    if (probs) std::memcpy(probs + o * g2, st.probs.data() + (size_t)i * g2, g2 * 4);
-    best[o * 2] = st.best[(size_t)i * 2]; best[o * 2 + 1] = st.best[(size_t)i * 2 + 1];
-    best_idx[o] = st.idx[i];
-    if (embed) std::memcpy(embed + o * h->P, st.embed.data() + (size_t)i * h->P, (size_t)h->P * 4);
-  }
-  return MV_OK;
-} catch (...) { return on_exception(h); }
-
-// mv_forward_ragged in two halves, so that the caller can hand over batch k + 1 BEFORE it collects batch k: `begin` orders and groups the rows, gathers them into
-// pinned memory, enqueues upload + passes + download on the stream of the next workspace set and returns a ticket without waiting; `end` waits for that stream and puts
-// the results into the caller's arrays in the caller's row order.  At most one batch per workspace set (MEMVUL_STREAMS: 2) is in flight; tickets are collected in
-// the order they were issued.  The GPU then never waits for the caller's Python between two batches (predict_memory.evaluate).
+// ---- by length: mv_forward on a pad-to-longest batch of UNSORTED rows (binding.Engine.forward_by_length) ----------------------------------------------------------
+// The rows are ordered (stably) by the padded length of their own token count and cut into groups (a group of fewer than min_tokens padded tokens travels with the
+// next longer one), each group is ONE pass at its own width, all passes back to back on one stream, and the results go back to the caller's row order.
+// ragged_plan: the order and the groups (group g = rows [ends[g - 1], ends[g]) of the length order at widths[g] tokens per row); every group fits one pass.
 static int ragged_plan(mv_handle* h, const int32_t* lens, int B, int S, int min_tokens, std::vector<int>& order, std::vector<int32_t>& ends, std::vector<int32_t>& widths) {
   std::vector<int> pl(B);
   order.resize(B);
@@ -1539,6 +1448,92 @@ static int ragged_plan(mv_handle* h, const int32_t* lens, int B, int S, int min_
   return MV_OK;
 }
 
+// The rows gathered into st in length order, then enqueued on workspace set `wk` without waiting: upload, one pass per group (its ids read in place from the
+// [B][S] upload: pitch S), download of the outputs st holds.  After a failure it waits for what was enqueued.
+static int ragged_enqueue(mv_handle* h, Work* wk, const int32_t* ids, const int32_t* lens, int S, const std::vector<int>& order, const std::vector<int32_t>& ends,
+                          const std::vector<int32_t>& widths, const RaggedStage& st) {
+  const int B = (int)order.size(), G = h->n_anchors;
+  for (int i = 0; i < B; ++i) {
+    std::memcpy(st.ids + (size_t)i * S, ids + (size_t)order[i] * S, (size_t)S * 4);
+    st.lens[i] = lens[order[i]];
+  }
+  Work* keep = h->w;
+  h->w = wk;
+  auto run = [&]() -> int {
+    HIPCHK(h, hipMemcpyAsync(h->w->d_ids, st.ids, (size_t)B * S * 4, hipMemcpyHostToDevice, h->w->stream));
+    HIPCHK(h, hipMemcpyAsync(h->w->d_lens, st.lens, (size_t)B * 4, hipMemcpyHostToDevice, h->w->stream));
+    int prev = 0;
+    for (size_t g = 0; g < ends.size(); ++g) {
+      const int nb = ends[g] - prev;
+      float* u = h->w->u + (size_t)prev * h->P;
+      if (int rc = encode_dev(h, h->w->d_ids + (size_t)prev * S, h->w->d_lens + prev, pass_min_len(st.lens + prev, nb), nb, widths[g], -1, u, false, S)) return rc;
+      // only the outputs the caller asked for leave the kernel (the best anchor always does)
+      if (int rc = match_dev(h, u, nb, st.logits ? h->w->logits + (size_t)prev * G * 2 : nullptr, st.probs ? h->w->probs + (size_t)prev * G * 2 : nullptr, nullptr, 1,
+                             h->w->best + (size_t)prev * 2, h->w->best_idx + prev)) return rc;
+      prev = ends[g];
+    }
+    const size_t bg = (size_t)B * G;
+    if (st.logits) HIPCHK(h, hipMemcpyAsync(st.logits, h->w->logits, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
+    if (st.probs) HIPCHK(h, hipMemcpyAsync(st.probs, h->w->probs, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
+    HIPCHK(h, hipMemcpyAsync(st.best, h->w->best, (size_t)B * 8, hipMemcpyDeviceToHost, h->w->stream));
+    HIPCHK(h, hipMemcpyAsync(st.idx, h->w->best_idx, (size_t)B * 4, hipMemcpyDeviceToHost, h->w->stream));
+    if (st.embed) HIPCHK(h, hipMemcpyAsync(st.embed, h->w->u, (size_t)B * h->P * 4, hipMemcpyDeviceToHost, h->w->stream));
+    return MV_OK;
+  };
+  const int rc = run();
+  h->w = keep;
+  if (rc != MV_OK) hipStreamSynchronize(wk->stream);
+  return rc;
+}
+
+// Row i of the length order (st) to row order[i] of the caller's arrays: the outputs st holds.
+static void ragged_scatter(const mv_handle* h, const std::vector<int>& order, int G, const RaggedStage& st, float* logits, float* probs, float* best, int32_t* best_idx,
+                           float* embed) {
+  const size_t g2 = (size_t)G * 2, P = (size_t)h->P;
+  for (size_t i = 0; i < order.size(); ++i) {
+    const size_t o = (size_t)order[i];
+    if (st.logits) std::memcpy(logits + o * g2, st.logits + i * g2, g2 * 4);
+    if (st.probs) std::memcpy(probs + o * g2, st.probs + i * g2, g2 * 4);
+    best[o * 2] = st.best[i * 2]; best[o * 2 + 1] = st.best[i * 2 + 1];
+    best_idx[o] = st.idx[i];
+    if (st.embed) std::memcpy(embed + o * P, st.embed + i * P, P * 4);
+  }
+}
+
+// The whole flow in ONE call on workspace set 0: one release of the caller's interpreter lock per batch (next to two other Python threads every release cost the
+// scoring thread ~10 ms of waiting: profiles/r06_*_e2e_dropin.txt).
+int mv_forward_ragged(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int min_tokens, float* logits, float* probs, float* best,
+                      int32_t* best_idx, float* embed) try {
+  if (int rc = check_ready(h)) return rc;
+  if (!ids || !lens || B <= 0 || S <= 0 || S > h->cfg.max_pos || !best || !best_idx) return fail(h, MV_ERR_INVALID, "mv_forward_ragged: bad argument");
+  if (h->n_anchors <= 0) return fail(h, MV_ERR_STATE, "anchor bank is empty (call mv_anchor_append / mv_anchor_set first)");
+  if (B > h->cfg.max_batch || (int64_t)B * S > h->cap_tokens) return fail(h, MV_ERR_CAPACITY, "mv_forward_ragged: the batch exceeds mv_config.max_batch / max_tokens");
+  std::vector<int> order;
+  std::vector<int32_t> ends, widths;
+  if (int rc = ragged_plan(h, lens, B, S, min_tokens, order, ends, widths)) return rc;
+  if (int rc = check_ids(h, ids, (int64_t)B * S, "mv_forward_ragged")) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const int G = h->n_anchors;
+  auto& v = h->ragged;
+  v.ids.resize((size_t)B * S);
+  v.lens.resize(B);
+  if (logits) v.logits.resize((size_t)B * G * 2);
+  if (probs) v.probs.resize((size_t)B * G * 2);
+  v.best.resize((size_t)B * 2);
+  v.idx.resize(B);
+  if (embed) v.embed.resize((size_t)B * h->P);
+  const RaggedStage st{v.ids.data(), v.lens.data(), v.idx.data(), logits ? v.logits.data() : nullptr, probs ? v.probs.data() : nullptr, v.best.data(),
+                       embed ? v.embed.data() : nullptr};
+  if (int rc = ragged_enqueue(h, &h->work[0], ids, lens, S, order, ends, widths, st)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->work[0].stream));
+  ragged_scatter(h, order, G, st, logits, probs, best, best_idx, embed);
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+// mv_forward_ragged in two halves, so that the caller can hand over batch k + 1 BEFORE it collects batch k: `begin` enqueues the batch on the next workspace set
+// into its pinned staging and returns a ticket without waiting; `end` waits for that set's stream and scatters the results.  At most one batch per workspace set
+// (MEMVUL_STREAMS: 2) is in flight; tickets are collected in the order they were issued.  The GPU then never waits for the caller's Python between two batches
+// (predict_memory.evaluate).
 int mv_forward_ragged_begin(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int min_tokens, int want_logits, int want_probs, int want_embed,
                             int* ticket) try {
   if (int rc = check_ready(h)) return rc;
@@ -1547,62 +1542,33 @@ int mv_forward_ragged_begin(mv_handle* h, const int32_t* ids, const int32_t* len
   if (B > h->cfg.max_batch || (int64_t)B * S > h->cap_tokens) return fail(h, MV_ERR_CAPACITY, "mv_forward_ragged_begin: the batch exceeds mv_config.max_batch / max_tokens");
   const int slot = h->rnext % (h->n_alloc < 2 ? 1 : 2);
   auto& rs = h->rslot[slot];
-  if (rs.busy) return fail(h, MV_ERR_STATE, "mv_forward_ragged_begin: the workspace set's previous batch has not been collected (mv_forward_ragged_end)");
+  if (rs.busy) return fail(h, MV_ERR_CAPACITY, "mv_forward_ragged_begin: every workspace set has a batch in flight (score this one with mv_forward_ragged)");
   std::vector<int32_t> ends, widths;
   if (int rc = ragged_plan(h, lens, B, S, min_tokens, rs.order, ends, widths)) return rc;
   if (int rc = check_ids(h, ids, (int64_t)B * S, "mv_forward_ragged_begin")) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const int G = h->n_anchors;
-  if (!rs.ids) {  // pinned staging of this slot, once
+  if (!rs.pin.ids) {  // pinned staging of this slot, once
     const size_t mb = (size_t)h->cfg.max_batch, bg2 = mb * (size_t)h->cfg.max_anchors * 2;
     auto pin = [&](void** p, size_t bytes) -> int {
       if (hipHostMalloc(p, bytes, hipHostMallocDefault) != hipSuccess) return fail(h, MV_ERR_NOMEM, "hipHostMalloc failed (mv_forward_ragged_begin)");
       h->pinned.push_back(*p);
       return MV_OK;
     };
-    int rc = pin((void**)&rs.ids, (size_t)h->cap_tokens * 4);
-    if (!rc) rc = pin((void**)&rs.lens, mb * 4);
-    if (!rc) rc = pin((void**)&rs.idx, mb * 4);
-    if (!rc) rc = pin((void**)&rs.lg, bg2 * 4);
-    if (!rc) rc = pin((void**)&rs.pr, bg2 * 4);
-    if (!rc) rc = pin((void**)&rs.best, mb * 2 * 4);
-    if (!rc) rc = pin((void**)&rs.emb, mb * (size_t)h->P * 4);
-    if (rc) { rs.ids = nullptr; return rc; }
+    int rc = pin((void**)&rs.pin.ids, (size_t)h->cap_tokens * 4);
+    if (!rc) rc = pin((void**)&rs.pin.lens, mb * 4);
+    if (!rc) rc = pin((void**)&rs.pin.idx, mb * 4);
+    if (!rc) rc = pin((void**)&rs.pin.logits, bg2 * 4);
+    if (!rc) rc = pin((void**)&rs.pin.probs, bg2 * 4);
+    if (!rc) rc = pin((void**)&rs.pin.best, mb * 2 * 4);
+    if (!rc) rc = pin((void**)&rs.pin.embed, mb * (size_t)h->P * 4);
+    if (rc) { rs.pin.ids = nullptr; return rc; }
   }
-  for (int i = 0; i < B; ++i) {
-    std::memcpy(rs.ids + (size_t)i * S, ids + (size_t)rs.order[i] * S, (size_t)S * 4);
-    rs.lens[i] = lens[rs.order[i]];
-  }
-  Work* keep = h->w;
-  h->w = &h->work[slot];
-  auto run = [&]() -> int {
-    HIPCHK(h, hipMemcpyAsync(h->w->d_ids, rs.ids, (size_t)B * S * 4, hipMemcpyHostToDevice, h->w->stream));
-    HIPCHK(h, hipMemcpyAsync(h->w->d_lens, rs.lens, (size_t)B * 4, hipMemcpyHostToDevice, h->w->stream));
-    int prev = 0;
-    for (size_t g = 0; g < ends.size(); ++g) {
-      const int nb = ends[g] - prev;
-      float* u = h->w->u + (size_t)prev * h->P;
-      if (int rc = encode_dev(h, h->w->d_ids + (size_t)prev * S, h->w->d_lens + prev, pass_min_len(rs.lens + prev, nb), nb, widths[g], -1, u, false, S)) return rc;
-      if (int rc = match_dev(h, u, nb, want_logits ? h->w->logits + (size_t)prev * G * 2 : nullptr, want_probs ? h->w->probs + (size_t)prev * G * 2 : nullptr, nullptr, 1,
-                             h->w->best + (size_t)prev * 2, h->w->best_idx + prev)) return rc;
-      prev = ends[g];
-    }
-    const size_t bg = (size_t)B * G;
-    if (want_logits) HIPCHK(h, hipMemcpyAsync(rs.lg, h->w->logits, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
-    if (want_probs) HIPCHK(h, hipMemcpyAsync(rs.pr, h->w->probs, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
-    HIPCHK(h, hipMemcpyAsync(rs.best, h->w->best, (size_t)B * 8, hipMemcpyDeviceToHost, h->w->stream));
-    HIPCHK(h, hipMemcpyAsync(rs.idx, h->w->best_idx, (size_t)B * 4, hipMemcpyDeviceToHost, h->w->stream));
-    if (want_embed) HIPCHK(h, hipMemcpyAsync(rs.emb, h->w->u, (size_t)B * h->P * 4, hipMemcpyDeviceToHost, h->w->stream));
-    return MV_OK;
-  };
-  const int rc = run();
-  h->w = keep;
-  if (rc != MV_OK) {
-    hipStreamSynchronize(h->work[slot].stream);
-    return rc;
-  }
-  rs.busy = true; rs.B = B; rs.G = G;
-  rs.logits = want_logits != 0; rs.probs = want_probs != 0; rs.embed = want_embed != 0;
+  RaggedStage st = rs.pin;
+  if (!want_logits) st.logits = nullptr;
+  if (!want_probs) st.probs = nullptr;
+  if (!want_embed) st.embed = nullptr;
+  if (int rc = ragged_enqueue(h, &h->work[slot], ids, lens, S, rs.order, ends, widths, st)) return rc;
+  rs.busy = true; rs.G = h->n_anchors; rs.st = st;
   *ticket = slot;
   h->rnext += 1;
   return MV_OK;
@@ -1615,17 +1581,9 @@ int mv_forward_ragged_end(mv_handle* h, int ticket, float* logits, float* probs,
   const hipError_t e = hipStreamSynchronize(h->work[ticket].stream);
   rs.busy = false;
   if (e != hipSuccess) return fail(h, MV_ERR_HIP, std::string("mv_forward_ragged_end: ") + hipGetErrorString(e));
-  if (!best || !best_idx || (rs.logits && !logits) || (rs.probs && !probs) || (rs.embed && !embed))
+  if (!best || !best_idx || (rs.st.logits && !logits) || (rs.st.probs && !probs) || (rs.st.embed && !embed))
     return fail(h, MV_ERR_INVALID, "mv_forward_ragged_end: an output the batch was started with is missing");
-  const size_t g2 = (size_t)rs.G * 2;
-  for (int i = 0; i < rs.B; ++i) {
-    const size_t o = (size_t)rs.order[i];
-    if (rs.logits) std::memcpy(logits + o * g2, rs.lg + (size_t)i * g2, g2 * 4);
-    if (rs.probs) std::memcpy(probs + o * g2, rs.pr + (size_t)i * g2, g2 * 4);
-    best[o * 2] = rs.best[(size_t)i * 2]; best[o * 2 + 1] = rs.best[(size_t)i * 2 + 1];
-    best_idx[o] = rs.idx[i];
-    if (rs.embed) std::memcpy(embed + o * h->P, rs.emb + (size_t)i * h->P, (size_t)h->P * 4);
-  }
+  ragged_scatter(h, rs.order, rs.G, rs.st, logits, probs, best, best_idx, embed);
   return MV_OK;
 } catch (...) { return on_exception(h); }
 

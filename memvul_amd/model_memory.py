@@ -297,7 +297,7 @@ class ModelMemory(Model):
 
     def forward_end(self, pending) -> Dict[str, Any]:
         """... and is collected here, where the metric accumulators are updated: ``forward_end(forward_begin(**batch))`` is ``forward(**batch)`` (model_memory.py:118-167),
-        and batches collected in the order they were begun update the metrics in the reference's order."""
+        and batches collected in the order they were begun update the metrics in the reference's order.  Collecting consumes the ticket, also when this call raises."""
         if pending[0] == "done":
             return pending[1]
         _, ticket, label, metadata = pending

@@ -68,6 +68,7 @@ def evaluate(model, data_loader, cuda_device: int = -1, batch_weight_key: str = 
         # a model with forward_begin / forward_end (ModelMemory): batch k + 1 is handed to the engine BEFORE batch k is collected, so the GPU does not wait for
         # this thread's Python — or for the interpreter lock it shares with the two others — between batches; collected in order: the same calls in the same
         # order on the metric accumulators.  Any other model: model(**batch), as AllenNLP's evaluate calls it.
+        # `pending` is the batch begun and not yet collected; a collect consumes its batch even when it raises (ModelMemory.forward_end).
         two_halves = hasattr(model, "forward_begin") and hasattr(model, "forward_end")
         pending = None
         try:
@@ -79,11 +80,10 @@ def evaluate(model, data_loader, cuda_device: int = -1, batch_weight_key: str = 
                 if batch is None:
                     break
                 if two_halves:
-                    nxt = model.forward_begin(**batch)
-                    out = model.forward_end(pending) if pending is not None else None
-                    pending = nxt
-                    if out is None:
+                    prev, pending = pending, model.forward_begin(**batch)
+                    if prev is None:
                         continue
+                    out = model.forward_end(prev)
                 else:
                     out = model(**batch)
                 if predictions_output_file:

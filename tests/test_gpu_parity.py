@@ -653,10 +653,12 @@ def test_length_bucketed_sweep_matches_padded_sweep(gu, compute):
 
 
 @pytest.mark.parametrize("compute", ["precise", "f16"])
-def test_forward_by_length_matches_the_padded_forward(gu, compute):
-    """Engine.forward_by_length (what ModelMemory.forward calls): the rows of a pad-to-longest batch grouped by their own padded length, one mv_forward per
-    group, results back in place.  Same per-row mathematics as the one padded pass at a different padded length: probabilities agree at the fp16-operand
-    level, decisions wherever the top-2 margin is clear; rows of the longest group ran at the batch's own length in both forms and (MV_F16X8) agree bit for bit."""
+def test_forward_by_length_and_its_two_halves_match_the_padded_forward(gu, compute):
+    """Engine.forward_by_length (what ModelMemory.forward calls): the rows of a pad-to-longest batch grouped by their own padded length, one pass per group,
+    results back in place.  Same per-row mathematics as the one padded pass at a different padded length: probabilities agree at the fp16-operand level,
+    decisions wherever the top-2 margin is clear; rows of the longest group ran at the batch's own length in both forms and (MV_F16X8) agree bit for bit.
+    The one library call, the Python per-group walk and the two halves (begin / end, with every workspace set busy, and with one workspace set) give the
+    same bits."""
     dk, wk = dict(layers=3, vocab_size=2048), dict(qk_scale=2.0, match_scale=6.0)
     dims, w = gu.weights_for(dk, wk)
     eng = gu.engine_for(dk, wk, compute_dtype=compute, max_tokens=128 * 512, max_batch=128, max_anchors=32)
@@ -665,17 +667,13 @@ def test_forward_by_length_matches_the_padded_forward(gu, compute):
     eng.anchor_set(synth.make_anchor_bank(24))
     a = eng.forward(ids, lens)
     b = eng.forward_by_length(ids, lens, min_tokens=4096)
-    # b came from ONE mv_forward_ragged call; the same grouping done in Python around mv_forward_groups, and around one mv_forward per group: the same bits
+    # b came from ONE mv_forward_ragged call; the same grouping done in Python around one mv_forward per group: the same bits
     eng._forward_ragged = None
     try:
-        c = eng.forward_by_length(ids, lens, min_tokens=4096)
-        eng._forward_groups = None
         d2 = eng.forward_by_length(ids, lens, min_tokens=4096)
     finally:
         del eng._forward_ragged
-        if "_forward_groups" in eng.__dict__:
-            del eng._forward_groups
-    assert all(np.array_equal(b[k], c[k]) and np.array_equal(b[k], d2[k]) for k in ("logits", "probs", "best", "best_idx"))
+    assert all(np.array_equal(b[k], d2[k]) for k in ("logits", "probs", "best", "best_idx"))
     e1 = eng.forward_by_length(ids, lens, want_logits=False, want_embed=True, min_tokens=4096)
     assert e1["logits"] is None and np.array_equal(e1["probs"], b["probs"]) and np.array_equal(e1["embed"], eng.forward_by_length(ids, lens, want_embed=True, min_tokens=4096)["embed"])
     d = float(np.abs(a["probs"] - b["probs"]).max())
@@ -696,18 +694,25 @@ def test_forward_by_length_matches_the_padded_forward(gu, compute):
     assert t1[0] == "pending" and t2[0] == "pending"
     t3 = eng.forward_by_length_begin(ids[:16], lens[:16])  # too small to be worth grouping: scored at once, next to the two in flight
     assert t3[0] == "done"
+    t4 = eng.forward_by_length_begin(ids, lens, min_tokens=4096)  # every workspace set busy (the library's MV_ERR_CAPACITY): scored at once, behind the two in flight
+    assert t4[0] == "done" and all(np.array_equal(t4[1][k], b[k]) for k in ("logits", "probs", "best", "best_idx"))
     with pytest.raises(RuntimeError):
         eng.forward_by_length_end(t2)  # out of order
     r1, r2, r3 = eng.forward_by_length_end(t1), eng.forward_by_length_end(t2), eng.forward_by_length_end(t3)
     assert all(np.array_equal(r1[k], b[k]) for k in ("logits", "probs", "best", "best_idx"))
     assert r2["logits"] is None and np.array_equal(r2["probs"], b["probs"][::-1]) and np.array_equal(r2["best_idx"], b["best_idx"][::-1])
     assert np.array_equal(r3["probs"], eng.forward(ids[:16], lens[:16])["probs"])
-    # mv_forward_groups rejects what it cannot run as handed over (before any GPU work)
-    bufs = {"logits": None, "probs": None, "best": np.empty((128, 2), np.float32), "best_idx": np.empty(128, np.int32), "embed": None}
-    for ends, widths in (([64], [512]), ([128], [64]), ([64, 64], [512, 512]), ([64, 128], [512, 600])):  # not the whole batch / a row longer than its group / empty group / wider than S
-        with pytest.raises(RuntimeError):
-            eng._forward_groups(ids, lens, ends, widths, bufs)
     eng.anchor_reset()
+    # one workspace set (MEMVUL_STREAMS=1): the second batch begun while the first is in flight is scored at once; both the bits of the one-call form
+    eng1 = gu.engine_for(dk, wk, compute_dtype=compute, max_tokens=128 * 512, max_batch=128, max_anchors=32, env={"MEMVUL_STREAMS": "1"})
+    eng1.anchor_set(synth.make_anchor_bank(24))
+    b1 = eng1.forward_by_length(ids, lens, min_tokens=4096)
+    t1 = eng1.forward_by_length_begin(ids, lens, min_tokens=4096)
+    t2 = eng1.forward_by_length_begin(ids, lens, min_tokens=4096)
+    assert t1[0] == "pending" and t2[0] == "done"
+    for r in (eng1.forward_by_length_end(t1), eng1.forward_by_length_end(t2)):
+        assert all(np.array_equal(r[k], b1[k]) for k in ("logits", "probs", "best", "best_idx"))
+    eng1.anchor_reset()
 
 
 @pytest.mark.parametrize("gemm_tile,compute", PATHS)

@@ -304,7 +304,8 @@ def test_native_record_formatter_prints_what_json_dumps_prints():
 def test_evaluate_keeps_one_batch_in_flight_and_collects_in_order(tmp_path):
     """predict_memory.evaluate with a model that scores in two halves (ModelMemory.forward_begin / forward_end): batch k + 1 is begun BEFORE batch k is
     collected, every batch is collected exactly once and in order (the metric accumulators see the reference's order, predict_memory.py:103-110), the records
-    come out in order, and an error in either half surfaces on the caller's thread with nothing left in flight.  Host logic only: a recording stand-in."""
+    come out in order, and an error in either half surfaces on the caller's thread with nothing left in flight and no batch collected twice (a collect consumes its
+    batch even when it raises).  Host logic only: a recording stand-in that tracks WHICH batches are in flight."""
     from memvul_amd.predict_memory import evaluate
 
     class Model:
@@ -312,7 +313,7 @@ def test_evaluate_keeps_one_batch_in_flight_and_collects_in_order(tmp_path):
         _golden_labels = ["CWE-1", "CWE-2"]
 
         def __init__(self, fail_at=None):
-            self.log, self.in_flight, self.max_in_flight, self.fail_at = [], 0, 0, fail_at
+            self.log, self.in_flight, self.max_in_flight, self.stray, self.fail_at = [], set(), 0, [], fail_at
 
         def eval(self):
             pass
@@ -322,13 +323,15 @@ def test_evaluate_keeps_one_batch_in_flight_and_collects_in_order(tmp_path):
             if self.fail_at == ("begin", k):
                 raise ValueError("begin %d" % k)
             self.log.append(("begin", k))
-            self.in_flight += 1
-            self.max_in_flight = max(self.max_in_flight, self.in_flight)
+            self.in_flight.add(k)
+            self.max_in_flight = max(self.max_in_flight, len(self.in_flight))
             return (k, metadata)
 
         def forward_end(self, pending):
             k, metadata = pending
-            self.in_flight -= 1
+            if k not in self.in_flight:
+                self.stray.append(k)  # collected twice, or never begun
+            self.in_flight.discard(k)
             self.log.append(("end", k))
             if self.fail_at == ("end", k):
                 raise ValueError("end %d" % k)
@@ -346,7 +349,7 @@ def test_evaluate_keeps_one_batch_in_flight_and_collects_in_order(tmp_path):
     m = Model()
     out = str(tmp_path / "pred.json")
     assert evaluate(m, loader(5), predictions_output_file=out) == {"n_end": 5}
-    assert [e for e in m.log if e[0] == "end"] == [("end", k) for k in range(5)] and m.max_in_flight == 2 and m.in_flight == 0
+    assert [e for e in m.log if e[0] == "end"] == [("end", k) for k in range(5)] and m.max_in_flight == 2 and not m.in_flight and not m.stray
     assert m.log.index(("begin", 1)) < m.log.index(("end", 0)) and m.log.index(("begin", 4)) < m.log.index(("end", 3))
     lines = [json.loads(l) for l in open(out)]
     assert [r[0]["Issue_Url"] for r in lines] == ["u%d_0" % k for k in range(5)] and lines[3][1]["predict"]["CWE-2"] == float(np.float32(0.28))
@@ -354,4 +357,5 @@ def test_evaluate_keeps_one_batch_in_flight_and_collects_in_order(tmp_path):
         m = Model(fail_at)
         with pytest.raises(ValueError):
             evaluate(m, loader(5), predictions_output_file=out)
-        assert m.in_flight == 0  # whatever was begun has been collected
+        ends = [e[1] for e in m.log if e[0] == "end"]
+        assert not m.in_flight and not m.stray and len(ends) == len(set(ends)), (fail_at, m.log)  # whatever was begun has been collected, once
