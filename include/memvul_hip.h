@@ -143,15 +143,17 @@ int mv_forward(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int
                float* logits, float* probs, float* best, int32_t* best_idx, float* embed);
 /* mv_forward on a pad-to-longest batch of rows in ANY order (binding.Engine.forward_by_length: the reference's batch of UNSORTED issue reports,
  * predict_memory.py:97-101, scored without its padding): the rows are ordered by the padded length of their own token count (64 .. 256 in steps of 64, 384,
- * 512), groups of fewer than min_tokens padded tokens are merged into the next longer one, every group is one pass at its own length, the passes run back to back,
- * one synchronisation, results in the caller's row order.  ids [B][S], outputs as mv_forward's (best / best_idx required).  B <= max_batch, B * S <= max_tokens
- * and every group within one pass, else MV_ERR_CAPACITY before any GPU work. */
+ * 512), groups of fewer than min_tokens padded tokens are merged into the next longer one, every group runs at its own length (in passes of as many rows as
+ * one pass holds, like mv_forward's), the passes run back to back, one synchronisation, results in the caller's row order.  ids [B][S], outputs as
+ * mv_forward's (best / best_idx required).  Takes every batch mv_forward takes: each pass's ids are uploaded at its own width, in one copy when they fit
+ * max_tokens, and each output comes back in one copy when B <= max_batch. */
 int mv_forward_ragged(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int min_tokens, float* logits, float* probs, float* best,
                       int32_t* best_idx, float* embed);
-/* mv_forward_ragged in two halves: `begin` enqueues the batch (upload, passes, download into pinned staging) on the stream of the next workspace set and returns a
- * ticket without waiting; `end` waits for it and fills the caller's arrays (those of the outputs `begin` was asked for; best / best_idx always).  One batch per
- * workspace set (MEMVUL_STREAMS, 2 by default) may be in flight: with no free workspace set `begin` returns MV_ERR_CAPACITY before any work, like for a batch too
- * large for one upload, and the caller scores the batch synchronously (mv_forward_ragged: stream-ordered behind the batch in flight on workspace set 0).  Collect
+/* mv_forward_ragged in two halves: `begin` enqueues the batch (upload, passes, download into pinned staging) on the stream of a workspace set without a ticket
+ * and returns a ticket without waiting; `end` waits for it and fills the caller's arrays (those of the outputs `begin` was asked for; best / best_idx always).  One
+ * batch per workspace set (MEMVUL_STREAMS, 2 by default) may be in flight: with no free workspace set, or B > max_batch, `begin` returns MV_ERR_CAPACITY before any
+ * work, and the caller scores the batch synchronously (mv_forward_ragged: stream-ordered behind the batch in flight on workspace set 0).  mv_anchor_append waits
+ * for a ticket in flight on another workspace set before it rewrites the bank (mv_anchor_set waits for everything): a ticket scores against the bank it began with.  Collect
  * tickets in the order they were issued; `end` consumes its ticket even when it fails.  predict_memory.evaluate hands over batch k + 1 before it collects batch k,
  * so the GPU does not wait for the host between batches (the reference's loop is serial: predict_memory.py:103-110).  The batches use the workspace sets of the
  * resident sweep (mv_corpus_run): collect every ticket before starting one, and the other way round; like the rest of a handle's entry points these two are not

@@ -305,10 +305,11 @@ class Engine:
 
     def forward_by_length(self, ids: np.ndarray, lens: np.ndarray, want_logits=True, want_probs=True, want_embed=False, min_tokens: Optional[int] = None):
         """``forward`` on a pad-to-longest batch of UNSORTED issue reports (the reference's collation, predict_memory.py:97-101) without paying for the
-        padding: the rows are grouped by the padded length of their OWN token count (64 .. 256 in steps of 64, 384, 512: engine.hip padded_len), every
-        group is one ``mv_forward`` at its own length, and the results go back to the rows' places.  A group of fewer than ``min_tokens`` tokens travels
-        with the next longer one (a pass that small leaves most of the chip idle).  Same per-row arithmetic as ``forward`` at a different padded length
-        (what Engine.bucketed_sweep does to a resident corpus); a batch whose rows share one padded length is ONE call, bit for bit ``forward``."""
+        padding, in ONE library call (mv_forward_ragged: one release of the interpreter lock per batch): the rows are grouped by the padded length of their
+        OWN token count (64 .. 256 in steps of 64, 384, 512: engine.hip padded_len), every group runs at its own length, and the results go back to the rows'
+        places.  A group of fewer than ``min_tokens`` tokens travels with the next longer one (a pass that small leaves most of the chip idle).  Same per-row
+        arithmetic as ``forward`` at a different padded length (what Engine.bucketed_sweep does to a resident corpus); a batch whose rows share one padded
+        length is bit for bit ``forward`` at that length."""
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         B, S = ids.shape
         if min_tokens is None:
@@ -316,42 +317,15 @@ class Engine:
         if B == 0 or B * S < 2 * min_tokens:
             return self.forward(ids, lens, want_logits, want_probs, want_embed)
         out = _outputs(B, self.n_anchors, self.P, want_logits, want_probs, want_embed)
-        ragged = getattr(self, "_forward_ragged", None)  # (a stand-in engine of the tests has only `forward`)
-        if ragged is not None and ragged(ids, lens, min_tokens, out):
-            return out  # everything below inside the library (mv_forward_ragged): ONE release of the interpreter lock per batch
-        # a batch larger than one upload: the same grouping, one ``forward`` per group
-        pl = np.where(lens <= 256, (np.maximum(lens, 1) + 63) // 64 * 64, (lens + 127) // 128 * 128).astype(np.int64)
-        top = int(pl.max()) if B else 0
-        if int(pl.min()) == top:  # one group: one call, at the group's own length
-            return self.forward(np.ascontiguousarray(ids[:, :top]) if top < S else ids, lens, want_logits, want_probs, want_embed)
-        # ONE gather into length order, the groups are then row slices of it and every pass writes its results straight into its slice of the
-        # length-ordered outputs (`out`; no per-group fancy indexing: that was 8 ms of the scorer thread's 15 ms per 512-report batch), ONE gather back
-        order = np.argsort(pl, kind="stable")
-        spl = pl[order]
-        ids_s, lens_s = ids[order], lens[order]
-        cuts = np.flatnonzero(np.diff(spl)) + 1  # group boundaries in the length order
-        ends, widths, start = [], [], 0
-        for end in list(cuts) + [B]:
-            width = int(spl[end - 1])
-            if end < B and (end - start) * width < min_tokens:
-                continue  # too small a pass: these rows travel with the next longer group
-            ends.append(int(end)); widths.append(min(S, width))
-            start = end
-        start = 0
-        for end, width in zip(ends, widths):
-            sub = self.forward(np.ascontiguousarray(ids_s[start:end, :width]), lens_s[start:end], want_logits, want_probs, want_embed)
-            for k, v in sub.items():
-                if v is not None and out.get(k) is not None:
-                    out[k][start:end] = v
-            start = end
-        inv = np.empty(B, np.int64)
-        inv[order] = np.arange(B)
-        return {k: (v[inv] if v is not None else None) for k, v in out.items()}
+        self._check(self._lib.mv_forward_ragged(self._h, _ptr(ids), _ptr(lens), B, S, int(min_tokens), _ptr(out["logits"]), _ptr(out["probs"]),
+                                                _ptr(out["best"]), _ptr(out["best_idx"]), _ptr(out["embed"])), "mv_forward_ragged")
+        self._check_saturation()
+        return out
 
     def forward_by_length_begin(self, ids: np.ndarray, lens: np.ndarray, want_logits=True, want_probs=True, want_embed=False, min_tokens: Optional[int] = None):
         """``forward_by_length`` handed over without waiting for it (mv_forward_ragged_begin): returns a ticket for ``forward_by_length_end``.  One batch per
         workspace set may be in flight (two by default); collect in the order of the calls.  A batch the asynchronous entry cannot take (too small to be
-        worth grouping, too large for one upload, every workspace set busy: the library's MV_ERR_CAPACITY) is scored at once and its ticket holds the results."""
+        worth grouping, more than max_batch rows, every workspace set busy: the library's MV_ERR_CAPACITY) is scored at once and its ticket holds the results."""
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         B, S = ids.shape
         mt = self.BY_LENGTH_MIN_TOKENS if min_tokens is None else min_tokens
@@ -360,7 +334,7 @@ class Engine:
             rc = self._lib.mv_forward_ragged_begin(self._h, _ptr(ids), _ptr(lens), B, S, int(mt), int(want_logits), int(want_probs), int(want_embed), C.byref(t))
             if rc == 0:
                 self._tickets.append(t.value)
-                return ("pending", t.value, B, bool(want_logits), bool(want_probs), bool(want_embed))
+                return ("pending", t.value, B, self.n_anchors, bool(want_logits), bool(want_probs), bool(want_embed))
             if rc != -5:  # (MV_ERR_CAPACITY: below)
                 self._check(rc, "mv_forward_ragged_begin")
         return ("done", self.forward_by_length(ids, lens, want_logits, want_probs, want_embed, min_tokens))
@@ -369,27 +343,16 @@ class Engine:
         """The results of a ``forward_by_length_begin`` ticket.  Collecting consumes the ticket, also when this call raises."""
         if ticket[0] == "done":
             return ticket[1]
-        _, t, B, want_logits, want_probs, want_embed = ticket
+        _, t, B, G, want_logits, want_probs, want_embed = ticket  # (G: the anchors the batch began with, what the library scatters)
         if not self._tickets or self._tickets[0] != t:
             raise RuntimeError("forward_by_length_end: tickets are collected in the order they were issued")
-        out = _outputs(B, self.n_anchors, self.P, want_logits, want_probs, want_embed)
+        out = _outputs(B, G, self.P, want_logits, want_probs, want_embed)
         self._tickets.pop(0)
         self._check(self._lib.mv_forward_ragged_end(self._h, t, _ptr(out["logits"]), _ptr(out["probs"]), _ptr(out["best"]), _ptr(out["best_idx"]), _ptr(out["embed"])),
                     "mv_forward_ragged_end")
         if not self._tickets:  # (the counters are read after a synchronisation of EVERY stream: with the next batch in flight that would wait for it — holding the lock)
             self._check_saturation()
         return out
-
-    def _forward_ragged(self, ids: np.ndarray, lens: np.ndarray, min_tokens: int, out: Dict[str, Optional[np.ndarray]]) -> bool:
-        """mv_forward_ragged into the caller's arrays; False = the batch does not fit one upload (the caller walks the groups itself)."""
-        B, S = ids.shape
-        rc = self._lib.mv_forward_ragged(self._h, _ptr(ids), _ptr(lens), B, S, int(min_tokens), _ptr(out.get("logits")), _ptr(out.get("probs")),
-                                         _ptr(out["best"]), _ptr(out["best_idx"]), _ptr(out.get("embed")))
-        if rc == -5:  # MV_ERR_CAPACITY (checked before any GPU work)
-            return False
-        self._check(rc, "mv_forward_ragged")
-        self._check_saturation()
-        return True
 
     def encode(self, ids: np.ndarray, lens: np.ndarray) -> np.ndarray:
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)

@@ -116,7 +116,26 @@ struct ProfRec {
 
 }  // namespace
 
-// Activation buffers of ONE in-flight batch and the stream its kernels run on
+// The host side of one batch, rows in plan order (Plan): the ids of every pass at the pass's own width, back to back, the lengths, and the results
+// (NULL: an output not asked for)
+struct Stage {
+  int32_t *ids = nullptr, *lens = nullptr, *idx = nullptr;
+  float *logits = nullptr, *probs = nullptr, *best = nullptr, *embed = nullptr;
+};
+
+// How a batch runs: its row order (plan row i = caller row order[i]; empty = the identity) and its passes, each rows [first, first + rows) of that order
+// at `width` tokens per row, its ids at token `tok` of the staging
+struct Pass {
+  int first, rows, width, min_len;  // min_len: the shortest row of the pass (encode_dev)
+  int64_t tok;
+};
+struct Plan {
+  std::vector<int> order;
+  std::vector<Pass> passes;
+  int64_t tokens = 0;  // ids of every pass
+};
+
+// Activation buffers of ONE in-flight batch and the stream its kernels run on, and what is in flight there
 struct Work {
   hipStream_t stream = nullptr;
   int32_t *d_ids = nullptr, *d_lens = nullptr;  // host-path inputs
@@ -146,13 +165,12 @@ struct Work {
   float* cls_corr = nullptr;  // ... and 2^11 x their A-side correction term A_lo W_hi^T [2 Bp][3072] (GemmArgs::cls_corr)
   half_t* vlo_sp = nullptr;   // 2^11 x the low parts of V of the special rows [B 12][64][2] (GemmArgs::vlo_sp -> AttnArgs::vlo_sp)
   int32_t* tile_both = nullptr;  // cls_aside: per 256-row tile of the pass, non-zero = its sequence is shorter than cls_min_len (GemmArgs::tile_both)
-};
-
-// host staging of one by-length batch (mv_forward_ragged*): its rows gathered in length order, its results before they go back to the caller's row order
-// (NULL: an output not asked for)
-struct RaggedStage {
-  int32_t *ids = nullptr, *lens = nullptr, *idx = nullptr;
-  float *logits = nullptr, *probs = nullptr, *best = nullptr, *embed = nullptr;
+  // in flight on this stream: batches of a resident sweep (check_ready waits for them) and / or a ticket of mv_forward_ragged_begin — its plan, anchor
+  // count and staging `st`: `pin` (PINNED, allocated at the set's first ticket) without the outputs it was not asked for
+  bool sweep = false, ticket = false;
+  Plan plan;
+  int G = 0;
+  Stage pin, st;
 };
 
 struct mv_handle {
@@ -175,14 +193,17 @@ struct mv_handle {
   // workspaces: two sets, each with its own stream.  mv_corpus_run alternates the batches of a sweep between them,
   // so two batches are in flight on the GPU at once: the persistent kernels of one batch fill the CUs the other
   // batch's kernel tails, small kernels and memory phases leave idle (+5 % issue reports/s, scripts/dual_stream_probe.py).
-  // Every other entry point works on set 0 (`w` points at the set in use).
+  // mv_forward_ragged_begin puts its batch on a set without a ticket; every other entry point works on set 0.
   int64_t cap_tokens = 0;  // rows every activation buffer holds (multiple of 128, + slack)
   Work work[2];
-  Work* w = &work[0];
   int n_streams = 2;       // sets in use by the resident sweep (mv_set_streams); env MEMVUL_STREAMS=1: only one is created
   int n_alloc = 2;         // sets created
-  bool dual_pending = false;  // work[1] may still be running a batch
-  int rr = 0;                 // workspace set of the next resident-sweep batch
+  int rr = 0;              // workspace set of the next resident-sweep batch
+  Plan plan;               // the synchronous entry points' plan and by-length staging (they run on set 0, behind whatever ticket is in flight there)
+  struct {
+    std::vector<int32_t> ids, lens, idx;
+    std::vector<float> logits, probs, best, embed;
+  } stage;
   float* anchors = nullptr;
   int n_anchors = 0;
   unsigned long long* attn_conc = nullptr;  // MV_F16X8: [0] max collision mass of the [CLS] row on ordinary keys (float bits), [1] items above 0.25 (AttnArgs::conc)
@@ -191,18 +212,6 @@ struct mv_handle {
   // resident corpus
   int32_t *c_ids = nullptr, *c_lens = nullptr;
   std::vector<int32_t> c_lens_host;  // the lengths as uploaded (encode_dev's min_len of each pass)
-  struct {  // mv_forward_ragged: the storage of its staging
-    std::vector<int32_t> ids, lens, idx;
-    std::vector<float> logits, probs, best, embed;
-  } ragged;
-  struct RaggedSlot {  // mv_forward_ragged_begin / _end: one batch in flight per workspace set, its staging in PINNED host memory (the copies really are asynchronous)
-    bool busy = false;
-    int G = 0;
-    std::vector<int> order;
-    RaggedStage pin;  // allocated once: [cap_tokens], [max_batch], [max_batch], [max_batch][max_anchors][2] x 2, [max_batch][2], [max_batch][P]
-    RaggedStage st;   // the batch in flight's: `pin` without the outputs it was not asked for
-  } rslot[2];
-  int rnext = 0;
   std::vector<void*> pinned;
   int64_t c_n = 0;
   int c_S = 0;
@@ -296,13 +305,13 @@ int on_exception(mv_handle* h) noexcept {
   } while (0)
 
 template <typename T>
-int dev_alloc(mv_handle* h, T** p, int64_t count, bool zero = true) {
+int dev_alloc(mv_handle* h, hipStream_t stream, T** p, int64_t count, bool zero = true) {
   void* d = nullptr;
   const size_t bytes = (size_t)count * sizeof(T);
   hipError_t e = hipMalloc(&d, bytes ? bytes : 16);
   if (e != hipSuccess) return fail(h, MV_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
   if (zero) {
-    e = hipMemsetAsync(d, 0, bytes ? bytes : 16, h->w->stream);
+    e = hipMemsetAsync(d, 0, bytes ? bytes : 16, stream);
     if (e != hipSuccess) return fail(h, MV_ERR_HIP, std::string("hipMemset failed: ") + hipGetErrorString(e));
   }
   h->allocs.push_back(d);
@@ -329,19 +338,20 @@ hipEvent_t get_event(mv_handle* h) {
 
 struct ProfScope {
   mv_handle* h;
+  hipStream_t stream;
   ProfRec rec;
   bool on;
-  ProfScope(mv_handle* h_, int cls) : h(h_), on(h_->prof && ((h_->prof_mask >> cls) & 1u)) {
+  ProfScope(mv_handle* h_, hipStream_t s, int cls) : h(h_), stream(s), on(h_->prof && ((h_->prof_mask >> cls) & 1u)) {
     if (on) {
       rec.cls = cls;
       rec.e0 = get_event(h);
       rec.e1 = get_event(h);
-      hipEventRecord(rec.e0, h->w->stream);
+      hipEventRecord(rec.e0, stream);
     }
   }
   ~ProfScope() {
     if (on) {
-      hipEventRecord(rec.e1, h->w->stream);
+      hipEventRecord(rec.e1, stream);
       h->recs.push_back(rec);
     }
   }
@@ -361,12 +371,12 @@ int choose_gn(int tn, int gn_max) {
 }
 
 template <int EPI>
-int launch_gemm128(mv_handle* h, int cls, GemmArgs a) {
+int launch_gemm128(mv_handle* h, hipStream_t stream, int cls, GemmArgs a) {
   if (a.M % 128 || a.N % 128 || a.K % 64) return fail(h, MV_ERR_INVALID, "gemm128: M,N % 128, K % 64 required");
   a.GN = choose_gn(a.N / 128, 8);
   const int grid = (a.M / 128) * (a.N / 128);
-  ProfScope ps(h, cls);
-  hipLaunchKernelGGL((gemm128_kernel<EPI>), dim3(grid), dim3(256), G128_LDS_BYTES, h->w->stream, a);
+  ProfScope ps(h, stream, cls);
+  hipLaunchKernelGGL((gemm128_kernel<EPI>), dim3(grid), dim3(256), G128_LDS_BYTES, stream, a);
   return launch_check(h, "gemm128");
 }
 
@@ -374,19 +384,19 @@ int launch_gemm128(mv_handle* h, int cls, GemmArgs a) {
 // 4x the workgroups of the 128^2 kernel and a K loop that is DMA-latency-bound per step rather than per tile
 constexpr int RING64_LDS = 4 * (64 + 64) * 64 * 2;
 template <int EPI>
-int launch_ring64(mv_handle* h, int cls, GemmArgs a) {
+int launch_ring64(mv_handle* h, hipStream_t stream, int cls, GemmArgs a) {
   if (a.M % 64 || a.N % 64 || a.K % 64) return fail(h, MV_ERR_INVALID, "gemm_ring: shape not a multiple of the 64 x 64 x 64 tile");
   a.GN = choose_gn(a.N / 64, 8);
   const int grid = (a.M / 64) * (a.N / 64);
-  ProfScope ps(h, cls);
-  hipLaunchKernelGGL((gemm_ring_kernel<EPI, 1, 1, 2, 2, 64, 4, 2>), dim3(grid), dim3(256), RING64_LDS, h->w->stream, a);
+  ProfScope ps(h, stream, cls);
+  hipLaunchKernelGGL((gemm_ring_kernel<EPI, 1, 1, 2, 2, 64, 4, 2>), dim3(grid), dim3(256), RING64_LDS, stream, a);
   return launch_check(h, "gemm_ring");
 }
 
 // The persistent ping-pong GEMM (gemm_pp.h): one workgroup per CU walks the 256^2 output tiles.  a.A8 set = the
 // MV_F16X8 build (a second, fp8 sweep over [A8 | W8]).
 template <int PPEPI>
-int launch_pp(mv_handle* h, int cls, GemmArgs a) {
+int launch_pp(mv_handle* h, hipStream_t stream, int cls, GemmArgs a) {
   constexpr int RAW = PPEPI != PP_RESLN3;
   if (a.M % 256 || a.N % 256 || a.K % 128 || a.K < 256 || a.N > MV_INTER)
     return fail(h, MV_ERR_INVALID, "gemm_pp: M,N % 256, K % 128, K >= 256, N <= 3072 required");  // K >= 256: the RAW kernels stage the
@@ -402,12 +412,12 @@ int launch_pp(mv_handle* h, int cls, GemmArgs a) {
   // the A-stationary raster (gemm_pp.h raster_pp; MEMVUL_RASTER=1): only where its windows tile the sequence exactly
   a.raster_mode = (h->pp_raster == 1 && a.N / 256 > a.GN && ((a.M / 256) * a.GN) % grid == 0) ? 1 : 0;
   const int lds = RAW ? PP_LDS_BYTES_RAW : PP_LDS_BYTES;
-  ProfScope ps(h, cls);
+  ProfScope ps(h, stream, cls);
   if (a.A8) {
     if (!a.W8 || (PPEPI != PP_QK && !a.out8)) return fail(h, MV_ERR_STATE, "internal: MV_F16X8 GEMM without its fp8 planes");
-    hipLaunchKernelGGL((gemm_pp_kernel<PPEPI, RAW, 1>), dim3(grid), dim3(512), lds, h->w->stream, a);
+    hipLaunchKernelGGL((gemm_pp_kernel<PPEPI, RAW, 1>), dim3(grid), dim3(512), lds, stream, a);
   } else {
-    hipLaunchKernelGGL((gemm_pp_kernel<PPEPI, RAW, 0>), dim3(grid), dim3(512), lds, h->w->stream, a);
+    hipLaunchKernelGGL((gemm_pp_kernel<PPEPI, RAW, 0>), dim3(grid), dim3(512), lds, stream, a);
   }
   return launch_check(h, "gemm_pp");
 }
@@ -422,19 +432,19 @@ bool pp_selected(const mv_handle* h, int64_t M) {
 
 // the mid-size / skinny GEMMs of a pass that does not fill the chip (and of the [CLS] tail)
 template <int EPI>
-int launch_small(mv_handle* h, int cls, const GemmArgs& a) {
-  if (h->gemm_tile == 0 && a.M <= 512 && a.M % 64 == 0 && a.N % 64 == 0) return launch_ring64<EPI>(h, cls, a);
-  return launch_gemm128<EPI>(h, cls, a);
+int launch_small(mv_handle* h, hipStream_t stream, int cls, const GemmArgs& a) {
+  if (h->gemm_tile == 0 && a.M <= 512 && a.M % 64 == 0 && a.N % 64 == 0) return launch_ring64<EPI>(h, stream, cls, a);
+  return launch_gemm128<EPI>(h, stream, cls, a);
 }
 
 // K7 + K8: pooler on the [CLS] rows (row_stride floats apart), then the header
-int pool_head(mv_handle* h, const float* x, size_t row_stride, int B, float* u_out) {
+int pool_head(mv_handle* h, Work& wk, const float* x, size_t row_stride, int B, float* u_out) {
   const unsigned gx = (unsigned)((B + 31) / 32);
-  hipLaunchKernelGGL(dense768_kernel<0>, dim3(gx, MV_HIDDEN / 32), dim3(512), 0, h->w->stream, x, row_stride, B, h->WpT, h->bp,
-                     MV_HIDDEN, h->P == MV_HIDDEN ? u_out : h->w->pooled);
+  hipLaunchKernelGGL(dense768_kernel<0>, dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, x, row_stride, B, h->WpT, h->bp,
+                     MV_HIDDEN, h->P == MV_HIDDEN ? u_out : wk.pooled);
   if (int rc = launch_check(h, "pooler")) return rc;
   if (h->P == MV_HIDDEN) return MV_OK;  // use_header = False: the pooler output is the embedding
-  hipLaunchKernelGGL(dense768_kernel<1>, dim3(gx, MV_PROJ / 32), dim3(512), 0, h->w->stream, h->w->pooled, (size_t)MV_HIDDEN, B, h->WhT,
+  hipLaunchKernelGGL(dense768_kernel<1>, dim3(gx, MV_PROJ / 32), dim3(512), 0, wk.stream, wk.pooled, (size_t)MV_HIDDEN, B, h->WhT,
                      h->bh, MV_PROJ, u_out);
   return launch_check(h, "header");
 }
@@ -442,28 +452,28 @@ int pool_head(mv_handle* h, const float* x, size_t row_stride, int B, float* u_o
 // padded sequence length of a pass: attention_v2 runs 64-key blocks up to 256 and 128-key chunks above
 inline int padded_len(int S_in) { return (int)round_up(S_in, S_in <= 256 ? 64 : 128); }
 
-int launch_attention(mv_handle* h, const int32_t* d_lens, int B, int Sp, bool x8, bool sp_out = false) {
+int launch_attention(mv_handle* h, Work& wk, const int32_t* d_lens, int B, int Sp, bool x8, bool sp_out = false) {
   const bool vlo = x8 && h->short_vlo && Sp <= 128;  // the QKV projection of this pass wrote V^T's lo plane (encode_dev: the same predicate)
-  AttnArgs a{h->w->q, h->w->k, h->w->vt, d_lens, h->w->ctx, Sp, B, x8 ? h->w->ctx8 : nullptr, h->x8_sat, vlo ? h->w->vt_lo : nullptr,
-             vlo ? h->w->q_lo : nullptr, vlo ? h->w->k_lo : nullptr,
-             (x8 && !vlo) ? h->w->vlo_sp : nullptr,     // special rows: V of keys 0, 1 as hi + lo (the two-plane short passes carry every key's lo plane)
+  AttnArgs a{wk.q, wk.k, wk.vt, d_lens, wk.ctx, Sp, B, x8 ? wk.ctx8 : nullptr, h->x8_sat, vlo ? wk.vt_lo : nullptr,
+             vlo ? wk.q_lo : nullptr, vlo ? wk.k_lo : nullptr,
+             (x8 && !vlo) ? wk.vlo_sp : nullptr,     // special rows: V of keys 0, 1 as hi + lo (the two-plane short passes carry every key's lo plane)
              x8 ? h->attn_conc : nullptr,               // concentration monitor (mv_attention_concentration)
              sp_out ? h->cls_min_len : 0,               // [CLS]-row form: no lo8 plane of the context for the sequences that take it
-             sp_out ? h->w->cls_lo : nullptr};
-  ProfScope ps(h, KC_ATTENTION);
+             sp_out ? wk.cls_lo : nullptr};
+  ProfScope ps(h, wk.stream, KC_ATTENTION);
   if (vlo) {
     const int nkb = Sp / 64, items = B * MV_HEADS;
     const int slots = h->num_cu * (nkb == 1 ? 2 : 1);  // resident workgroups by LDS: 64 / 128 KiB each
     const int grid = items < slots ? items : slots;
-    if (nkb == 1) hipLaunchKernelGGL((attention_v2_kernel<1, 1, 1, 1>), dim3(grid), dim3(128), ATT2_LDS_BYTES_VLO(1), h->w->stream, a, items);
-    else hipLaunchKernelGGL((attention_v2_kernel<2, 1, 1, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES_VLO(2), h->w->stream, a, items);
+    if (nkb == 1) hipLaunchKernelGGL((attention_v2_kernel<1, 1, 1, 1>), dim3(grid), dim3(128), ATT2_LDS_BYTES_VLO(1), wk.stream, a, items);
+    else hipLaunchKernelGGL((attention_v2_kernel<2, 1, 1, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES_VLO(2), wk.stream, a, items);
   } else if (Sp <= 256) {
     const int nkb = Sp / 64, items = B * MV_HEADS;
     const int slots = h->num_cu * (nkb == 1 ? 4 : nkb == 2 ? 2 : 1);  // resident workgroups: 8 waves and <= 128 KiB LDS per CU
     const int grid = items < slots ? items : slots;
 #define MV_ATT(NKB)                                                                                                              \
-    if (x8) hipLaunchKernelGGL((attention_v2_kernel<NKB, 1, 1>), dim3(grid), dim3(NKB * 128), ATT2_LDS_BYTES(NKB), h->w->stream, a, items); \
-    else hipLaunchKernelGGL((attention_v2_kernel<NKB, 1, 0>), dim3(grid), dim3(NKB * 128), ATT2_LDS_BYTES(NKB), h->w->stream, a, items)
+    if (x8) hipLaunchKernelGGL((attention_v2_kernel<NKB, 1, 1>), dim3(grid), dim3(NKB * 128), ATT2_LDS_BYTES(NKB), wk.stream, a, items); \
+    else hipLaunchKernelGGL((attention_v2_kernel<NKB, 1, 0>), dim3(grid), dim3(NKB * 128), ATT2_LDS_BYTES(NKB), wk.stream, a, items)
     switch (nkb) {
       case 1: MV_ATT(1); break;
       case 2: MV_ATT(2); break;
@@ -476,21 +486,14 @@ int launch_attention(mv_handle* h, const int32_t* d_lens, int B, int Sp, bool x8
     // workgroups of 4 waves per CU; consecutive units of a workgroup are the query blocks of one head (K / V^T from L2)
     const int nch = Sp / 128, units = B * MV_HEADS * nch;
     const int grid = units < 2 * h->num_cu ? units : 2 * h->num_cu;
-    if (nch == 3 && x8) hipLaunchKernelGGL((attention_v2_kernel<2, 3, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), h->w->stream, a, units);
-    else if (nch == 3) hipLaunchKernelGGL((attention_v2_kernel<2, 3, 0>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), h->w->stream, a, units);
-    else if (x8) hipLaunchKernelGGL((attention_v2_kernel<2, 4, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), h->w->stream, a, units);
-    else hipLaunchKernelGGL((attention_v2_kernel<2, 4, 0>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), h->w->stream, a, units);
+    if (nch == 3 && x8) hipLaunchKernelGGL((attention_v2_kernel<2, 3, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), wk.stream, a, units);
+    else if (nch == 3) hipLaunchKernelGGL((attention_v2_kernel<2, 3, 0>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), wk.stream, a, units);
+    else if (x8) hipLaunchKernelGGL((attention_v2_kernel<2, 4, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), wk.stream, a, units);
+    else hipLaunchKernelGGL((attention_v2_kernel<2, 4, 0>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), wk.stream, a, units);
   } else {
     return fail(h, MV_ERR_INVALID, "internal: attention at a padded length other than 64 .. 256 / 384 / 512");
   }
   return launch_check(h, "attention");
-}
-
-// the shortest sequence of a pass, from the host copy of its lengths
-inline int pass_min_len(const int32_t* lens, int n) {
-  int m = INT32_MAX;
-  for (int i = 0; i < n; ++i) m = lens[i] < m ? lens[i] : m;
-  return n > 0 ? m : 0;
 }
 
 // ---- encoder: ids (device) -> u (device, [B][512]); stops after n_layers (<0: all) ------------
@@ -500,8 +503,8 @@ inline int pass_min_len(const int32_t* lens, int n) {
 //   * small passes: one-tile-per-workgroup GEMMs (gemm.h) on an fp32 stream with explicit LayerNorm kernels.
 // The last layer is pruned to the [CLS] rows when the pooler follows (cls_prune); `full` (debug taps) disables that and
 // leaves the normalised fp32 stream of the last layer run in xres.
-int encode_dev(mv_handle* h, const int32_t* d_ids, const int32_t* d_lens, int min_len, int B, int S_in, int n_layers, float* u_out,
-               bool full = false, int pitch = 0) {  // min_len: the shortest sequence of the pass as the HOST knows it (pass_min_len; 0 = unknown)
+int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_lens, int min_len, int B, int S_in, int n_layers, float* u_out,
+               bool full = false, int pitch = 0) {  // min_len: the shortest sequence of the pass as the HOST knows it (Pass::min_len; 0 = unknown)
   if (pitch <= 0) pitch = S_in;  // ints between the rows of d_ids
   const mv_config& c = h->cfg;
   const int Sp = padded_len(S_in);
@@ -527,8 +530,8 @@ int encode_dev(mv_handle* h, const int32_t* d_ids, const int32_t* d_lens, int mi
   const bool cls_as = big && x8 && h->cls_aside && (one_seq_tiles || whole_pass);
   if (cls_as && one_seq_tiles) {
     const int ntile = (int)(Mpad / 256);
-    hipLaunchKernelGGL(cls_tile_flags_kernel, dim3((unsigned)((ntile + 255) / 256)), dim3(256), 0, h->w->stream, d_lens, B, Sp, h->cls_min_len, ntile,
-                       h->w->tile_both);
+    hipLaunchKernelGGL(cls_tile_flags_kernel, dim3((unsigned)((ntile + 255) / 256)), dim3(256), 0, wk.stream, d_lens, B, Sp, h->cls_min_len, ntile,
+                       wk.tile_both);
     if (int rc = launch_check(h, "cls_tile_flags")) return rc;
   }
   // Special rows (round 6): rows 0 and 1 of every sequence hold its [CLS] and its [SEP] token (embed_ln_kernel swaps the last token into row 1) — the token the
@@ -538,199 +541,199 @@ int encode_dev(mv_handle* h, const int32_t* d_ids, const int32_t* d_lens, int mi
   // never sweep the A-side term for all rows by default), the other three GEMMs where the [CLS]-row form is in force.
   const bool special = big && x8;
   auto row_term = [&](const half_t* A, const half_t* W, int N, int K) -> int {  // cls_corr [2 B][N] = A [2 B][K] W^T (both 2^11 x); A = st_lo (stream) or cls_lo (context, GELU output)
-    ProfScope ps(h, KC_CLS_ROW_TERM);
+    ProfScope ps(h, wk.stream, KC_CLS_ROW_TERM);
     GemmArgs t{};
-    t.M = (int)round_up(2 * B, 64); t.Mreal = 2 * B; t.S = 64; t.A = A; t.W = W; t.N = N; t.K = K; t.outf = h->w->cls_corr;
+    t.M = (int)round_up(2 * B, 64); t.Mreal = 2 * B; t.S = 64; t.A = A; t.W = W; t.N = N; t.K = K; t.outf = wk.cls_corr;
     t.GN = choose_gn(N / 64, 8);
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI_F32, 1, 1, 2, 2, 64, 4, 2>), dim3((unsigned)((t.M / 64) * (N / 64))), dim3(256), RING64_LDS, h->w->stream, t);
+    hipLaunchKernelGGL((gemm_ring_kernel<EPI_F32, 1, 1, 2, 2, 64, 4, 2>), dim3((unsigned)((t.M / 64) * (N / 64))), dim3(256), RING64_LDS, wk.stream, t);
     return launch_check(h, "row term gemm_ring");
   };
   const unsigned ln_grid = (unsigned)((M + 3) / 4);
   {
-    ProfScope ps(h, KC_EMBED_LN);
+    ProfScope ps(h, wk.stream, KC_EMBED_LN);
     if (big)
-      hipLaunchKernelGGL(embed_ln_kernel<true>, dim3(ln_grid), dim3(256), 0, h->w->stream, d_ids, pitch, S_in, Sp, (int)M, c.vocab_size,
-                         h->wemb, h->pemb, h->temb, h->embg, h->embb, c.ln_eps, h->w->xres, h->w->x16, h->w->lnstats,
-                         x8 ? (half_t*)nullptr : h->w->xlo, x8 ? h->w->x8 : (uint8_t*)nullptr, h->x8_sat, special ? d_lens : (const int32_t*)nullptr,
-                         special ? h->w->st_lo : (half_t*)nullptr);
+      hipLaunchKernelGGL(embed_ln_kernel<true>, dim3(ln_grid), dim3(256), 0, wk.stream, d_ids, pitch, S_in, Sp, (int)M, c.vocab_size,
+                         h->wemb, h->pemb, h->temb, h->embg, h->embb, c.ln_eps, wk.xres, wk.x16, wk.lnstats,
+                         x8 ? (half_t*)nullptr : wk.xlo, x8 ? wk.x8 : (uint8_t*)nullptr, h->x8_sat, special ? d_lens : (const int32_t*)nullptr,
+                         special ? wk.st_lo : (half_t*)nullptr);
     else
-      hipLaunchKernelGGL(embed_ln_kernel<false>, dim3(ln_grid), dim3(256), 0, h->w->stream, d_ids, pitch, S_in, Sp, (int)M, c.vocab_size,
-                         h->wemb, h->pemb, h->temb, h->embg, h->embb, c.ln_eps, h->w->xres, h->w->x16, (float*)nullptr,
+      hipLaunchKernelGGL(embed_ln_kernel<false>, dim3(ln_grid), dim3(256), 0, wk.stream, d_ids, pitch, S_in, Sp, (int)M, c.vocab_size,
+                         h->wemb, h->pemb, h->temb, h->embg, h->embb, c.ln_eps, wk.xres, wk.x16, (float*)nullptr,
                          (half_t*)nullptr, (uint8_t*)nullptr, (unsigned long long*)nullptr);
     if (int rc = launch_check(h, "embed_ln")) return rc;
   }
   // big: the LayerNorm whose statistics are pending in the vstats buffers — gamma / beta the next residual GEMM applies
   const float *pend_g = h->embg, *pend_b = h->embb;
   auto run_ln = [&](float* x32, half_t* x16, int rows, const float* g, const float* b) -> int {
-    ProfScope ps(h, KC_LN);
-    hipLaunchKernelGGL(ln_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, h->w->stream, x32, x16, rows, g, b, c.ln_eps,
+    ProfScope ps(h, wk.stream, KC_LN);
+    hipLaunchKernelGGL(ln_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, wk.stream, x32, x16, rows, g, b, c.ln_eps,
                        (float*)nullptr);
     return launch_check(h, "layernorm");
   };
   auto final_ln = [&](const float* g, const float* b) -> int {  // two-plane raw stream -> normalised fp32 rows (pooler / debug taps)
     const size_t n4 = (size_t)M * MV_HIDDEN / 4;
-    hipLaunchKernelGGL(hilo_to_f32_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, h->w->stream, h->w->x16, h->w->xlo, n4, h->w->xres,
-                       special ? (const half_t*)h->w->st_lo : (const half_t*)nullptr, Sp, (const uint8_t*)h->w->x8);
+    hipLaunchKernelGGL(hilo_to_f32_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, wk.stream, wk.x16, wk.xlo, n4, wk.xres,
+                       special ? (const half_t*)wk.st_lo : (const half_t*)nullptr, Sp, (const uint8_t*)wk.x8);
     if (int rc = launch_check(h, "hilo_to_f32")) return rc;
-    return run_ln(h->w->xres, h->w->x16, (int)M, g, b);
+    return run_ln(wk.xres, wk.x16, (int)M, g, b);
   };
   if (big && n_layers == 0) { if (int rc = final_ln(h->embg, h->embb)) return rc; }
   // big: st_in = vstats of the layer's input rows (embedding / previous FFN-2), st_mid = of the rows after the
   // attention-output projection; no statistics kernel in between (gemm_pp.h)
-  float *st_in = h->w->lnstats, *st_mid = h->w->lnpart;
+  float *st_in = wk.lnstats, *st_mid = wk.lnpart;
   for (int l = 0; l < n_layers; ++l) {
     const LayerW& w = h->L[l];
     const bool last = (l == n_layers - 1);
     GemmArgs g{};
     g.M = (int)Mpad; g.Mreal = (int)M; g.S = Sp; g.ln_eps = c.ln_eps; g.x8_sat = h->x8_sat;
-    g.tile_both = (cls_as && one_seq_tiles) ? h->w->tile_both : nullptr;  // (whole_pass: no tile is short)
-    g.q = h->w->q; g.k = h->w->k; g.vt = h->w->vt;
+    g.tile_both = (cls_as && one_seq_tiles) ? wk.tile_both : nullptr;  // (whole_pass: no tile is short)
+    g.q = wk.q; g.k = wk.k; g.vt = wk.vt;
     const half_t* wqkv = big ? w.wqkv_f : w.wqkv;
     const float* bqkv = big ? w.bqkv_f : w.bqkv;
     if (last && prune) {
       // ---- last layer, [CLS] rows only: K and V of every token, everything else on B rows
       const int Bp = (int)round_up(B, 128);
-      g.A = h->w->x16; g.W = wqkv + (size_t)MV_HIDDEN * MV_HIDDEN; g.bias = bqkv + MV_HIDDEN; g.N = 2 * MV_HIDDEN; g.K = MV_HIDDEN;
+      g.A = wk.x16; g.W = wqkv + (size_t)MV_HIDDEN * MV_HIDDEN; g.bias = bqkv + MV_HIDDEN; g.N = 2 * MV_HIDDEN; g.K = MV_HIDDEN;
       g.col0 = MV_HIDDEN;
       if (big) {
         g.lnstats = st_in;
-        if (x8) { g.A8 = h->w->x8; g.W8 = w.wqkv_f8 + (size_t)MV_HIDDEN * 2 * MV_HIDDEN; g.x8_scale = w.sc_qkv; g.x8_terms = 3; g.x8_aside_mask = h->qkv_aside_mask; }
+        if (x8) { g.A8 = wk.x8; g.W8 = w.wqkv_f8 + (size_t)MV_HIDDEN * 2 * MV_HIDDEN; g.x8_scale = w.sc_qkv; g.x8_terms = 3; g.x8_aside_mask = h->qkv_aside_mask; }
         if (special) {  // K and V of the special rows: row term wherever a block sweeps the weight-side term only; V also as hi + lo (the [CLS] query itself is fp32: the tail below)
           if ((h->qkv_aside_mask & 6) != 6) {
-            if (int rc = row_term(h->w->st_lo, g.W, g.N, g.K)) return rc;
-            g.cls_corr = h->w->cls_corr;
+            if (int rc = row_term(wk.st_lo, g.W, g.N, g.K)) return rc;
+            g.cls_corr = wk.cls_corr;
           }
-          g.vlo_sp = (h->short_vlo && Sp <= 128) ? nullptr : h->w->vlo_sp;
+          g.vlo_sp = (h->short_vlo && Sp <= 128) ? nullptr : wk.vlo_sp;
         }
-        if (int rc = launch_pp<PP_QK>(h, KC_GEMM_KV_LAST, g)) return rc;
-      } else if (int rc = launch_small<EPI_QKV>(h, KC_GEMM_KV_LAST, g)) return rc;
-      ProfScope tail(h, KC_CLS_TAIL);
+        if (int rc = launch_pp<PP_QK>(h, wk.stream, KC_GEMM_KV_LAST, g)) return rc;
+      } else if (int rc = launch_small<EPI_QKV>(h, wk.stream, KC_GEMM_KV_LAST, g)) return rc;
+      ProfScope tail(h, wk.stream, KC_CLS_TAIL);
       const uint32_t keep_mask = h->prof_mask;
       h->prof_mask = 0;  // the tail is one profiled span; its inner launches carry no events of their own
       auto tail_rc = [&]() -> int {
-        hipLaunchKernelGGL(cls_gather_kernel, dim3((B + 3) / 4), dim3(256), 0, h->w->stream, h->w->xres, h->w->x16, Sp, B,
-                           big ? st_in : (const float*)nullptr, pend_g, pend_b, h->w->c32, h->w->c16, big ? 1 : 0,
-                           (big && !x8) ? h->w->xlo : (const half_t*)nullptr, big ? 1 : 0, c.ln_eps, special ? (const half_t*)h->w->st_lo : (const half_t*)nullptr);
+        hipLaunchKernelGGL(cls_gather_kernel, dim3((B + 3) / 4), dim3(256), 0, wk.stream, wk.xres, wk.x16, Sp, B,
+                           big ? st_in : (const float*)nullptr, pend_g, pend_b, wk.c32, wk.c16, big ? 1 : 0,
+                           (big && !x8) ? wk.xlo : (const half_t*)nullptr, big ? 1 : 0, c.ln_eps, special ? (const half_t*)wk.st_lo : (const half_t*)nullptr);
         if (int rc = launch_check(h, "cls_gather")) return rc;
         if (x8) {
           // MV_F16X8: the B [CLS] rows in full fp32 on the fp32-input matrix cores (their operand rounding would reach the
           // pooler un-attenuated): Q projection, single-query attention (fp16 K / V^T of the main path, fp32 context), output
           // projection + residual, LayerNorm, FFN, LayerNorm — the fp16 skinny GEMMs below are MV_F16's tail
           const unsigned gx = (unsigned)((B + 31) / 32);
-          hipLaunchKernelGGL((dense768_kernel<2, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, h->w->stream, (const float*)h->w->c32,
-                             (size_t)MV_HIDDEN, B, (const float*)w.wqT32, (const float*)w.bqkv, MV_HIDDEN, h->w->cq, (const float*)nullptr);
+          hipLaunchKernelGGL((dense768_kernel<2, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.c32,
+                             (size_t)MV_HIDDEN, B, (const float*)w.wqT32, (const float*)w.bqkv, MV_HIDDEN, wk.cq, (const float*)nullptr);
           if (int rc = launch_check(h, "cls q")) return rc;
-          hipLaunchKernelGGL(attention_cls_kernel, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, h->w->stream, h->w->cq, h->w->k, h->w->vt,
-                             d_lens, h->w->cctx, Sp, B * MV_HEADS, h->w->pooled, (const half_t*)g.vlo_sp);
+          hipLaunchKernelGGL(attention_cls_kernel, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt,
+                             d_lens, wk.cctx, Sp, B * MV_HEADS, wk.pooled, (const half_t*)g.vlo_sp);
           if (int rc = launch_check(h, "attention_cls")) return rc;
-          hipLaunchKernelGGL((dense768_kernel<4, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, h->w->stream, (const float*)h->w->pooled,
-                             (size_t)MV_HIDDEN, B, (const float*)w.woT32, (const float*)w.bo, MV_HIDDEN, h->w->c32, (const float*)h->w->c32);
+          hipLaunchKernelGGL((dense768_kernel<4, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.pooled,
+                             (size_t)MV_HIDDEN, B, (const float*)w.woT32, (const float*)w.bo, MV_HIDDEN, wk.c32, (const float*)wk.c32);
           if (int rc = launch_check(h, "cls out")) return rc;
-          if (int rc = run_ln(h->w->c32, h->w->c16, B, w.ln1g, w.ln1b)) return rc;
-          hipLaunchKernelGGL((dense768_kernel<3, MV_HIDDEN>), dim3(gx, MV_INTER / 32), dim3(512), 0, h->w->stream, (const float*)h->w->c32,
-                             (size_t)MV_HIDDEN, B, (const float*)w.w1T32, (const float*)w.b1, MV_INTER, h->w->ch32, (const float*)nullptr);
+          if (int rc = run_ln(wk.c32, wk.c16, B, w.ln1g, w.ln1b)) return rc;
+          hipLaunchKernelGGL((dense768_kernel<3, MV_HIDDEN>), dim3(gx, MV_INTER / 32), dim3(512), 0, wk.stream, (const float*)wk.c32,
+                             (size_t)MV_HIDDEN, B, (const float*)w.w1T32, (const float*)w.b1, MV_INTER, wk.ch32, (const float*)nullptr);
           if (int rc = launch_check(h, "cls ffn1")) return rc;
-          hipLaunchKernelGGL((dense768_kernel<4, MV_INTER>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, h->w->stream, (const float*)h->w->ch32,
-                             (size_t)MV_INTER, B, (const float*)w.w2T32, (const float*)w.b2, MV_HIDDEN, h->w->c32, (const float*)h->w->c32);
+          hipLaunchKernelGGL((dense768_kernel<4, MV_INTER>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.ch32,
+                             (size_t)MV_INTER, B, (const float*)w.w2T32, (const float*)w.b2, MV_HIDDEN, wk.c32, (const float*)wk.c32);
           if (int rc = launch_check(h, "cls ffn2")) return rc;
-          if (int rc = run_ln(h->w->c32, h->w->c16, B, w.ln2g, w.ln2b)) return rc;
-          return pool_head(h, h->w->c32, MV_HIDDEN, B, u_out);
+          if (int rc = run_ln(wk.c32, wk.c16, B, w.ln2g, w.ln2b)) return rc;
+          return pool_head(h, wk, wk.c32, MV_HIDDEN, B, u_out);
         }
         GemmArgs t{};
         t.M = Bp; t.Mreal = B; t.S = 64;
-        t.A = h->w->c16; t.W = w.wqkv; t.bias = w.bqkv; t.N = MV_HIDDEN; t.K = MV_HIDDEN; t.outf = h->w->cq;
-        if (int rc = launch_small<EPI_F32>(h, KC_CLS_TAIL, t)) return rc;
-        hipLaunchKernelGGL(attention_cls_kernel, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, h->w->stream, h->w->cq, h->w->k, h->w->vt,
-                           d_lens, h->w->cctx, Sp, B * MV_HEADS);
+        t.A = wk.c16; t.W = w.wqkv; t.bias = w.bqkv; t.N = MV_HIDDEN; t.K = MV_HIDDEN; t.outf = wk.cq;
+        if (int rc = launch_small<EPI_F32>(h, wk.stream, KC_CLS_TAIL, t)) return rc;
+        hipLaunchKernelGGL(attention_cls_kernel, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt,
+                           d_lens, wk.cctx, Sp, B * MV_HEADS);
         if (int rc = launch_check(h, "attention_cls")) return rc;
-        t.A = h->w->cctx; t.W = w.wo; t.bias = w.bo; t.N = MV_HIDDEN; t.K = MV_HIDDEN; t.xres = h->w->c32; t.outf = nullptr;
-        if (int rc = launch_small<EPI_RES>(h, KC_CLS_TAIL, t)) return rc;
-        if (int rc = run_ln(h->w->c32, h->w->c16, B, w.ln1g, w.ln1b)) return rc;
-        t.A = h->w->c16; t.W = w.w1; t.bias = w.b1; t.N = MV_INTER; t.K = MV_HIDDEN; t.out16 = h->w->ch16;
-        if (int rc = launch_small<EPI_GELU>(h, KC_CLS_TAIL, t)) return rc;
-        t.A = h->w->ch16; t.W = w.w2; t.bias = w.b2; t.N = MV_HIDDEN; t.K = MV_INTER; t.xres = h->w->c32;
-        if (int rc = launch_small<EPI_RES>(h, KC_CLS_TAIL, t)) return rc;
-        if (int rc = run_ln(h->w->c32, h->w->c16, B, w.ln2g, w.ln2b)) return rc;
-        return pool_head(h, h->w->c32, MV_HIDDEN, B, u_out);
+        t.A = wk.cctx; t.W = w.wo; t.bias = w.bo; t.N = MV_HIDDEN; t.K = MV_HIDDEN; t.xres = wk.c32; t.outf = nullptr;
+        if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_CLS_TAIL, t)) return rc;
+        if (int rc = run_ln(wk.c32, wk.c16, B, w.ln1g, w.ln1b)) return rc;
+        t.A = wk.c16; t.W = w.w1; t.bias = w.b1; t.N = MV_INTER; t.K = MV_HIDDEN; t.out16 = wk.ch16;
+        if (int rc = launch_small<EPI_GELU>(h, wk.stream, KC_CLS_TAIL, t)) return rc;
+        t.A = wk.ch16; t.W = w.w2; t.bias = w.b2; t.N = MV_HIDDEN; t.K = MV_INTER; t.xres = wk.c32;
+        if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_CLS_TAIL, t)) return rc;
+        if (int rc = run_ln(wk.c32, wk.c16, B, w.ln2g, w.ln2b)) return rc;
+        return pool_head(h, wk, wk.c32, MV_HIDDEN, B, u_out);
       }();
       h->prof_mask = keep_mask;
       return tail_rc;
     }
     if (big) {
       // K2: Q, K, V^T projection of the raw stream (LayerNorm folded into W'' / b')
-      g.A = h->w->x16; g.W = wqkv; g.bias = bqkv; g.N = 3 * MV_HIDDEN; g.K = MV_HIDDEN; g.lnstats = st_in;
-      if (x8) { g.A8 = h->w->x8; g.W8 = w.wqkv_f8; g.x8_scale = w.sc_qkv; g.x8_terms = 3; g.x8_aside_mask = h->qkv_aside_mask; }
-      g.vt_lo = (x8 && h->short_vlo && Sp <= 128) ? h->w->vt_lo : nullptr;  // short passes: Q, K, V^T as hi + lo planes (launch_attention: the same predicate)
-      g.q_lo = h->w->q_lo; g.k_lo = h->w->k_lo;
+      g.A = wk.x16; g.W = wqkv; g.bias = bqkv; g.N = 3 * MV_HIDDEN; g.K = MV_HIDDEN; g.lnstats = st_in;
+      if (x8) { g.A8 = wk.x8; g.W8 = w.wqkv_f8; g.x8_scale = w.sc_qkv; g.x8_terms = 3; g.x8_aside_mask = h->qkv_aside_mask; }
+      g.vt_lo = (x8 && h->short_vlo && Sp <= 128) ? wk.vt_lo : nullptr;  // short passes: Q, K, V^T as hi + lo planes (launch_attention: the same predicate)
+      g.q_lo = wk.q_lo; g.k_lo = wk.k_lo;
       // x8_terms stays 3 — a block of x8_aside_mask (Q by default) keeps its A-side term for EVERY row; the other blocks take it for the special rows from
       // the row term (the launch skips it in blocks that swept both terms: gemm_pp.h).  With diffuse attention K and V of one token are one key among S for
       // every query and the term buys nothing (round 5: model, four draws); with an attention sink on that token they reach every row un-averaged.
       if (special) {
         if (h->qkv_aside_mask != 7) {
-          if (int rc = row_term(h->w->st_lo, g.W, g.N, g.K)) return rc;
-          g.cls_corr = h->w->cls_corr;
+          if (int rc = row_term(wk.st_lo, g.W, g.N, g.K)) return rc;
+          g.cls_corr = wk.cls_corr;
         }
-        g.vlo_sp = g.vt_lo ? nullptr : h->w->vlo_sp;
+        g.vlo_sp = g.vt_lo ? nullptr : wk.vlo_sp;
       }
-      if (int rc = launch_pp<PP_QK>(h, KC_GEMM_QKV, g)) return rc;
+      if (int rc = launch_pp<PP_QK>(h, wk.stream, KC_GEMM_QKV, g)) return rc;
       g.cls_corr = nullptr; g.vlo_sp = nullptr;
       // K3: attention (cls_as: + the context's special rows' low parts for the output projection's row term)
-      if (int rc = launch_attention(h, d_lens, B, Sp, x8, cls_as)) return rc;
+      if (int rc = launch_attention(h, wk, d_lens, B, Sp, x8, cls_as)) return rc;
       // K4: attention output projection + bias + LayerNorm(residual), in place on the raw stream; + vstats of the new rows
-      g.A = h->w->ctx; g.W = w.wo; g.bias = w.bo; g.N = MV_HIDDEN; g.K = MV_HIDDEN;
-      g.lnstats = st_in; g.lng = pend_g; g.lnb = pend_b; g.lnpart = st_mid; g.out16 = h->w->x16; g.out16b = h->w->xlo;
-      if (x8) { g.A8 = h->w->ctx8; g.W8 = w.wo8; g.x8_scale = w.sc_o; g.out8 = h->w->x8; g.x8_terms = 2; }
+      g.A = wk.ctx; g.W = w.wo; g.bias = w.bo; g.N = MV_HIDDEN; g.K = MV_HIDDEN;
+      g.lnstats = st_in; g.lng = pend_g; g.lnb = pend_b; g.lnpart = st_mid; g.out16 = wk.x16; g.out16b = wk.xlo;
+      if (x8) { g.A8 = wk.ctx8; g.W8 = w.wo8; g.x8_scale = w.sc_o; g.out8 = wk.x8; g.x8_terms = 2; }
       if (cls_as) {
-        if (int rc = row_term(h->w->cls_lo, g.W, g.N, g.K)) return rc;  // (the context's special low parts: launch_attention)
-        g.cls_corr = h->w->cls_corr; g.x8_terms = 1;  // (cls_corr stays set for the rest of the layer: every GEMM's term goes through the same buffer)
+        if (int rc = row_term(wk.cls_lo, g.W, g.N, g.K)) return rc;  // (the context's special low parts: launch_attention)
+        g.cls_corr = wk.cls_corr; g.x8_terms = 1;  // (cls_corr stays set for the rest of the layer: every GEMM's term goes through the same buffer)
         g.out8_hi_only = 0;  // FFN-1 sweeps the weight-side term only (hi8), but the lo8 plane IS the stream's low part: FFN-2 reads it back (gemm.h GemmArgs::out16b)
       }
-      if (special) g.sp_lo_out = h->w->st_lo;  // the stream rows' special low parts, read back and rewritten in place: FFN-1's row term, and FFN-2's residual
-      if (int rc = launch_pp<PP_RESLN3>(h, KC_GEMM_OUT, g)) return rc;
+      if (special) g.sp_lo_out = wk.st_lo;  // the stream rows' special low parts, read back and rewritten in place: FFN-1's row term, and FFN-2's residual
+      if (int rc = launch_pp<PP_RESLN3>(h, wk.stream, KC_GEMM_OUT, g)) return rc;
       pend_g = w.ln1g; pend_b = w.ln1b;
       // K5: FFN-1 + exact-erf GELU
-      g.A = h->w->x16; g.W = w.w1_f; g.bias = w.b1_f; g.N = MV_INTER; g.K = MV_HIDDEN; g.lnstats = st_mid; g.out16 = h->w->h16;
+      g.A = wk.x16; g.W = w.w1_f; g.bias = w.b1_f; g.N = MV_INTER; g.K = MV_HIDDEN; g.lnstats = st_mid; g.out16 = wk.h16;
       g.out16b = nullptr; g.lnpart = nullptr; g.sp_lo_out = nullptr;
-      if (x8) { g.A8 = h->w->x8; g.W8 = w.w1_f8; g.x8_scale = w.sc_1; g.out8 = h->w->h8; g.x8_terms = 2; }
+      if (x8) { g.A8 = wk.x8; g.W8 = w.w1_f8; g.x8_scale = w.sc_1; g.out8 = wk.h8; g.x8_terms = 2; }
       if (cls_as) {
-        if (int rc = row_term(h->w->st_lo, g.W, g.N, g.K)) return rc;
+        if (int rc = row_term(wk.st_lo, g.W, g.N, g.K)) return rc;
         g.x8_terms = 1;
         g.out8_hi_only = 1;  // h8 is FFN-2's A8: hi8 alone
-        g.sp_lo_out = h->w->cls_lo;  // the GELU output's special low parts: FFN-2's row term
+        g.sp_lo_out = wk.cls_lo;  // the GELU output's special low parts: FFN-2's row term
       }
-      if (int rc = launch_pp<PP_GELU>(h, KC_GEMM_FFN1, g)) return rc;
+      if (int rc = launch_pp<PP_GELU>(h, wk.stream, KC_GEMM_FFN1, g)) return rc;
       // K6: FFN-2 + bias + LayerNorm(residual)
-      g.A = h->w->h16; g.W = w.w2; g.bias = w.b2; g.N = MV_HIDDEN; g.K = MV_INTER;
-      g.lnstats = st_mid; g.lng = pend_g; g.lnb = pend_b; g.lnpart = st_in; g.out16 = h->w->x16; g.out16b = h->w->xlo;
-      if (x8) { g.A8 = h->w->h8; g.W8 = w.w28; g.x8_scale = w.sc_2; g.out8 = h->w->x8; g.x8_terms = 2; }
+      g.A = wk.h16; g.W = w.w2; g.bias = w.b2; g.N = MV_HIDDEN; g.K = MV_INTER;
+      g.lnstats = st_mid; g.lng = pend_g; g.lnb = pend_b; g.lnpart = st_in; g.out16 = wk.x16; g.out16b = wk.xlo;
+      if (x8) { g.A8 = wk.h8; g.W8 = w.w28; g.x8_scale = w.sc_2; g.out8 = wk.x8; g.x8_terms = 2; }
       if (cls_as) {
-        if (int rc = row_term(h->w->cls_lo, g.W, g.N, g.K)) return rc;
+        if (int rc = row_term(wk.cls_lo, g.W, g.N, g.K)) return rc;
         g.x8_terms = 1;
         g.out8_hi_only = 0;  // the lo8 plane is the stream's low part as well as the A-side operand of the next QKV projection's Q block
       } else {
         g.cls_corr = nullptr;
       }
-      if (special) g.sp_lo_out = h->w->st_lo;  // the next layer's QKV row term reads the new stream rows' special low parts in every pass of this compute dtype
-      if (int rc = launch_pp<PP_RESLN3>(h, KC_GEMM_FFN2, g)) return rc;
+      if (special) g.sp_lo_out = wk.st_lo;  // the next layer's QKV row term reads the new stream rows' special low parts in every pass of this compute dtype
+      if (int rc = launch_pp<PP_RESLN3>(h, wk.stream, KC_GEMM_FFN2, g)) return rc;
       pend_g = w.ln2g; pend_b = w.ln2b;
       if (last) { if (int rc = final_ln(w.ln2g, w.ln2b)) return rc; }  // the pooler reads a normalised stream
     } else {
-      g.A = h->w->x16; g.W = wqkv; g.bias = bqkv; g.N = 3 * MV_HIDDEN; g.K = MV_HIDDEN;
-      if (int rc = launch_small<EPI_QKV>(h, KC_GEMM_QKV, g)) return rc;
-      if (int rc = launch_attention(h, d_lens, B, Sp, false)) return rc;
-      g.A = h->w->ctx; g.W = w.wo; g.bias = w.bo; g.N = MV_HIDDEN; g.K = MV_HIDDEN; g.xres = h->w->xres;
-      if (int rc = launch_small<EPI_RES>(h, KC_GEMM_OUT, g)) return rc;
-      if (int rc = run_ln(h->w->xres, h->w->x16, (int)M, w.ln1g, w.ln1b)) return rc;
-      g.A = h->w->x16; g.W = w.w1; g.bias = w.b1; g.N = MV_INTER; g.K = MV_HIDDEN; g.out16 = h->w->h16;
-      if (int rc = launch_small<EPI_GELU>(h, KC_GEMM_FFN1, g)) return rc;
-      g.A = h->w->h16; g.W = w.w2; g.bias = w.b2; g.N = MV_HIDDEN; g.K = MV_INTER; g.xres = h->w->xres;
-      if (int rc = launch_small<EPI_RES>(h, KC_GEMM_FFN2, g)) return rc;
-      if (int rc = run_ln(h->w->xres, h->w->x16, (int)M, w.ln2g, w.ln2b)) return rc;
+      g.A = wk.x16; g.W = wqkv; g.bias = bqkv; g.N = 3 * MV_HIDDEN; g.K = MV_HIDDEN;
+      if (int rc = launch_small<EPI_QKV>(h, wk.stream, KC_GEMM_QKV, g)) return rc;
+      if (int rc = launch_attention(h, wk, d_lens, B, Sp, false)) return rc;
+      g.A = wk.ctx; g.W = w.wo; g.bias = w.bo; g.N = MV_HIDDEN; g.K = MV_HIDDEN; g.xres = wk.xres;
+      if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_GEMM_OUT, g)) return rc;
+      if (int rc = run_ln(wk.xres, wk.x16, (int)M, w.ln1g, w.ln1b)) return rc;
+      g.A = wk.x16; g.W = w.w1; g.bias = w.b1; g.N = MV_INTER; g.K = MV_HIDDEN; g.out16 = wk.h16;
+      if (int rc = launch_small<EPI_GELU>(h, wk.stream, KC_GEMM_FFN1, g)) return rc;
+      g.A = wk.h16; g.W = w.w2; g.bias = w.b2; g.N = MV_HIDDEN; g.K = MV_INTER; g.xres = wk.xres;
+      if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_GEMM_FFN2, g)) return rc;
+      if (int rc = run_ln(wk.xres, wk.x16, (int)M, w.ln2g, w.ln2b)) return rc;
     }
   }
   if (u_out) {
-    ProfScope ps(h, KC_POOL_HEAD);
-    if (int rc = pool_head(h, h->w->xres, (size_t)Sp * MV_HIDDEN, B, u_out)) return rc;
+    ProfScope ps(h, wk.stream, KC_POOL_HEAD);
+    if (int rc = pool_head(h, wk, wk.xres, (size_t)Sp * MV_HIDDEN, B, u_out)) return rc;
   }
   return MV_OK;
 }
@@ -746,7 +749,7 @@ int max_rows_for(mv_handle* h, int S_in) {
 // K9 + K10 fused (match_topk.h): logits / probs / psame_out are optional full outputs; k >= 1 selects the best anchor
 // (and, with topk_p / topk_idx, the k best).  4 issue reports per workgroup when that already fills the chip, else 1
 // (the same bits either way).
-int match_dev(mv_handle* h, const float* u_dev, int B, float* logits, float* probs, float* psame_out, int k, float* best_out,
+int match_dev(mv_handle* h, Work& wk, const float* u_dev, int B, float* logits, float* probs, float* psame_out, int k, float* best_out,
               int32_t* idx_out, float* topk_p = nullptr, int32_t* topk_idx = nullptr) {
   const int G = h->n_anchors;
   if (G <= 0) return fail(h, MV_ERR_STATE, "anchor bank is empty (call mv_anchor_append / mv_anchor_set first)");
@@ -758,43 +761,42 @@ int match_dev(mv_handle* h, const float* u_dev, int B, float* logits, float* pro
   if ((int64_t)a.nchunk * k > 1024) return fail(h, MV_ERR_INVALID, "top-k: anchors / 256 * k must not exceed 1024");
   a.logits = logits; a.probs = probs; a.psame = psame_out;
   a.best = best_out; a.best_idx = idx_out; a.topk_p = topk_p; a.topk_idx = topk_idx;
-  a.part_p = h->w->part_p; a.part_q = h->w->part_q; a.part_i = h->w->part_i;
+  a.part_p = wk.part_p; a.part_q = wk.part_q; a.part_i = wk.part_i;
   {
-    ProfScope ps(h, KC_MATCH);
+    ProfScope ps(h, wk.stream, KC_MATCH);
     const dim3 grid(small ? 1 : a.nchunk, (B + 3) / 4);
 #define MV_MATCH(PD)                                                                                                                          \
-    if (small && a.logits) hipLaunchKernelGGL((match_topk_kernel<2, 128, 64, 1, 2, PD>), grid, dim3(256), 0, h->w->stream, u_dev, h->anchors, h->Wm, a); \
-    else if (small) hipLaunchKernelGGL((match_topk_kernel<2, 128, 64, 0, 2, PD>), grid, dim3(256), 0, h->w->stream, u_dev, h->anchors, h->Wm, a);        \
-    else if (a.logits) hipLaunchKernelGGL((match_topk_kernel<2, 256, 32, 1, 2, PD>), grid, dim3(512), 0, h->w->stream, u_dev, h->anchors, h->Wm, a);     \
-    else hipLaunchKernelGGL((match_topk_kernel<2, 256, 32, 0, 2, PD>), grid, dim3(512), 0, h->w->stream, u_dev, h->anchors, h->Wm, a)
+    if (small && a.logits) hipLaunchKernelGGL((match_topk_kernel<2, 128, 64, 1, 2, PD>), grid, dim3(256), 0, wk.stream, u_dev, h->anchors, h->Wm, a); \
+    else if (small) hipLaunchKernelGGL((match_topk_kernel<2, 128, 64, 0, 2, PD>), grid, dim3(256), 0, wk.stream, u_dev, h->anchors, h->Wm, a);        \
+    else if (a.logits) hipLaunchKernelGGL((match_topk_kernel<2, 256, 32, 1, 2, PD>), grid, dim3(512), 0, wk.stream, u_dev, h->anchors, h->Wm, a);     \
+    else hipLaunchKernelGGL((match_topk_kernel<2, 256, 32, 0, 2, PD>), grid, dim3(512), 0, wk.stream, u_dev, h->anchors, h->Wm, a)
     if (h->P == MV_PROJ) { MV_MATCH(MV_PROJ); } else { MV_MATCH(MV_HIDDEN); }
 #undef MV_MATCH
     if (int rc = launch_check(h, "match_topk")) return rc;
   }
   if (a.nchunk > 1 && k > 0) {
-    ProfScope ps(h, KC_TOPK);
-    launch_topk_merge(a, h->w->stream);
+    ProfScope ps(h, wk.stream, KC_TOPK);
+    launch_topk_merge(a, wk.stream);
     if (int rc = launch_check(h, "topk_merge")) return rc;
   }
   return MV_OK;
 }
 
-int sync_all(mv_handle* h) {
-  for (int wi = 0; wi < h->n_alloc; ++wi) HIPCHK(h, hipStreamSynchronize(h->work[wi].stream));
-  h->dual_pending = false;
+int sync_all(mv_handle* h) {  // (a ticket stays in flight until mv_forward_ragged_end collects it)
+  for (int wi = 0; wi < h->n_alloc; ++wi) { HIPCHK(h, hipStreamSynchronize(h->work[wi].stream)); h->work[wi].sweep = false; }
   return MV_OK;
 }
 
-// Every entry point but the resident sweep works on set 0; a sweep may have left set 1 busy (it reads the anchor
-// bank and the resident corpus): wait for it first.
+// Every entry point but the resident sweep works on set 0 (mv_forward_ragged_begin: on a set without a ticket), stream-ordered behind
+// what is there; a sweep may have left the other set busy (it reads the anchor bank and the resident corpus): wait for it first.
 int check_ready(mv_handle* h) {
   if (!h) return MV_ERR_INVALID;
   if (!h->finalized) return fail(h, MV_ERR_STATE, "weights not finalized (mv_finalize_weights)");
-  if (h->dual_pending) {
-    HIPCHK(h, hipStreamSynchronize(h->work[1].stream));
-    h->dual_pending = false;
-  }
-  h->w = &h->work[0];
+  for (int wi = 1; wi < h->n_alloc; ++wi)
+    if (h->work[wi].sweep) {
+      HIPCHK(h, hipStreamSynchronize(h->work[wi].stream));
+      h->work[wi].sweep = false;
+    }
   return MV_OK;
 }
 
@@ -826,10 +828,10 @@ int need(mv_handle* h, const std::string& k, std::initializer_list<int64_t> shap
   return MV_OK;
 }
 
-int upload_f32(mv_handle* h, float** dst, const float* src, int64_t n) {
-  if (int rc = dev_alloc(h, dst, n, false)) return rc;
-  HIPCHK(h, hipMemcpyAsync(*dst, src, (size_t)n * 4, hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
+int upload_f32(mv_handle* h, hipStream_t stream, float** dst, const float* src, int64_t n) {
+  if (int rc = dev_alloc(h, stream, dst, n, false)) return rc;
+  HIPCHK(h, hipMemcpyAsync(*dst, src, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+  HIPCHK(h, hipStreamSynchronize(stream));
   return MV_OK;
 }
 // Virtual LayerNorm weights (gemm_pp.h): W''[n][k] = W[n][k] gamma[k] - mean_k(W[n][.] gamma[.]),  b'[n] = b[n] + sum_k W[n][k] beta[k]
@@ -902,22 +904,156 @@ void make_x8_weight_planes(const float* W, int64_t N, int64_t K, std::vector<uin
   *scale_word = e8 * 0x01010101;
 }
 
-int upload_x8_weight(mv_handle* h, uint8_t** dst, int* scale_word, const float* W, int64_t N, int64_t K) {
+int upload_x8_weight(mv_handle* h, hipStream_t stream, uint8_t** dst, int* scale_word, const float* W, int64_t N, int64_t K) {
   std::vector<uint8_t> tmp;
   make_x8_weight_planes(W, N, K, tmp, scale_word);
-  if (int rc = dev_alloc(h, dst, (int64_t)tmp.size(), false)) return rc;
-  HIPCHK(h, hipMemcpyAsync(*dst, tmp.data(), tmp.size(), hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
+  if (int rc = dev_alloc(h, stream, dst, (int64_t)tmp.size(), false)) return rc;
+  HIPCHK(h, hipMemcpyAsync(*dst, tmp.data(), tmp.size(), hipMemcpyHostToDevice, stream));
+  HIPCHK(h, hipStreamSynchronize(stream));
   return MV_OK;
 }
 
-int upload_f16(mv_handle* h, half_t** dst, const float* src, int64_t n, float scale = 1.0f) {
+int upload_f16(mv_handle* h, hipStream_t stream, half_t** dst, const float* src, int64_t n, float scale = 1.0f) {
   std::vector<uint16_t> tmp((size_t)n);
   for (int64_t i = 0; i < n; ++i) tmp[(size_t)i] = f32_to_f16_bits(src[i] * scale);
-  if (int rc = dev_alloc(h, dst, n, false)) return rc;
-  HIPCHK(h, hipMemcpyAsync(*dst, tmp.data(), (size_t)n * 2, hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
+  if (int rc = dev_alloc(h, stream, dst, n, false)) return rc;
+  HIPCHK(h, hipMemcpyAsync(*dst, tmp.data(), (size_t)n * 2, hipMemcpyHostToDevice, stream));
+  HIPCHK(h, hipStreamSynchronize(stream));
   return MV_OK;
+}
+
+// ---- the one planner and the one pass loop -------------------------------------------------------------------------------------------------------------------
+// plan_batch: rows [0, B) of lengths `lens` into pl.  by_length false: the identity order in passes of max_rows_for(S) rows at width S.  by_length true
+// (mv_forward_ragged*: a pad-to-longest batch of UNSORTED rows): the rows ordered (stably) by the padded length of their own token count, a run of one padded
+// length merged into the next longer one while it holds fewer than min_tokens padded tokens, each group then cut into passes of max_rows_for(its width) rows.
+// max_rows > 0 caps the rows of a pass further (the resident sweep's batch).
+int plan_batch(mv_handle* h, const int32_t* lens, int B, int S, int min_tokens, bool by_length, int max_rows, Plan& pl) {
+  pl.order.clear(), pl.passes.clear(), pl.tokens = 0;
+  auto cut = [&](int start, int end, int width) -> int {  // rows [start, end) of the order, at `width` tokens per row
+    int rows = max_rows_for(h, width);
+    if (max_rows > 0 && max_rows < rows) rows = max_rows;
+    if (rows <= 0) return fail(h, MV_ERR_CAPACITY, "mv_config.max_tokens too small for one row of this length");
+    for (int first = start; first < end; first += rows) {
+      const int n = end - first < rows ? end - first : rows;
+      int m = INT32_MAX;
+      for (int i = first; i < first + n; ++i) m = std::min(m, lens[pl.order.empty() ? i : pl.order[i]]);
+      pl.passes.push_back({first, n, width, m, pl.tokens});
+      pl.tokens += (int64_t)n * width;
+    }
+    return MV_OK;
+  };
+  if (!by_length) return cut(0, B, S);
+  auto pad = [&](int r) { return padded_len(lens[r] < 1 ? 1 : lens[r]); };  // of caller row r
+  pl.order.resize(B);
+  for (int i = 0; i < B; ++i) {
+    if (lens[i] > S) return fail(h, MV_ERR_INVALID, "a row is longer than S");
+    pl.order[i] = i;
+  }
+  std::stable_sort(pl.order.begin(), pl.order.end(), [&](int a, int b) { return pad(a) < pad(b); });
+  int start = 0;
+  for (int end = 1; end <= B; ++end) {
+    const int width = pad(pl.order[end - 1]);
+    if (end < B && pad(pl.order[end]) == width) continue;                   // inside a run of one padded length
+    if (end < B && (int64_t)(end - start) * width < min_tokens) continue;  // too small a pass: these rows travel with the next longer group
+    if (int rc = cut(start, end, width < S ? width : S)) return rc;
+    start = end;
+  }
+  return MV_OK;
+}
+
+// What run_passes does with a planned batch besides encoding it, and where the results go
+struct Job {
+  const int32_t *ids = nullptr, *lens = nullptr;  // host, plan order: the ids of every pass at its own width, back to back (Pass::tok); NULL: the resident corpus
+  int64_t c_row = 0; bool keep_psame = false;    // ... whose row c_row is plan row 0: ids read in place at pitch c_S, results (and P(same)) to its arrays
+  Stage out;                                      // host results, plan order (NULL: not asked for; out.ids / out.lens unused)
+  bool match = false;                             // + the matcher: the best anchor always, logits / probs where `out` asks for them
+  float* u_dev = nullptr;                         // the encoder's output to the device here (mv_anchor_append: the bank) instead of wk.u
+  int n_layers = -1; bool full = false;           // mv_debug_encode: the layers to run, and the full last layer (encode_dev)
+};
+
+// The one pass loop: the passes [p0, p1) of pl enqueued on workspace set wk without waiting; after a failure it waits for what was enqueued.  Host ids /
+// lengths: one upload when they fit wk's buffers, else one per pass at its own width.  Host results: one download each when the rows fit wk's max_batch
+// rows (every pass writes at its own rows there), else one per pass.
+int run_passes(mv_handle* h, Work& wk, const Plan& pl, size_t p0, size_t p1, const Job& j) {
+  const int G = h->n_anchors;
+  const size_t P = (size_t)h->P;
+  const Pass &a = pl.passes[p0], &z = pl.passes[p1 - 1];
+  const int rows = z.first + z.rows - a.first;
+  const int64_t tokens = z.tok + (int64_t)z.rows * z.width - a.tok;
+  const bool one_down = rows <= h->cfg.max_batch, one_up = one_down && tokens <= h->cap_tokens;
+  auto upload = [&](int first, int n, int64_t tok, int64_t n_tok) -> int {
+    HIPCHK(h, hipMemcpyAsync(wk.d_ids, j.ids + tok, (size_t)n_tok * 4, hipMemcpyHostToDevice, wk.stream));
+    HIPCHK(h, hipMemcpyAsync(wk.d_lens, j.lens + first, (size_t)n * 4, hipMemcpyHostToDevice, wk.stream));
+    return MV_OK;
+  };
+  auto download = [&](int first, int n) -> int {  // plan rows [first, first + n) from rows [0, n) of wk's buffers
+    const Stage& o = j.out;
+    const size_t bg = (size_t)n * G;
+    if (o.logits) HIPCHK(h, hipMemcpyAsync(o.logits + (size_t)first * G * 2, wk.logits, bg * 8, hipMemcpyDeviceToHost, wk.stream));
+    if (o.probs) HIPCHK(h, hipMemcpyAsync(o.probs + (size_t)first * G * 2, wk.probs, bg * 8, hipMemcpyDeviceToHost, wk.stream));
+    if (o.best) HIPCHK(h, hipMemcpyAsync(o.best + (size_t)first * 2, wk.best, (size_t)n * 8, hipMemcpyDeviceToHost, wk.stream));
+    if (o.idx) HIPCHK(h, hipMemcpyAsync(o.idx + first, wk.best_idx, (size_t)n * 4, hipMemcpyDeviceToHost, wk.stream));
+    if (o.embed) HIPCHK(h, hipMemcpyAsync(o.embed + (size_t)first * P, wk.u, (size_t)n * P * 4, hipMemcpyDeviceToHost, wk.stream));
+    return MV_OK;
+  };
+  auto run = [&]() -> int {
+    if (j.ids && one_up)
+      if (int rc = upload(a.first, rows, a.tok, tokens)) return rc;
+    for (size_t i = p0; i < p1; ++i) {
+      const Pass& p = pl.passes[i];
+      const int32_t* ids = j.ids ? wk.d_ids + (one_up ? p.tok - a.tok : 0) : h->c_ids + (size_t)(j.c_row + p.first) * h->c_S;
+      const int32_t* lens = j.ids ? wk.d_lens + (one_up ? p.first - a.first : 0) : h->c_lens + j.c_row + p.first;
+      if (j.ids && !one_up)
+        if (int rc = upload(p.first, p.rows, p.tok, (int64_t)p.rows * p.width)) return rc;
+      const size_t r = one_down ? (size_t)(p.first - a.first) : 0;  // the pass's first row in wk's buffers
+      float* u = j.u_dev ? j.u_dev + (size_t)p.first * P : wk.u + r * P;
+      if (int rc = encode_dev(h, wk, ids, lens, p.min_len, p.rows, p.width, j.n_layers, u, j.full, j.ids ? p.width : h->c_S)) return rc;
+      if (!j.ids) {
+        const size_t c = (size_t)(j.c_row + p.first);
+        if (int rc = match_dev(h, wk, u, p.rows, nullptr, nullptr, j.keep_psame ? h->c_psame + c * G : nullptr, 1, h->c_best + c * 2, h->c_idx + c)) return rc;
+      } else if (j.match) {  // only the outputs the caller asked for leave the kernel (the best anchor always does)
+        if (int rc = match_dev(h, wk, u, p.rows, j.out.logits ? wk.logits + r * G * 2 : nullptr, j.out.probs ? wk.probs + r * G * 2 : nullptr, nullptr, 1,
+                               wk.best + r * 2, wk.best_idx + r)) return rc;
+      }
+      if (!one_down)
+        if (int rc = download(p.first, p.rows)) return rc;
+    }
+    return one_down ? download(a.first, rows) : MV_OK;
+  };
+  const int rc = run();
+  if (rc != MV_OK) hipStreamSynchronize(wk.stream);
+  return rc;
+}
+
+// mv_forward / mv_encode / mv_anchor_append / mv_debug_encode: the rows in their own order, the pass loop on workspace set 0, then wait.
+int run_in_order(mv_handle* h, const int32_t* lens, int B, int S, Job& j) {
+  if (int rc = plan_batch(h, lens, B, S, 0, false, 0, h->plan)) return rc;
+  if (int rc = run_passes(h, h->work[0], h->plan, 0, h->plan.passes.size(), j)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->work[0].stream));
+  return MV_OK;
+}
+
+// The rows of a by-length batch gathered into plan order: each pass's ids at its own width (ids [B][S]).
+void gather(const Plan& pl, const int32_t* ids, const int32_t* lens, int S, int32_t* ids_out, int32_t* lens_out) {
+  for (const Pass& p : pl.passes)
+    for (int i = 0; i < p.rows; ++i) {
+      const size_t r = (size_t)pl.order[p.first + i];
+      std::memcpy(ids_out + p.tok + (int64_t)i * p.width, ids + r * S, (size_t)p.width * 4);
+      lens_out[p.first + i] = lens[r];
+    }
+}
+
+// Row i of the plan order (st) to row order[i] of the caller's arrays: the outputs st holds.
+void scatter(const mv_handle* h, const std::vector<int>& order, int G, const Stage& st, float* logits, float* probs, float* best, int32_t* best_idx, float* embed) {
+  const size_t g2 = (size_t)G * 2, P = (size_t)h->P;
+  for (size_t i = 0; i < order.size(); ++i) {
+    const size_t o = (size_t)order[i];
+    if (st.logits) std::memcpy(logits + o * g2, st.logits + i * g2, g2 * 4);
+    if (st.probs) std::memcpy(probs + o * g2, st.probs + i * g2, g2 * 4);
+    best[o * 2] = st.best[i * 2]; best[o * 2 + 1] = st.best[i * 2 + 1];
+    best_idx[o] = st.idx[i];
+    if (st.embed) std::memcpy(embed + o * P, st.embed + i * P, P * 4);
+  }
 }
 
 }  // namespace
@@ -1052,47 +1188,47 @@ int mv_create(int device, const mv_config* cfg, mv_handle** out) try {
   const int64_t BG = (int64_t)cfg->max_batch * cfg->max_anchors;
   const int64_t Bp = round_up(cfg->max_batch, 256);  // [CLS]-row buffers of the pruned last layer
   for (int wi = 0; wi < h->n_alloc; ++wi) {
-    h->w = &h->work[wi];
-    A(dev_alloc(h, &h->w->d_ids, T));
-    A(dev_alloc(h, &h->w->d_lens, (int64_t)cfg->max_batch + 16));
-    A(dev_alloc(h, &h->w->xres, T * MV_HIDDEN));
-    A(dev_alloc(h, &h->w->x16, T * MV_HIDDEN));
-    A(dev_alloc(h, &h->w->q, T * MV_HIDDEN));
-    A(dev_alloc(h, &h->w->k, T * MV_HIDDEN));
-    A(dev_alloc(h, &h->w->vt, T * MV_HIDDEN));
-    A(dev_alloc(h, &h->w->ctx, T * MV_HIDDEN));
-    A(dev_alloc(h, &h->w->h16, T * MV_INTER));
-    A(dev_alloc(h, &h->w->lnstats, T * 6));
-    A(dev_alloc(h, &h->w->lnpart, T * 6));
-    A(dev_alloc(h, &h->w->c32, Bp * MV_HIDDEN));
-    A(dev_alloc(h, &h->w->cq, Bp * MV_HIDDEN));
-    A(dev_alloc(h, &h->w->c16, Bp * MV_HIDDEN));
-    A(dev_alloc(h, &h->w->cctx, Bp * MV_HIDDEN));
-    A(dev_alloc(h, &h->w->ch16, Bp * MV_INTER));
-    A(dev_alloc(h, &h->w->u, (int64_t)cfg->max_batch * h->P));
-    A(dev_alloc(h, &h->w->pooled, (int64_t)cfg->max_batch * MV_HIDDEN));
-    A(dev_alloc(h, &h->w->u_in, (int64_t)cfg->max_batch * h->P));
-    A(dev_alloc(h, &h->w->logits, BG * 2));
-    A(dev_alloc(h, &h->w->probs, BG * 2));
-    A(dev_alloc(h, &h->w->psame, BG));
-    A(dev_alloc(h, &h->w->best, (int64_t)cfg->max_batch * 2));
-    A(dev_alloc(h, &h->w->best_idx, cfg->max_batch));
-    A(dev_alloc(h, &h->w->topk_p, (int64_t)cfg->max_batch * 64));
-    A(dev_alloc(h, &h->w->topk_idx, (int64_t)cfg->max_batch * 64));
+    Work& wk = h->work[wi];
+    A(dev_alloc(h, wk.stream, &wk.d_ids, T));
+    A(dev_alloc(h, wk.stream, &wk.d_lens, (int64_t)cfg->max_batch + 16));
+    A(dev_alloc(h, wk.stream, &wk.xres, T * MV_HIDDEN));
+    A(dev_alloc(h, wk.stream, &wk.x16, T * MV_HIDDEN));
+    A(dev_alloc(h, wk.stream, &wk.q, T * MV_HIDDEN));
+    A(dev_alloc(h, wk.stream, &wk.k, T * MV_HIDDEN));
+    A(dev_alloc(h, wk.stream, &wk.vt, T * MV_HIDDEN));
+    A(dev_alloc(h, wk.stream, &wk.ctx, T * MV_HIDDEN));
+    A(dev_alloc(h, wk.stream, &wk.h16, T * MV_INTER));
+    A(dev_alloc(h, wk.stream, &wk.lnstats, T * 6));
+    A(dev_alloc(h, wk.stream, &wk.lnpart, T * 6));
+    A(dev_alloc(h, wk.stream, &wk.c32, Bp * MV_HIDDEN));
+    A(dev_alloc(h, wk.stream, &wk.cq, Bp * MV_HIDDEN));
+    A(dev_alloc(h, wk.stream, &wk.c16, Bp * MV_HIDDEN));
+    A(dev_alloc(h, wk.stream, &wk.cctx, Bp * MV_HIDDEN));
+    A(dev_alloc(h, wk.stream, &wk.ch16, Bp * MV_INTER));
+    A(dev_alloc(h, wk.stream, &wk.u, (int64_t)cfg->max_batch * h->P));
+    A(dev_alloc(h, wk.stream, &wk.pooled, (int64_t)cfg->max_batch * MV_HIDDEN));
+    A(dev_alloc(h, wk.stream, &wk.u_in, (int64_t)cfg->max_batch * h->P));
+    A(dev_alloc(h, wk.stream, &wk.logits, BG * 2));
+    A(dev_alloc(h, wk.stream, &wk.probs, BG * 2));
+    A(dev_alloc(h, wk.stream, &wk.psame, BG));
+    A(dev_alloc(h, wk.stream, &wk.best, (int64_t)cfg->max_batch * 2));
+    A(dev_alloc(h, wk.stream, &wk.best_idx, cfg->max_batch));
+    A(dev_alloc(h, wk.stream, &wk.topk_p, (int64_t)cfg->max_batch * 64));
+    A(dev_alloc(h, wk.stream, &wk.topk_idx, (int64_t)cfg->max_batch * 64));
     {
       const int64_t nch = (cfg->max_anchors + 255) / 256;
       const int64_t per = nch > 1 ? (nch * MK_KMAX < 1024 ? nch * MK_KMAX : 1024) : 0;  // chunks x k <= 1024 (match_dev)
-      A(dev_alloc(h, &h->w->part_p, (int64_t)cfg->max_batch * per));
-      A(dev_alloc(h, &h->w->part_q, (int64_t)cfg->max_batch * per));
-      A(dev_alloc(h, &h->w->part_i, (int64_t)cfg->max_batch * per));
+      A(dev_alloc(h, wk.stream, &wk.part_p, (int64_t)cfg->max_batch * per));
+      A(dev_alloc(h, wk.stream, &wk.part_q, (int64_t)cfg->max_batch * per));
+      A(dev_alloc(h, wk.stream, &wk.part_i, (int64_t)cfg->max_batch * per));
     }
-    if (rc == MV_OK && hipStreamSynchronize(h->w->stream) != hipSuccess) rc = MV_ERR_HIP;
+    if (rc == MV_OK && hipStreamSynchronize(wk.stream) != hipSuccess) rc = MV_ERR_HIP;
   }
-  h->w = &h->work[0];
-  A(dev_alloc(h, &h->anchors, (int64_t)cfg->max_anchors * h->P));
-  A(dev_alloc(h, &h->x8_sat, 1));  // (zeroed by dev_alloc)
-  A(dev_alloc(h, &h->attn_conc, 4));
-  if (rc == MV_OK && hipStreamSynchronize(h->w->stream) != hipSuccess) rc = MV_ERR_HIP;
+  const hipStream_t s0 = h->work[0].stream;
+  A(dev_alloc(h, s0, &h->anchors, (int64_t)cfg->max_anchors * h->P));
+  A(dev_alloc(h, s0, &h->x8_sat, 1));  // (zeroed by dev_alloc)
+  A(dev_alloc(h, s0, &h->attn_conc, 4));
+  if (rc == MV_OK && hipStreamSynchronize(s0) != hipSuccess) rc = MV_ERR_HIP;
   if (rc != MV_OK) {
     g_create_error = h->err.empty() ? "workspace allocation failed" : h->err;
     return rc;  // the guard destroys the handle
@@ -1151,6 +1287,7 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
                                    "sweeps); bf16 is a storage dtype of mv_load_tensor only (include/memvul_hip.h)");
   const bool precise = compute_dtype == MV_F16X8;
   HIPCHK(h, hipSetDevice(h->device));
+  const hipStream_t s0 = h->work[0].stream;  // (the uploads)
   const mv_config& c = h->cfg;
   const std::string P = "_text_field_embedder.token_embedder_tokens.transformer_model.";
   const int64_t H = MV_HIDDEN, I = MV_INTER;
@@ -1158,20 +1295,20 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
   int rc;
 #define NEED(key, ...) if ((rc = need(h, key, {__VA_ARGS__}, &t)) != MV_OK) return rc
   NEED(P + "embeddings.word_embeddings.weight", c.vocab_size, H);
-  if ((rc = upload_f32(h, &h->wemb, t->data.data(), (int64_t)c.vocab_size * H))) return rc;
+  if ((rc = upload_f32(h, s0, &h->wemb, t->data.data(), (int64_t)c.vocab_size * H))) return rc;
   {
     const HostTensor* tp = find(h, P + "embeddings.position_embeddings.weight");
     if (!tp) return fail(h, MV_ERR_MISSING_WEIGHT, "missing weight: " + P + "embeddings.position_embeddings.weight");
     if (tp->shape.size() != 2 || tp->shape[1] != H || tp->shape[0] < c.max_pos)
       return fail(h, MV_ERR_INVALID, "bad shape for position_embeddings");
-    if ((rc = upload_f32(h, &h->pemb, tp->data.data(), (int64_t)c.max_pos * H))) return rc;
+    if ((rc = upload_f32(h, s0, &h->pemb, tp->data.data(), (int64_t)c.max_pos * H))) return rc;
   }
   NEED(P + "embeddings.token_type_embeddings.weight", c.type_vocab, H);
-  if ((rc = upload_f32(h, &h->temb, t->data.data(), H))) return rc;  // row 0 only: type ids are all zero on this path
+  if ((rc = upload_f32(h, s0, &h->temb, t->data.data(), H))) return rc;  // row 0 only: type ids are all zero on this path
   NEED(P + "embeddings.LayerNorm.weight", H);
-  if ((rc = upload_f32(h, &h->embg, t->data.data(), H))) return rc;
+  if ((rc = upload_f32(h, s0, &h->embg, t->data.data(), H))) return rc;
   NEED(P + "embeddings.LayerNorm.bias", H);
-  if ((rc = upload_f32(h, &h->embb, t->data.data(), H))) return rc;
+  if ((rc = upload_f32(h, s0, &h->embb, t->data.data(), H))) return rc;
   h->L.resize(c.layers);
   for (int l = 0; l < c.layers; ++l) {
     const std::string q = P + "encoder.layer." + std::to_string(l) + ".";
@@ -1188,7 +1325,7 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
         pack[(size_t)(H * H + i)] = t2->data[(size_t)i];
         pack[(size_t)(2 * H * H + i)] = t3->data[(size_t)i];
       }
-      if ((rc = upload_f16(h, &w.wqkv, pack.data(), 3 * H * H))) return rc;
+      if ((rc = upload_f16(h, s0, &w.wqkv, pack.data(), 3 * H * H))) return rc;
       wqkv_host = pack;
     }
     if ((rc = need(h, q + "attention.self.query.bias", {H}, &t))) return rc;
@@ -1201,7 +1338,7 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
         pack[(size_t)(H + i)] = t2->data[(size_t)i];
         pack[(size_t)(2 * H + i)] = t3->data[(size_t)i];
       }
-      if ((rc = upload_f32(h, &w.bqkv, pack.data(), 3 * H))) return rc;
+      if ((rc = upload_f32(h, s0, &w.bqkv, pack.data(), 3 * H))) return rc;
       bqkv_host = pack;
     }
     {  // the LayerNorm in front of this layer's QKV projection: the embedding LayerNorm or the previous layer's output LayerNorm
@@ -1211,23 +1348,23 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
       if ((rc = need(h, lnk + "bias", {H}, &tb))) return rc;
       std::vector<float> Wf, bf;
       fold_layernorm(wqkv_host.data(), bqkv_host.data(), tg->data.data(), tb->data.data(), 3 * H, H, Wf, bf);
-      if ((rc = upload_f16(h, &w.wqkv_f, Wf.data(), 3 * H * H))) return rc;
-      if (precise && (rc = upload_x8_weight(h, &w.wqkv_f8, &w.sc_qkv, Wf.data(), 3 * H, H))) return rc;
-      if ((rc = upload_f32(h, &w.bqkv_f, bf.data(), 3 * H))) return rc;
+      if ((rc = upload_f16(h, s0, &w.wqkv_f, Wf.data(), 3 * H * H))) return rc;
+      if (precise && (rc = upload_x8_weight(h, s0, &w.wqkv_f8, &w.sc_qkv, Wf.data(), 3 * H, H))) return rc;
+      if ((rc = upload_f32(h, s0, &w.bqkv_f, bf.data(), 3 * H))) return rc;
     }
     NEED(q + "attention.output.dense.weight", H, H);
-    if ((rc = upload_f16(h, &w.wo, t->data.data(), H * H))) return rc;
-    if (precise && (rc = upload_x8_weight(h, &w.wo8, &w.sc_o, t->data.data(), H, H))) return rc;
+    if ((rc = upload_f16(h, s0, &w.wo, t->data.data(), H * H))) return rc;
+    if (precise && (rc = upload_x8_weight(h, s0, &w.wo8, &w.sc_o, t->data.data(), H, H))) return rc;
     NEED(q + "attention.output.dense.bias", H);
-    if ((rc = upload_f32(h, &w.bo, t->data.data(), H))) return rc;
+    if ((rc = upload_f32(h, s0, &w.bo, t->data.data(), H))) return rc;
     NEED(q + "attention.output.LayerNorm.weight", H);
-    if ((rc = upload_f32(h, &w.ln1g, t->data.data(), H))) return rc;
+    if ((rc = upload_f32(h, s0, &w.ln1g, t->data.data(), H))) return rc;
     NEED(q + "attention.output.LayerNorm.bias", H);
-    if ((rc = upload_f32(h, &w.ln1b, t->data.data(), H))) return rc;
+    if ((rc = upload_f32(h, s0, &w.ln1b, t->data.data(), H))) return rc;
     NEED(q + "intermediate.dense.weight", I, H);
-    if ((rc = upload_f16(h, &w.w1, t->data.data(), I * H))) return rc;
+    if ((rc = upload_f16(h, s0, &w.w1, t->data.data(), I * H))) return rc;
     NEED(q + "intermediate.dense.bias", I);
-    if ((rc = upload_f32(h, &w.b1, t->data.data(), I))) return rc;
+    if ((rc = upload_f32(h, s0, &w.b1, t->data.data(), I))) return rc;
     {  // FFN-1 with the attention-output LayerNorm folded in
       const HostTensor *tw = nullptr, *tg = nullptr, *tb = nullptr;
       if ((rc = need(h, q + "intermediate.dense.weight", {I, H}, &tw))) return rc;
@@ -1235,19 +1372,19 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
       if ((rc = need(h, q + "attention.output.LayerNorm.bias", {H}, &tb))) return rc;
       std::vector<float> Wf, bf;
       fold_layernorm(tw->data.data(), t->data.data(), tg->data.data(), tb->data.data(), I, H, Wf, bf);
-      if ((rc = upload_f16(h, &w.w1_f, Wf.data(), I * H))) return rc;
-      if (precise && (rc = upload_x8_weight(h, &w.w1_f8, &w.sc_1, Wf.data(), I, H))) return rc;
-      if ((rc = upload_f32(h, &w.b1_f, bf.data(), I))) return rc;
+      if ((rc = upload_f16(h, s0, &w.w1_f, Wf.data(), I * H))) return rc;
+      if (precise && (rc = upload_x8_weight(h, s0, &w.w1_f8, &w.sc_1, Wf.data(), I, H))) return rc;
+      if ((rc = upload_f32(h, s0, &w.b1_f, bf.data(), I))) return rc;
     }
     NEED(q + "output.dense.weight", H, I);
-    if ((rc = upload_f16(h, &w.w2, t->data.data(), H * I))) return rc;
-    if (precise && (rc = upload_x8_weight(h, &w.w28, &w.sc_2, t->data.data(), H, I))) return rc;
+    if ((rc = upload_f16(h, s0, &w.w2, t->data.data(), H * I))) return rc;
+    if (precise && (rc = upload_x8_weight(h, s0, &w.w28, &w.sc_2, t->data.data(), H, I))) return rc;
     NEED(q + "output.dense.bias", H);
-    if ((rc = upload_f32(h, &w.b2, t->data.data(), H))) return rc;
+    if ((rc = upload_f32(h, s0, &w.b2, t->data.data(), H))) return rc;
     NEED(q + "output.LayerNorm.weight", H);
-    if ((rc = upload_f32(h, &w.ln2g, t->data.data(), H))) return rc;
+    if ((rc = upload_f32(h, s0, &w.ln2g, t->data.data(), H))) return rc;
     NEED(q + "output.LayerNorm.bias", H);
-    if ((rc = upload_f32(h, &w.ln2b, t->data.data(), H))) return rc;
+    if ((rc = upload_f32(h, s0, &w.ln2b, t->data.data(), H))) return rc;
   }
   if (precise && c.layers > 0) {  // fp32 [CLS] tail of the last layer: weights transposed to [k][n]
     const std::string q = P + "encoder.layer." + std::to_string(c.layers - 1) + ".";
@@ -1257,7 +1394,7 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
       if (int r = need(h, key, {N, K}, &tt)) return r;
       std::vector<float> tr((size_t)(N * K));
       for (int64_t n = 0; n < N; ++n) for (int64_t k = 0; k < K; ++k) tr[(size_t)(k * N + n)] = tt->data[(size_t)(n * K + k)] * scale;
-      return upload_f32(h, dst, tr.data(), N * K);
+      return upload_f32(h, s0, dst, tr.data(), N * K);
     };
     if ((rc = up_T(q + "attention.self.query.weight", H, H, 0.125f, &w.wqT32))) return rc;  // 1/sqrt(64) folded like the packed QKV
     if ((rc = up_T(q + "attention.output.dense.weight", H, H, 1.0f, &w.woT32))) return rc;
@@ -1269,54 +1406,50 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
   {
     std::vector<float> tr((size_t)(H * H));
     for (int64_t n = 0; n < H; ++n) for (int64_t k = 0; k < H; ++k) tr[(size_t)(k * H + n)] = t->data[(size_t)(n * H + k)];
-    if ((rc = upload_f32(h, &h->WpT, tr.data(), H * H))) return rc;
+    if ((rc = upload_f32(h, s0, &h->WpT, tr.data(), H * H))) return rc;
   }
   NEED("_bert_pooler.pooler.dense.bias", H);
-  if ((rc = upload_f32(h, &h->bp, t->data.data(), H))) return rc;
+  if ((rc = upload_f32(h, s0, &h->bp, t->data.data(), H))) return rc;
   if (h->P == MV_PROJ) {  // use_header (model_memory.py:69-71); with proj_dim = 768 the model has no _projector_single
     NEED("_projector_single._linear_layers.0.weight", MV_PROJ, H);
     {
       std::vector<float> tr((size_t)(H * MV_PROJ));
       for (int64_t n = 0; n < MV_PROJ; ++n) for (int64_t k = 0; k < H; ++k) tr[(size_t)(k * MV_PROJ + n)] = t->data[(size_t)(n * H + k)];
-      if ((rc = upload_f32(h, &h->WhT, tr.data(), H * MV_PROJ))) return rc;
+      if ((rc = upload_f32(h, s0, &h->WhT, tr.data(), H * MV_PROJ))) return rc;
     }
     NEED("_projector_single._linear_layers.0.bias", MV_PROJ);
-    if ((rc = upload_f32(h, &h->bh, t->data.data(), MV_PROJ))) return rc;
+    if ((rc = upload_f32(h, s0, &h->bh, t->data.data(), MV_PROJ))) return rc;
   }
   NEED("_projector.weight", 2, 3 * (int64_t)h->P);
-  if ((rc = upload_f32(h, &h->Wm, t->data.data(), 2 * 3 * (int64_t)h->P))) return rc;
+  if ((rc = upload_f32(h, s0, &h->Wm, t->data.data(), 2 * 3 * (int64_t)h->P))) return rc;
 #undef NEED
   if (!precise) {  // MV_F16: the lo fp16 plane of the two-plane raw stream (MV_F16X8 keeps the stream's low part in the lo8 plane of x8 + st_lo: gemm.h GemmArgs::out16b)
     for (int wi = 0; wi < h->n_alloc; ++wi) {
-      Work* keep = h->w;
-      h->w = &h->work[wi];
-      rc = dev_alloc(h, &h->work[wi].xlo, h->cap_tokens * MV_HIDDEN);
-      if (rc == MV_OK && hipStreamSynchronize(h->w->stream) != hipSuccess) rc = MV_ERR_HIP;
-      h->w = keep;
+      Work& wk = h->work[wi];
+      rc = dev_alloc(h, wk.stream, &wk.xlo, h->cap_tokens * MV_HIDDEN);
+      if (rc == MV_OK && hipStreamSynchronize(wk.stream) != hipSuccess) rc = MV_ERR_HIP;
       if (rc != MV_OK) return rc;
     }
   }
   if (precise) {  // fp8 planes [lo8 | hi8] of the three activations that are GEMM A operands
     if (h->gemm_tile == 128) return fail(h, MV_ERR_STATE, "MV_F16X8 runs on the persistent GEMM path: MEMVUL_GEMM_TILE=128 excludes it");
     for (int wi = 0; wi < h->n_alloc; ++wi) {
-      Work* keep = h->w;
-      h->w = &h->work[wi];
-      rc = dev_alloc(h, &h->work[wi].x8, h->cap_tokens * 2 * MV_HIDDEN);
-      if (rc == MV_OK) rc = dev_alloc(h, &h->work[wi].ctx8, h->cap_tokens * 2 * MV_HIDDEN);
-      if (rc == MV_OK) rc = dev_alloc(h, &h->work[wi].h8, h->cap_tokens * 2 * MV_INTER);
-      if (rc == MV_OK) rc = dev_alloc(h, &h->work[wi].ch32, (int64_t)round_up(h->cfg.max_batch, 256) * MV_INTER);
-      if (rc == MV_OK) rc = dev_alloc(h, &h->work[wi].cls_lo, 2 * (int64_t)round_up(h->cfg.max_batch, 256) * MV_INTER);
-      if (rc == MV_OK) rc = dev_alloc(h, &h->work[wi].cls_corr, 2 * (int64_t)round_up(h->cfg.max_batch, 256) * MV_INTER);
-      if (rc == MV_OK) rc = dev_alloc(h, &h->work[wi].st_lo, 2 * (int64_t)round_up(h->cfg.max_batch, 256) * MV_HIDDEN);
-      if (rc == MV_OK) rc = dev_alloc(h, &h->work[wi].vlo_sp, (int64_t)h->cfg.max_batch * MV_HEADS * MV_HEAD_DIM * 2);
-      if (rc == MV_OK) rc = dev_alloc(h, &h->work[wi].tile_both, h->cap_tokens / 256 + 1);
+      Work& wk = h->work[wi];
+      rc = dev_alloc(h, wk.stream, &wk.x8, h->cap_tokens * 2 * MV_HIDDEN);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.ctx8, h->cap_tokens * 2 * MV_HIDDEN);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.h8, h->cap_tokens * 2 * MV_INTER);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.ch32, (int64_t)round_up(h->cfg.max_batch, 256) * MV_INTER);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.cls_lo, 2 * (int64_t)round_up(h->cfg.max_batch, 256) * MV_INTER);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.cls_corr, 2 * (int64_t)round_up(h->cfg.max_batch, 256) * MV_INTER);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.st_lo, 2 * (int64_t)round_up(h->cfg.max_batch, 256) * MV_HIDDEN);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.vlo_sp, (int64_t)h->cfg.max_batch * MV_HEADS * MV_HEAD_DIM * 2);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.tile_both, h->cap_tokens / 256 + 1);
       if (h->short_vlo) {  // second fp16 planes of V^T, Q, K: read only by passes of padded length <= 128 in this compute dtype (attention_v2.h VLO)
-        if (rc == MV_OK) rc = dev_alloc(h, &h->work[wi].vt_lo, h->cap_tokens * MV_HIDDEN);
-        if (rc == MV_OK) rc = dev_alloc(h, &h->work[wi].q_lo, h->cap_tokens * MV_HIDDEN);
-        if (rc == MV_OK) rc = dev_alloc(h, &h->work[wi].k_lo, h->cap_tokens * MV_HIDDEN);
+        if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.vt_lo, h->cap_tokens * MV_HIDDEN);
+        if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.q_lo, h->cap_tokens * MV_HIDDEN);
+        if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.k_lo, h->cap_tokens * MV_HIDDEN);
       }
-      if (rc == MV_OK && hipStreamSynchronize(h->w->stream) != hipSuccess) rc = MV_ERR_HIP;
-      h->w = keep;
+      if (rc == MV_OK && hipStreamSynchronize(wk.stream) != hipSuccess) rc = MV_ERR_HIP;
       if (rc != MV_OK) return rc;
     }
   }
@@ -1340,15 +1473,11 @@ int mv_anchor_append(mv_handle* h, const int32_t* ids, const int32_t* lens, int 
   if (h->n_anchors + n > h->cfg.max_anchors) return fail(h, MV_ERR_CAPACITY, "anchor bank capacity (mv_config.max_anchors) exceeded");
   if (int rc = check_ids(h, ids, (int64_t)n * S, "mv_anchor_append")) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const int rows = max_rows_for(h, S);
-  if (rows <= 0) return fail(h, MV_ERR_CAPACITY, "mv_config.max_tokens too small for one anchor of this length");
-  for (int off = 0; off < n; off += rows) {
-    const int nb = (n - off < rows) ? (n - off) : rows;
-    HIPCHK(h, hipMemcpyAsync(h->w->d_ids, ids + (size_t)off * S, (size_t)nb * S * 4, hipMemcpyHostToDevice, h->w->stream));
-    HIPCHK(h, hipMemcpyAsync(h->w->d_lens, lens + off, (size_t)nb * 4, hipMemcpyHostToDevice, h->w->stream));
-    if (int rc = encode_dev(h, h->w->d_ids, h->w->d_lens, pass_min_len(lens + off, nb), nb, S, -1, h->anchors + (size_t)(h->n_anchors + off) * h->P)) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->w->stream));
-  }
+  for (int wi = 1; wi < h->n_alloc; ++wi)  // a ticket in flight on another set still reads the bank this call writes
+    if (h->work[wi].ticket) HIPCHK(h, hipStreamSynchronize(h->work[wi].stream));
+  Job j;
+  j.ids = ids; j.lens = lens; j.u_dev = h->anchors + (size_t)h->n_anchors * h->P;
+  if (int rc = run_in_order(h, lens, n, S, j)) return rc;
   h->n_anchors += n;
   return MV_OK;
 } catch (...) { return on_exception(h); }
@@ -1357,9 +1486,9 @@ int mv_anchor_get(mv_handle* h, float* out) try {
   if (!h || !out) return MV_ERR_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = sync_all(h)) return rc;  // a sweep may still be appending / reading on the other stream
-  h->w = &h->work[0];
-  HIPCHK(h, hipMemcpyAsync(out, h->anchors, (size_t)h->n_anchors * h->P * 4, hipMemcpyDeviceToHost, h->w->stream));
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
+  Work& wk = h->work[0];
+  HIPCHK(h, hipMemcpyAsync(out, h->anchors, (size_t)h->n_anchors * h->P * 4, hipMemcpyDeviceToHost, wk.stream));
+  HIPCHK(h, hipStreamSynchronize(wk.stream));
   return MV_OK;
 } catch (...) { return on_exception(h); }
 
@@ -1368,9 +1497,9 @@ int mv_anchor_set(mv_handle* h, const float* v, int G) try {
   if (G > h->cfg.max_anchors) return fail(h, MV_ERR_CAPACITY, "anchor bank capacity (mv_config.max_anchors) exceeded");
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = sync_all(h)) return rc;  // batches of a resident sweep in flight read the bank
-  h->w = &h->work[0];
-  HIPCHK(h, hipMemcpyAsync(h->anchors, v, (size_t)G * h->P * 4, hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
+  Work& wk = h->work[0];
+  HIPCHK(h, hipMemcpyAsync(h->anchors, v, (size_t)G * h->P * 4, hipMemcpyHostToDevice, wk.stream));
+  HIPCHK(h, hipStreamSynchronize(wk.stream));
   h->n_anchors = G;
   return MV_OK;
 } catch (...) { return on_exception(h); }
@@ -1380,17 +1509,9 @@ int mv_encode(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int 
   if (!ids || !lens || B <= 0 || S <= 0 || S > h->cfg.max_pos) return fail(h, MV_ERR_INVALID, "mv_encode: bad argument");
   if (int rc = check_ids(h, ids, (int64_t)B * S, "mv_encode")) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const int rows = max_rows_for(h, S);
-  if (rows <= 0) return fail(h, MV_ERR_CAPACITY, "mv_config.max_tokens too small for this sequence length");
-  for (int off = 0; off < B; off += rows) {
-    const int nb = (B - off < rows) ? (B - off) : rows;
-    HIPCHK(h, hipMemcpyAsync(h->w->d_ids, ids + (size_t)off * S, (size_t)nb * S * 4, hipMemcpyHostToDevice, h->w->stream));
-    HIPCHK(h, hipMemcpyAsync(h->w->d_lens, lens + off, (size_t)nb * 4, hipMemcpyHostToDevice, h->w->stream));
-    if (int rc = encode_dev(h, h->w->d_ids, h->w->d_lens, pass_min_len(lens + off, nb), nb, S, -1, h->w->u)) return rc;
-    if (embed) HIPCHK(h, hipMemcpyAsync(embed + (size_t)off * h->P, h->w->u, (size_t)nb * h->P * 4, hipMemcpyDeviceToHost, h->w->stream));
-    HIPCHK(h, hipStreamSynchronize(h->w->stream));
-  }
-  return MV_OK;
+  Job j;
+  j.ids = ids; j.lens = lens; j.out.embed = embed;
+  return run_in_order(h, lens, B, S, j);
 } catch (...) { return on_exception(h); }
 
 int mv_forward(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, float* logits, float* probs, float* best,
@@ -1400,106 +1521,15 @@ int mv_forward(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int
   if (h->n_anchors <= 0) return fail(h, MV_ERR_STATE, "anchor bank is empty (call mv_anchor_append / mv_anchor_set first)");
   if (int rc = check_ids(h, ids, (int64_t)B * S, "mv_forward")) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const int rows = max_rows_for(h, S);
-  if (rows <= 0) return fail(h, MV_ERR_CAPACITY, "mv_config.max_tokens too small for this sequence length");
-  const int G = h->n_anchors;
-  for (int off = 0; off < B; off += rows) {
-    const int nb = (B - off < rows) ? (B - off) : rows;
-    HIPCHK(h, hipMemcpyAsync(h->w->d_ids, ids + (size_t)off * S, (size_t)nb * S * 4, hipMemcpyHostToDevice, h->w->stream));
-    HIPCHK(h, hipMemcpyAsync(h->w->d_lens, lens + off, (size_t)nb * 4, hipMemcpyHostToDevice, h->w->stream));
-    if (int rc = encode_dev(h, h->w->d_ids, h->w->d_lens, pass_min_len(lens + off, nb), nb, S, -1, h->w->u)) return rc;
-    // only the outputs the caller asked for leave the kernel (the best anchor always does)
-    if (int rc = match_dev(h, h->w->u, nb, logits ? h->w->logits : nullptr, probs ? h->w->probs : nullptr, nullptr, 1, h->w->best,
-                           h->w->best_idx)) return rc;
-    const size_t bg = (size_t)nb * G;
-    if (logits) HIPCHK(h, hipMemcpyAsync(logits + (size_t)off * G * 2, h->w->logits, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
-    if (probs) HIPCHK(h, hipMemcpyAsync(probs + (size_t)off * G * 2, h->w->probs, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
-    if (best) HIPCHK(h, hipMemcpyAsync(best + (size_t)off * 2, h->w->best, (size_t)nb * 8, hipMemcpyDeviceToHost, h->w->stream));
-    if (best_idx) HIPCHK(h, hipMemcpyAsync(best_idx + off, h->w->best_idx, (size_t)nb * 4, hipMemcpyDeviceToHost, h->w->stream));
-    if (embed) HIPCHK(h, hipMemcpyAsync(embed + (size_t)off * h->P, h->w->u, (size_t)nb * h->P * 4, hipMemcpyDeviceToHost, h->w->stream));
-    HIPCHK(h, hipStreamSynchronize(h->w->stream));
-  }
-  return MV_OK;
+  Job j;
+  j.ids = ids; j.lens = lens; j.match = true;
+  j.out.logits = logits; j.out.probs = probs; j.out.best = best; j.out.idx = best_idx; j.out.embed = embed;
+  return run_in_order(h, lens, B, S, j);
 } catch (...) { return on_exception(h); }
 
 // ---- by length: mv_forward on a pad-to-longest batch of UNSORTED rows (binding.Engine.forward_by_length) ----------------------------------------------------------
-// The rows are ordered (stably) by the padded length of their own token count and cut into groups (a group of fewer than min_tokens padded tokens travels with the
-// next longer one), each group is ONE pass at its own width, all passes back to back on one stream, and the results go back to the caller's row order.
-// ragged_plan: the order and the groups (group g = rows [ends[g - 1], ends[g]) of the length order at widths[g] tokens per row); every group fits one pass.
-static int ragged_plan(mv_handle* h, const int32_t* lens, int B, int S, int min_tokens, std::vector<int>& order, std::vector<int32_t>& ends, std::vector<int32_t>& widths) {
-  std::vector<int> pl(B);
-  order.resize(B);
-  for (int i = 0; i < B; ++i) {
-    if (lens[i] > S) return fail(h, MV_ERR_INVALID, "mv_forward_ragged: a row is longer than S");
-    pl[i] = padded_len(lens[i] < 1 ? 1 : lens[i]);
-    order[i] = i;
-  }
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pl[a] < pl[b]; });
-  int start = 0;
-  for (int end = 1; end <= B; ++end) {
-    if (end < B && pl[order[end]] == pl[order[end - 1]]) continue;  // inside a run of one padded length
-    const int width = pl[order[end - 1]];
-    if (end < B && (int64_t)(end - start) * width < min_tokens) continue;  // too small a pass: these rows travel with the next longer group
-    if (end - start > max_rows_for(h, width < S ? width : S)) return fail(h, MV_ERR_CAPACITY, "mv_forward_ragged: a group exceeds one pass (mv_config.max_tokens)");
-    ends.push_back(end);
-    widths.push_back(width < S ? width : S);
-    start = end;
-  }
-  return MV_OK;
-}
-
-// The rows gathered into st in length order, then enqueued on workspace set `wk` without waiting: upload, one pass per group (its ids read in place from the
-// [B][S] upload: pitch S), download of the outputs st holds.  After a failure it waits for what was enqueued.
-static int ragged_enqueue(mv_handle* h, Work* wk, const int32_t* ids, const int32_t* lens, int S, const std::vector<int>& order, const std::vector<int32_t>& ends,
-                          const std::vector<int32_t>& widths, const RaggedStage& st) {
-  const int B = (int)order.size(), G = h->n_anchors;
-  for (int i = 0; i < B; ++i) {
-    std::memcpy(st.ids + (size_t)i * S, ids + (size_t)order[i] * S, (size_t)S * 4);
-    st.lens[i] = lens[order[i]];
-  }
-  Work* keep = h->w;
-  h->w = wk;
-  auto run = [&]() -> int {
-    HIPCHK(h, hipMemcpyAsync(h->w->d_ids, st.ids, (size_t)B * S * 4, hipMemcpyHostToDevice, h->w->stream));
-    HIPCHK(h, hipMemcpyAsync(h->w->d_lens, st.lens, (size_t)B * 4, hipMemcpyHostToDevice, h->w->stream));
-    int prev = 0;
-    for (size_t g = 0; g < ends.size(); ++g) {
-      const int nb = ends[g] - prev;
-      float* u = h->w->u + (size_t)prev * h->P;
-      if (int rc = encode_dev(h, h->w->d_ids + (size_t)prev * S, h->w->d_lens + prev, pass_min_len(st.lens + prev, nb), nb, widths[g], -1, u, false, S)) return rc;
-      // only the outputs the caller asked for leave the kernel (the best anchor always does)
-      if (int rc = match_dev(h, u, nb, st.logits ? h->w->logits + (size_t)prev * G * 2 : nullptr, st.probs ? h->w->probs + (size_t)prev * G * 2 : nullptr, nullptr, 1,
-                             h->w->best + (size_t)prev * 2, h->w->best_idx + prev)) return rc;
-      prev = ends[g];
-    }
-    const size_t bg = (size_t)B * G;
-    if (st.logits) HIPCHK(h, hipMemcpyAsync(st.logits, h->w->logits, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
-    if (st.probs) HIPCHK(h, hipMemcpyAsync(st.probs, h->w->probs, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
-    HIPCHK(h, hipMemcpyAsync(st.best, h->w->best, (size_t)B * 8, hipMemcpyDeviceToHost, h->w->stream));
-    HIPCHK(h, hipMemcpyAsync(st.idx, h->w->best_idx, (size_t)B * 4, hipMemcpyDeviceToHost, h->w->stream));
-    if (st.embed) HIPCHK(h, hipMemcpyAsync(st.embed, h->w->u, (size_t)B * h->P * 4, hipMemcpyDeviceToHost, h->w->stream));
-    return MV_OK;
-  };
-  const int rc = run();
-  h->w = keep;
-  if (rc != MV_OK) hipStreamSynchronize(wk->stream);
-  return rc;
-}
-
-// Row i of the length order (st) to row order[i] of the caller's arrays: the outputs st holds.
-static void ragged_scatter(const mv_handle* h, const std::vector<int>& order, int G, const RaggedStage& st, float* logits, float* probs, float* best, int32_t* best_idx,
-                           float* embed) {
-  const size_t g2 = (size_t)G * 2, P = (size_t)h->P;
-  for (size_t i = 0; i < order.size(); ++i) {
-    const size_t o = (size_t)order[i];
-    if (st.logits) std::memcpy(logits + o * g2, st.logits + i * g2, g2 * 4);
-    if (st.probs) std::memcpy(probs + o * g2, st.probs + i * g2, g2 * 4);
-    best[o * 2] = st.best[i * 2]; best[o * 2 + 1] = st.best[i * 2 + 1];
-    best_idx[o] = st.idx[i];
-    if (st.embed) std::memcpy(embed + o * P, st.embed + i * P, P * 4);
-  }
-}
-
+// plan_batch orders and groups the rows, gather stages them in that order (each pass at its own width), run_passes runs the passes back to back on one stream,
+// scatter puts the results back in the caller's row order.
 // The whole flow in ONE call on workspace set 0: one release of the caller's interpreter lock per batch (next to two other Python threads every release cost the
 // scoring thread ~10 ms of waiting: profiles/r06_*_e2e_dropin.txt).
 int mv_forward_ragged(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int min_tokens, float* logits, float* probs, float* best,
@@ -1507,83 +1537,87 @@ int mv_forward_ragged(mv_handle* h, const int32_t* ids, const int32_t* lens, int
   if (int rc = check_ready(h)) return rc;
   if (!ids || !lens || B <= 0 || S <= 0 || S > h->cfg.max_pos || !best || !best_idx) return fail(h, MV_ERR_INVALID, "mv_forward_ragged: bad argument");
   if (h->n_anchors <= 0) return fail(h, MV_ERR_STATE, "anchor bank is empty (call mv_anchor_append / mv_anchor_set first)");
-  if (B > h->cfg.max_batch || (int64_t)B * S > h->cap_tokens) return fail(h, MV_ERR_CAPACITY, "mv_forward_ragged: the batch exceeds mv_config.max_batch / max_tokens");
-  std::vector<int> order;
-  std::vector<int32_t> ends, widths;
-  if (int rc = ragged_plan(h, lens, B, S, min_tokens, order, ends, widths)) return rc;
+  Plan& pl = h->plan;
+  if (int rc = plan_batch(h, lens, B, S, min_tokens, true, 0, pl)) return rc;
   if (int rc = check_ids(h, ids, (int64_t)B * S, "mv_forward_ragged")) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   const int G = h->n_anchors;
-  auto& v = h->ragged;
-  v.ids.resize((size_t)B * S);
+  auto& v = h->stage;
+  v.ids.resize((size_t)pl.tokens);
   v.lens.resize(B);
   if (logits) v.logits.resize((size_t)B * G * 2);
   if (probs) v.probs.resize((size_t)B * G * 2);
   v.best.resize((size_t)B * 2);
   v.idx.resize(B);
   if (embed) v.embed.resize((size_t)B * h->P);
-  const RaggedStage st{v.ids.data(), v.lens.data(), v.idx.data(), logits ? v.logits.data() : nullptr, probs ? v.probs.data() : nullptr, v.best.data(),
-                       embed ? v.embed.data() : nullptr};
-  if (int rc = ragged_enqueue(h, &h->work[0], ids, lens, S, order, ends, widths, st)) return rc;
+  gather(pl, ids, lens, S, v.ids.data(), v.lens.data());
+  Job j;
+  j.ids = v.ids.data(); j.lens = v.lens.data(); j.match = true;
+  j.out = Stage{nullptr, nullptr, v.idx.data(), logits ? v.logits.data() : nullptr, probs ? v.probs.data() : nullptr, v.best.data(), embed ? v.embed.data() : nullptr};
+  if (int rc = run_passes(h, h->work[0], pl, 0, pl.passes.size(), j)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->work[0].stream));
-  ragged_scatter(h, order, G, st, logits, probs, best, best_idx, embed);
+  scatter(h, pl.order, G, j.out, logits, probs, best, best_idx, embed);
   return MV_OK;
 } catch (...) { return on_exception(h); }
 
-// mv_forward_ragged in two halves, so that the caller can hand over batch k + 1 BEFORE it collects batch k: `begin` enqueues the batch on the next workspace set
-// into its pinned staging and returns a ticket without waiting; `end` waits for that set's stream and scatters the results.  At most one batch per workspace set
-// (MEMVUL_STREAMS: 2) is in flight; tickets are collected in the order they were issued.  The GPU then never waits for the caller's Python between two batches
-// (predict_memory.evaluate).
+// mv_forward_ragged in two halves, so that the caller can hand over batch k + 1 BEFORE it collects batch k: `begin` enqueues the batch on a workspace set without
+// a ticket, into that set's pinned staging, and returns a ticket (the set) without waiting; `end` waits for that set's stream and scatters the results.  At most
+// one batch per workspace set (MEMVUL_STREAMS: 2) is in flight; tickets are collected in the order they were issued.  The GPU then never waits for the caller's
+// Python between two batches (predict_memory.evaluate).
 int mv_forward_ragged_begin(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int min_tokens, int want_logits, int want_probs, int want_embed,
                             int* ticket) try {
   if (int rc = check_ready(h)) return rc;
   if (!ids || !lens || !ticket || B <= 0 || S <= 0 || S > h->cfg.max_pos) return fail(h, MV_ERR_INVALID, "mv_forward_ragged_begin: bad argument");
   if (h->n_anchors <= 0) return fail(h, MV_ERR_STATE, "anchor bank is empty (call mv_anchor_append / mv_anchor_set first)");
-  if (B > h->cfg.max_batch || (int64_t)B * S > h->cap_tokens) return fail(h, MV_ERR_CAPACITY, "mv_forward_ragged_begin: the batch exceeds mv_config.max_batch / max_tokens");
-  const int slot = h->rnext % (h->n_alloc < 2 ? 1 : 2);
-  auto& rs = h->rslot[slot];
-  if (rs.busy) return fail(h, MV_ERR_CAPACITY, "mv_forward_ragged_begin: every workspace set has a batch in flight (score this one with mv_forward_ragged)");
-  std::vector<int32_t> ends, widths;
-  if (int rc = ragged_plan(h, lens, B, S, min_tokens, rs.order, ends, widths)) return rc;
+  if (B > h->cfg.max_batch) return fail(h, MV_ERR_CAPACITY, "mv_forward_ragged_begin: the batch exceeds mv_config.max_batch");
+  int set = 0;
+  while (set < h->n_alloc && h->work[set].ticket) ++set;
+  if (set == h->n_alloc) return fail(h, MV_ERR_CAPACITY, "mv_forward_ragged_begin: every workspace set has a batch in flight (score this one with mv_forward_ragged)");
+  Work& wk = h->work[set];
+  if (int rc = plan_batch(h, lens, B, S, min_tokens, true, 0, wk.plan)) return rc;
   if (int rc = check_ids(h, ids, (int64_t)B * S, "mv_forward_ragged_begin")) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  if (!rs.pin.ids) {  // pinned staging of this slot, once
+  if (!wk.pin.best) {  // pinned staging of this set, once: [max_batch][max_pos], [max_batch] x 2, [max_batch][max_anchors][2] x 2, [max_batch][2], [max_batch][P]
     const size_t mb = (size_t)h->cfg.max_batch, bg2 = mb * (size_t)h->cfg.max_anchors * 2;
+    Stage s;
     auto pin = [&](void** p, size_t bytes) -> int {
       if (hipHostMalloc(p, bytes, hipHostMallocDefault) != hipSuccess) return fail(h, MV_ERR_NOMEM, "hipHostMalloc failed (mv_forward_ragged_begin)");
       h->pinned.push_back(*p);
       return MV_OK;
     };
-    int rc = pin((void**)&rs.pin.ids, (size_t)h->cap_tokens * 4);
-    if (!rc) rc = pin((void**)&rs.pin.lens, mb * 4);
-    if (!rc) rc = pin((void**)&rs.pin.idx, mb * 4);
-    if (!rc) rc = pin((void**)&rs.pin.logits, bg2 * 4);
-    if (!rc) rc = pin((void**)&rs.pin.probs, bg2 * 4);
-    if (!rc) rc = pin((void**)&rs.pin.best, mb * 2 * 4);
-    if (!rc) rc = pin((void**)&rs.pin.embed, mb * (size_t)h->P * 4);
-    if (rc) { rs.pin.ids = nullptr; return rc; }
+    int rc = pin((void**)&s.ids, mb * (size_t)h->cfg.max_pos * 4);
+    if (!rc) rc = pin((void**)&s.lens, mb * 4);
+    if (!rc) rc = pin((void**)&s.idx, mb * 4);
+    if (!rc) rc = pin((void**)&s.logits, bg2 * 4);
+    if (!rc) rc = pin((void**)&s.probs, bg2 * 4);
+    if (!rc) rc = pin((void**)&s.best, mb * 2 * 4);
+    if (!rc) rc = pin((void**)&s.embed, mb * (size_t)h->P * 4);
+    if (rc) return rc;
+    wk.pin = s;
   }
-  RaggedStage st = rs.pin;
+  Stage st = wk.pin;
   if (!want_logits) st.logits = nullptr;
   if (!want_probs) st.probs = nullptr;
   if (!want_embed) st.embed = nullptr;
-  if (int rc = ragged_enqueue(h, &h->work[slot], ids, lens, S, rs.order, ends, widths, st)) return rc;
-  rs.busy = true; rs.G = h->n_anchors; rs.st = st;
-  *ticket = slot;
-  h->rnext += 1;
+  gather(wk.plan, ids, lens, S, st.ids, st.lens);
+  Job j;
+  j.ids = st.ids; j.lens = st.lens; j.match = true; j.out = st;
+  if (int rc = run_passes(h, wk, wk.plan, 0, wk.plan.passes.size(), j)) return rc;
+  wk.ticket = true; wk.G = h->n_anchors; wk.st = st;
+  *ticket = set;
   return MV_OK;
 } catch (...) { return on_exception(h); }
 
 int mv_forward_ragged_end(mv_handle* h, int ticket, float* logits, float* probs, float* best, int32_t* best_idx, float* embed) try {
-  if (!h || ticket < 0 || ticket > 1 || !h->rslot[ticket].busy) return fail(h, MV_ERR_STATE, "mv_forward_ragged_end: no batch in flight under this ticket");
-  auto& rs = h->rslot[ticket];
+  if (!h || ticket < 0 || ticket > 1 || !h->work[ticket].ticket) return fail(h, MV_ERR_STATE, "mv_forward_ragged_end: no batch in flight under this ticket");
+  Work& wk = h->work[ticket];
   HIPCHK(h, hipSetDevice(h->device));
-  const hipError_t e = hipStreamSynchronize(h->work[ticket].stream);
-  rs.busy = false;
+  const hipError_t e = hipStreamSynchronize(wk.stream);
+  wk.ticket = false;
   if (e != hipSuccess) return fail(h, MV_ERR_HIP, std::string("mv_forward_ragged_end: ") + hipGetErrorString(e));
-  if (!best || !best_idx || (rs.st.logits && !logits) || (rs.st.probs && !probs) || (rs.st.embed && !embed))
+  if (!best || !best_idx || (wk.st.logits && !logits) || (wk.st.probs && !probs) || (wk.st.embed && !embed))
     return fail(h, MV_ERR_INVALID, "mv_forward_ragged_end: an output the batch was started with is missing");
-  ragged_scatter(h, rs.order, rs.G, rs.st, logits, probs, best, best_idx, embed);
+  scatter(h, wk.plan.order, wk.G, wk.st, logits, probs, best, best_idx, embed);
   return MV_OK;
 } catch (...) { return on_exception(h); }
 
@@ -1592,16 +1626,17 @@ int mv_match(mv_handle* h, const float* u, int B, float* logits, float* probs, f
   if (!u || B <= 0) return fail(h, MV_ERR_INVALID, "mv_match: bad argument");
   if (B > h->cfg.max_batch) return fail(h, MV_ERR_CAPACITY, "B exceeds mv_config.max_batch");
   HIPCHK(h, hipSetDevice(h->device));
+  Work& wk = h->work[0];
   const int G = h->n_anchors;
-  HIPCHK(h, hipMemcpyAsync(h->w->u_in, u, (size_t)B * h->P * 4, hipMemcpyHostToDevice, h->w->stream));
-  if (int rc = match_dev(h, h->w->u_in, B, logits ? h->w->logits : nullptr, probs ? h->w->probs : nullptr, nullptr, 1, h->w->best,
-                         h->w->best_idx)) return rc;
+  HIPCHK(h, hipMemcpyAsync(wk.u_in, u, (size_t)B * h->P * 4, hipMemcpyHostToDevice, wk.stream));
+  if (int rc = match_dev(h, wk, wk.u_in, B, logits ? wk.logits : nullptr, probs ? wk.probs : nullptr, nullptr, 1, wk.best,
+                         wk.best_idx)) return rc;
   const size_t bg = (size_t)B * G;
-  if (logits) HIPCHK(h, hipMemcpyAsync(logits, h->w->logits, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
-  if (probs) HIPCHK(h, hipMemcpyAsync(probs, h->w->probs, bg * 8, hipMemcpyDeviceToHost, h->w->stream));
-  if (best) HIPCHK(h, hipMemcpyAsync(best, h->w->best, (size_t)B * 8, hipMemcpyDeviceToHost, h->w->stream));
-  if (best_idx) HIPCHK(h, hipMemcpyAsync(best_idx, h->w->best_idx, (size_t)B * 4, hipMemcpyDeviceToHost, h->w->stream));
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
+  if (logits) HIPCHK(h, hipMemcpyAsync(logits, wk.logits, bg * 8, hipMemcpyDeviceToHost, wk.stream));
+  if (probs) HIPCHK(h, hipMemcpyAsync(probs, wk.probs, bg * 8, hipMemcpyDeviceToHost, wk.stream));
+  if (best) HIPCHK(h, hipMemcpyAsync(best, wk.best, (size_t)B * 8, hipMemcpyDeviceToHost, wk.stream));
+  if (best_idx) HIPCHK(h, hipMemcpyAsync(best_idx, wk.best_idx, (size_t)B * 4, hipMemcpyDeviceToHost, wk.stream));
+  HIPCHK(h, hipStreamSynchronize(wk.stream));
   return MV_OK;
 } catch (...) { return on_exception(h); }
 
@@ -1611,12 +1646,13 @@ int mv_topk(mv_handle* h, const float* u, int B, int k, float* topk_p, int32_t* 
   if (B > h->cfg.max_batch) return fail(h, MV_ERR_CAPACITY, "B exceeds mv_config.max_batch");
   if (k > h->n_anchors) return fail(h, MV_ERR_INVALID, "k exceeds the number of anchors");
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpyAsync(h->w->u_in, u, (size_t)B * h->P * 4, hipMemcpyHostToDevice, h->w->stream));
+  Work& wk = h->work[0];
+  HIPCHK(h, hipMemcpyAsync(wk.u_in, u, (size_t)B * h->P * 4, hipMemcpyHostToDevice, wk.stream));
   // one fused pass: P(same) [B, G] never reaches HBM, only 8 B k bytes of results do
-  if (int rc = match_dev(h, h->w->u_in, B, nullptr, nullptr, nullptr, k, nullptr, nullptr, h->w->topk_p, h->w->topk_idx)) return rc;
-  HIPCHK(h, hipMemcpyAsync(topk_p, h->w->topk_p, (size_t)B * k * 4, hipMemcpyDeviceToHost, h->w->stream));
-  HIPCHK(h, hipMemcpyAsync(topk_idx, h->w->topk_idx, (size_t)B * k * 4, hipMemcpyDeviceToHost, h->w->stream));
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
+  if (int rc = match_dev(h, wk, wk.u_in, B, nullptr, nullptr, nullptr, k, nullptr, nullptr, wk.topk_p, wk.topk_idx)) return rc;
+  HIPCHK(h, hipMemcpyAsync(topk_p, wk.topk_p, (size_t)B * k * 4, hipMemcpyDeviceToHost, wk.stream));
+  HIPCHK(h, hipMemcpyAsync(topk_idx, wk.topk_idx, (size_t)B * k * 4, hipMemcpyDeviceToHost, wk.stream));
+  HIPCHK(h, hipStreamSynchronize(wk.stream));
   return MV_OK;
 } catch (...) { return on_exception(h); }
 
@@ -1626,17 +1662,18 @@ int mv_corpus_upload(mv_handle* h, const int32_t* ids, const int32_t* lens, int6
   if (!ids || !lens || n <= 0 || S <= 0 || S > h->cfg.max_pos) return fail(h, MV_ERR_INVALID, "mv_corpus_upload: bad argument");
   if (int rc = check_ids(h, ids, n * S, "mv_corpus_upload")) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
+  const hipStream_t s0 = h->work[0].stream;
+  HIPCHK(h, hipStreamSynchronize(s0));
   dev_free(h, h->c_ids); dev_free(h, h->c_lens); dev_free(h, h->c_best); dev_free(h, h->c_idx); dev_free(h, h->c_psame);
   h->c_ids = nullptr; h->c_lens = nullptr; h->c_best = nullptr; h->c_idx = nullptr; h->c_psame = nullptr;
   h->c_psame_rows = 0;
-  if (int rc = dev_alloc(h, &h->c_ids, n * S, false)) return rc;
-  if (int rc = dev_alloc(h, &h->c_lens, n, false)) return rc;
-  if (int rc = dev_alloc(h, &h->c_best, n * 2)) return rc;
-  if (int rc = dev_alloc(h, &h->c_idx, n)) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->c_ids, ids, (size_t)n * S * 4, hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipMemcpyAsync(h->c_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
+  if (int rc = dev_alloc(h, s0, &h->c_ids, n * S, false)) return rc;
+  if (int rc = dev_alloc(h, s0, &h->c_lens, n, false)) return rc;
+  if (int rc = dev_alloc(h, s0, &h->c_best, n * 2)) return rc;
+  if (int rc = dev_alloc(h, s0, &h->c_idx, n)) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->c_ids, ids, (size_t)n * S * 4, hipMemcpyHostToDevice, s0));
+  HIPCHK(h, hipMemcpyAsync(h->c_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, s0));
+  HIPCHK(h, hipStreamSynchronize(s0));
   h->c_lens_host.assign(lens, lens + n);
   h->c_n = n;
   h->c_S = S;
@@ -1651,43 +1688,35 @@ int mv_corpus_run_len(mv_handle* h, int64_t first, int64_t count, int batch, int
   if (!h) return MV_ERR_INVALID;
   if (!h->finalized) return fail(h, MV_ERR_STATE, "weights not finalized (mv_finalize_weights)");
   if (!h->c_ids) return fail(h, MV_ERR_STATE, "no resident corpus (mv_corpus_upload)");
-  if (first < 0 || count <= 0 || first + count > h->c_n || batch <= 0) return fail(h, MV_ERR_INVALID, "mv_corpus_run: bad range");
+  if (first < 0 || count <= 0 || first + count > h->c_n || count > INT32_MAX || batch <= 0) return fail(h, MV_ERR_INVALID, "mv_corpus_run: bad range");
   if (h->n_anchors <= 0) return fail(h, MV_ERR_STATE, "anchor bank is empty");
   HIPCHK(h, hipSetDevice(h->device));
-  h->w = &h->work[0];
   if (s_eff < 0 || s_eff > h->c_S) return fail(h, MV_ERR_INVALID, "mv_corpus_run_len: s_eff must be in [0, S of the resident corpus]");
-  const int S_use = s_eff > 0 ? s_eff : h->c_S;  // tokens per row actually processed (rows longer than this must not be in the range)
-  const int rows = max_rows_for(h, S_use);
-  if (rows <= 0) return fail(h, MV_ERR_CAPACITY, "mv_config.max_tokens too small for one row of this length");
-  // a batch larger than one pass holds is walked in passes of `rows` (as mv_forward / mv_encode do): a row's result
-  // does not depend on the batch it travels in (bit-identical, tests/test_gpu_parity.py::test_full_batch_properties)
-  if (batch > rows) batch = rows;
+  // tokens per row actually processed (rows longer than this must not be in the range); a batch larger than one pass holds is walked in passes (as
+  // mv_forward / mv_encode do): a row's result does not depend on the batch it travels in (bit-identical, tests/test_gpu_parity.py::test_full_batch_properties)
+  const int S_use = s_eff > 0 ? s_eff : h->c_S;
+  Plan& pl = h->plan;
+  if (int rc = plan_batch(h, h->c_lens_host.data() + first, (int)count, S_use, 0, false, batch, pl)) return rc;
   const int G = h->n_anchors;
   if (keep_probs && (h->c_psame_rows != h->c_n || h->c_G != G)) {
     if (int rc = sync_all(h)) return rc;
     dev_free(h, h->c_psame);
     h->c_psame = nullptr;
-    if (int rc = dev_alloc(h, &h->c_psame, h->c_n * G)) return rc;
+    if (int rc = dev_alloc(h, h->work[0].stream, &h->c_psame, h->c_n * G)) return rc;
     h->c_psame_rows = h->c_n;
     h->c_G = G;
   }
   // consecutive batches (also across calls) alternate between the two workspace sets / streams: two batches are in
   // flight at once; their results go to disjoint slices of the resident arrays
-  int rc = MV_OK;
-  for (int64_t off = first; off < first + count && rc == MV_OK; off += batch) {
-    const int nb = (int)((first + count - off < batch) ? (first + count - off) : batch);
-    h->w = &h->work[h->rr];
-    if (h->n_streams == 2) {
-      if (h->rr == 1) h->dual_pending = true;
-      h->rr ^= 1;
-    }
-    rc = encode_dev(h, h->c_ids + (size_t)off * h->c_S, h->c_lens + off, pass_min_len(h->c_lens_host.data() + off, nb), nb, S_use, -1, h->w->u, false, h->c_S);
-    if (rc != MV_OK) break;
-    float* ps = keep_probs ? h->c_psame + (size_t)off * G : nullptr;  // P(same) [nb, G] only when the caller keeps it
-    rc = match_dev(h, h->w->u, nb, nullptr, nullptr, ps, 1, h->c_best + (size_t)off * 2, h->c_idx + off);
+  Job j;
+  j.c_row = first; j.keep_psame = keep_probs != 0;
+  for (size_t i = 0; i < pl.passes.size(); ++i) {
+    Work& wk = h->work[h->rr];
+    wk.sweep = true;
+    if (h->n_streams == 2) h->rr ^= 1;
+    if (int rc = run_passes(h, wk, pl, i, i + 1, j)) return rc;
   }
-  h->w = &h->work[0];
-  return rc;
+  return MV_OK;
 } catch (...) { return on_exception(h); }
 
 int mv_corpus_results(mv_handle* h, int64_t first, int64_t count, float* best, int32_t* best_idx, float* p_same) try {
@@ -1695,15 +1724,15 @@ int mv_corpus_results(mv_handle* h, int64_t first, int64_t count, float* best, i
   if (!h->c_ids) return fail(h, MV_ERR_STATE, "no resident corpus (mv_corpus_upload)");
   if (first < 0 || count <= 0 || first + count > h->c_n) return fail(h, MV_ERR_INVALID, "mv_corpus_results: bad range");
   HIPCHK(h, hipSetDevice(h->device));
-  h->w = &h->work[0];
   if (int rc = sync_all(h)) return rc;
-  if (best) HIPCHK(h, hipMemcpyAsync(best, h->c_best + (size_t)first * 2, (size_t)count * 8, hipMemcpyDeviceToHost, h->w->stream));
-  if (best_idx) HIPCHK(h, hipMemcpyAsync(best_idx, h->c_idx + first, (size_t)count * 4, hipMemcpyDeviceToHost, h->w->stream));
+  const hipStream_t s0 = h->work[0].stream;
+  if (best) HIPCHK(h, hipMemcpyAsync(best, h->c_best + (size_t)first * 2, (size_t)count * 8, hipMemcpyDeviceToHost, s0));
+  if (best_idx) HIPCHK(h, hipMemcpyAsync(best_idx, h->c_idx + first, (size_t)count * 4, hipMemcpyDeviceToHost, s0));
   if (p_same) {
     if (!h->c_psame) return fail(h, MV_ERR_STATE, "P(same) was not kept (mv_corpus_run keep_probs=0)");
-    HIPCHK(h, hipMemcpyAsync(p_same, h->c_psame + (size_t)first * h->c_G, (size_t)count * h->c_G * 4, hipMemcpyDeviceToHost, h->w->stream));
+    HIPCHK(h, hipMemcpyAsync(p_same, h->c_psame + (size_t)first * h->c_G, (size_t)count * h->c_G * 4, hipMemcpyDeviceToHost, s0));
   }
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
+  HIPCHK(h, hipStreamSynchronize(s0));
   return MV_OK;
 } catch (...) { return on_exception(h); }
 
@@ -1892,32 +1921,31 @@ int mv_debug_encode(mv_handle* h, const int32_t* ids, const int32_t* lens, int B
   if (B > max_rows_for(h, S)) return fail(h, MV_ERR_CAPACITY, "mv_debug_encode: batch too large for one pass");
   if (int rc = check_ids(h, ids, (int64_t)B * S, "mv_debug_encode")) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpyAsync(h->w->d_ids, ids, (size_t)B * S * 4, hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipMemcpyAsync(h->w->d_lens, lens, (size_t)B * 4, hipMemcpyHostToDevice, h->w->stream));
-  if (int rc = encode_dev(h, h->w->d_ids, h->w->d_lens, pass_min_len(lens, B), B, S, n_layers < 0 ? h->cfg.layers : n_layers, h->w->u, /*full=*/true)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
-  return MV_OK;
+  Job j;  // (on workspace set 0: what mv_debug_read reads)
+  j.ids = ids; j.lens = lens; j.n_layers = n_layers < 0 ? h->cfg.layers : n_layers; j.full = true;
+  return run_in_order(h, lens, B, S, j);
 } catch (...) { return on_exception(h); }
 
 int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes) try {
   if (!h || !dst || bytes <= 0) return MV_ERR_INVALID;
+  Work& wk = h->work[0];  // (mv_debug_encode's set)
   const int64_t T = (int64_t)h->dbg_B * h->dbg_Sp;
   const void* src = nullptr;
   int64_t avail = 0;
   switch (buffer) {
-    case 0: src = h->w->xres; avail = T * MV_HIDDEN * 4; break;
-    case 1: src = h->w->x16; avail = T * MV_HIDDEN * 2; break;
-    case 2: src = h->w->q; avail = T * MV_HIDDEN * 2; break;
-    case 3: src = h->w->k; avail = T * MV_HIDDEN * 2; break;
-    case 4: src = h->w->vt; avail = T * MV_HIDDEN * 2; break;
-    case 5: src = h->w->ctx; avail = T * MV_HIDDEN * 2; break;
-    case 6: src = h->w->h16; avail = T * MV_INTER * 2; break;
-    case 7: src = h->w->u; avail = (int64_t)h->dbg_B * h->P * 4; break;
+    case 0: src = wk.xres; avail = T * MV_HIDDEN * 4; break;
+    case 1: src = wk.x16; avail = T * MV_HIDDEN * 2; break;
+    case 2: src = wk.q; avail = T * MV_HIDDEN * 2; break;
+    case 3: src = wk.k; avail = T * MV_HIDDEN * 2; break;
+    case 4: src = wk.vt; avail = T * MV_HIDDEN * 2; break;
+    case 5: src = wk.ctx; avail = T * MV_HIDDEN * 2; break;
+    case 6: src = wk.h16; avail = T * MV_INTER * 2; break;
+    case 7: src = wk.u; avail = (int64_t)h->dbg_B * h->P * 4; break;
     default: return fail(h, MV_ERR_INVALID, "mv_debug_read: unknown buffer");
   }
   if (bytes > avail) return fail(h, MV_ERR_INVALID, "mv_debug_read: more bytes requested than the buffer holds");
-  HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, h->w->stream));
-  HIPCHK(h, hipStreamSynchronize(h->w->stream));
+  HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, wk.stream));
+  HIPCHK(h, hipStreamSynchronize(wk.stream));
   return MV_OK;
 } catch (...) { return on_exception(h); }
 
@@ -1927,30 +1955,31 @@ int mv_test_gemm(mv_handle* h, int variant, int M, int N, int K, const uint16_t*
   if (variant != 0 && variant != 19) return fail(h, MV_ERR_INVALID, "mv_test_gemm: variant 0 (128^2 tile) or 19 (64^2 ring)");
   if (variant == 0 && (M % 128 || N % 128 || K % 64)) return fail(h, MV_ERR_INVALID, "mv_test_gemm: M,N % 128 and K % 64 required");
   HIPCHK(h, hipSetDevice(h->device));
+  const hipStream_t s0 = h->work[0].stream;
   half_t *dA = nullptr, *dW = nullptr;
   float *dB = nullptr, *dC = nullptr;
   int rc;
-  if ((rc = dev_alloc(h, &dA, (int64_t)M * K, false))) return rc;
-  if ((rc = dev_alloc(h, &dW, (int64_t)N * K, false))) return rc;
-  if ((rc = dev_alloc(h, &dB, N))) return rc;
-  if ((rc = dev_alloc(h, &dC, (int64_t)M * N))) return rc;
-  HIPCHK(h, hipMemcpyAsync(dA, A, (size_t)M * K * 2, hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, h->w->stream));
-  if (bias) HIPCHK(h, hipMemcpyAsync(dB, bias, (size_t)N * 4, hipMemcpyHostToDevice, h->w->stream));
+  if ((rc = dev_alloc(h, s0, &dA, (int64_t)M * K, false))) return rc;
+  if ((rc = dev_alloc(h, s0, &dW, (int64_t)N * K, false))) return rc;
+  if ((rc = dev_alloc(h, s0, &dB, N))) return rc;
+  if ((rc = dev_alloc(h, s0, &dC, (int64_t)M * N))) return rc;
+  HIPCHK(h, hipMemcpyAsync(dA, A, (size_t)M * K * 2, hipMemcpyHostToDevice, s0));
+  HIPCHK(h, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s0));
+  if (bias) HIPCHK(h, hipMemcpyAsync(dB, bias, (size_t)N * 4, hipMemcpyHostToDevice, s0));
   GemmArgs g{};
   g.A = dA; g.W = dW; g.bias = dB; g.M = M; g.Mreal = M; g.N = N; g.K = K; g.outf = dC; g.S = 64;
   if (iters < 1) iters = 1;
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
   hipEventCreate(&e1);
-  auto run = [&]() -> int { return variant == 0 ? launch_gemm128<EPI_F32>(h, KC_TEST_GEMM, g) : launch_ring64<EPI_F32>(h, KC_TEST_GEMM, g); };
+  auto run = [&]() -> int { return variant == 0 ? launch_gemm128<EPI_F32>(h, s0, KC_TEST_GEMM, g) : launch_ring64<EPI_F32>(h, s0, KC_TEST_GEMM, g); };
   rc = run();  // warm-up / correctness launch
   if (rc == MV_OK) {
-    hipEventRecord(e0, h->w->stream);
+    hipEventRecord(e0, s0);
     for (int i = 0; i < iters && rc == MV_OK; ++i) rc = run();
-    hipEventRecord(e1, h->w->stream);
+    hipEventRecord(e1, s0);
   }
-  hipError_t se = hipStreamSynchronize(h->w->stream);
+  hipError_t se = hipStreamSynchronize(s0);
   float t = 0.f;
   hipEventElapsedTime(&t, e0, e1);
   hipEventDestroy(e0);
@@ -1976,6 +2005,7 @@ int mv_test_gemm_pp(mv_handle* h, int x8, int M, int N, int K, const float* A, c
     return fail(h, MV_ERR_INVALID, "mv_test_gemm_pp: M,N % 256, K % 128, K >= 256, N <= 3072 required");
   if (x8 == 2 && K % 256) return fail(h, MV_ERR_INVALID, "mv_test_gemm_pp: the weight-side-only sweep walks K / 128 K-tiles in pairs: K % 256 required");
   HIPCHK(h, hipSetDevice(h->device));
+  const hipStream_t s0 = h->work[0].stream;
   std::vector<uint16_t> a16((size_t)M * K), w16((size_t)N * K);
   for (size_t i = 0; i < a16.size(); ++i) a16[i] = f32_to_f16_bits(A[i]);
   for (size_t i = 0; i < w16.size(); ++i) w16[i] = f32_to_f16_bits(W[i]);
@@ -1998,23 +2028,23 @@ int mv_test_gemm_pp(mv_handle* h, int x8, int M, int N, int K, const float* A, c
   uint8_t *dA8 = nullptr, *dW8 = nullptr, *dO8 = nullptr;
   float *dB = nullptr, *dS = nullptr;
   int rc;
-  if ((rc = dev_alloc(h, &dA, (int64_t)M * K, false))) return rc;
-  if ((rc = dev_alloc(h, &dW, (int64_t)N * K, false))) return rc;
-  if ((rc = dev_alloc(h, &dO, (int64_t)M * N))) return rc;
-  if ((rc = dev_alloc(h, &dB, N, false))) return rc;
-  if ((rc = dev_alloc(h, &dS, (int64_t)M * 6, false))) return rc;
-  HIPCHK(h, hipMemcpyAsync(dA, a16.data(), a16.size() * 2, hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipMemcpyAsync(dW, w16.data(), w16.size() * 2, hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipMemcpyAsync(dB, bias, (size_t)N * 4, hipMemcpyHostToDevice, h->w->stream));
-  HIPCHK(h, hipMemcpyAsync(dS, st.data(), st.size() * 4, hipMemcpyHostToDevice, h->w->stream));
+  if ((rc = dev_alloc(h, s0, &dA, (int64_t)M * K, false))) return rc;
+  if ((rc = dev_alloc(h, s0, &dW, (int64_t)N * K, false))) return rc;
+  if ((rc = dev_alloc(h, s0, &dO, (int64_t)M * N))) return rc;
+  if ((rc = dev_alloc(h, s0, &dB, N, false))) return rc;
+  if ((rc = dev_alloc(h, s0, &dS, (int64_t)M * 6, false))) return rc;
+  HIPCHK(h, hipMemcpyAsync(dA, a16.data(), a16.size() * 2, hipMemcpyHostToDevice, s0));
+  HIPCHK(h, hipMemcpyAsync(dW, w16.data(), w16.size() * 2, hipMemcpyHostToDevice, s0));
+  HIPCHK(h, hipMemcpyAsync(dB, bias, (size_t)N * 4, hipMemcpyHostToDevice, s0));
+  HIPCHK(h, hipMemcpyAsync(dS, st.data(), st.size() * 4, hipMemcpyHostToDevice, s0));
   GemmArgs g{};
   g.A = dA; g.W = dW; g.bias = dB; g.M = M; g.Mreal = M; g.N = N; g.K = K; g.out16 = dO; g.S = 64; g.lnstats = dS; g.ln_eps = 0.f;
   if (x8) {
-    if ((rc = dev_alloc(h, &dA8, (int64_t)a8.size(), false))) return rc;
-    if ((rc = dev_alloc(h, &dW8, (int64_t)w8.size(), false))) return rc;
-    if ((rc = dev_alloc(h, &dO8, (int64_t)M * 2 * N))) return rc;
-    HIPCHK(h, hipMemcpyAsync(dA8, a8.data(), a8.size(), hipMemcpyHostToDevice, h->w->stream));
-    HIPCHK(h, hipMemcpyAsync(dW8, w8.data(), w8.size(), hipMemcpyHostToDevice, h->w->stream));
+    if ((rc = dev_alloc(h, s0, &dA8, (int64_t)a8.size(), false))) return rc;
+    if ((rc = dev_alloc(h, s0, &dW8, (int64_t)w8.size(), false))) return rc;
+    if ((rc = dev_alloc(h, s0, &dO8, (int64_t)M * 2 * N))) return rc;
+    HIPCHK(h, hipMemcpyAsync(dA8, a8.data(), a8.size(), hipMemcpyHostToDevice, s0));
+    HIPCHK(h, hipMemcpyAsync(dW8, w8.data(), w8.size(), hipMemcpyHostToDevice, s0));
     g.A8 = dA8; g.W8 = dW8; g.out8 = dO8; g.x8_scale = scale_word;
     g.x8_terms = (x8 == 2) ? 1 : 2;  // x8 = 2: the weight-side term only (the QKV projection's form)
   }
@@ -2022,13 +2052,13 @@ int mv_test_gemm_pp(mv_handle* h, int x8, int M, int N, int K, const float* A, c
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
   hipEventCreate(&e1);
-  rc = launch_pp<PP_GELU>(h, KC_TEST_GEMM, g);
+  rc = launch_pp<PP_GELU>(h, s0, KC_TEST_GEMM, g);
   if (rc == MV_OK) {
-    hipEventRecord(e0, h->w->stream);
-    for (int i = 0; i < iters && rc == MV_OK; ++i) rc = launch_pp<PP_GELU>(h, KC_TEST_GEMM, g);
-    hipEventRecord(e1, h->w->stream);
+    hipEventRecord(e0, s0);
+    for (int i = 0; i < iters && rc == MV_OK; ++i) rc = launch_pp<PP_GELU>(h, s0, KC_TEST_GEMM, g);
+    hipEventRecord(e1, s0);
   }
-  hipError_t se = hipStreamSynchronize(h->w->stream);
+  hipError_t se = hipStreamSynchronize(s0);
   float t = 0.f;
   hipEventElapsedTime(&t, e0, e1);
   hipEventDestroy(e0);

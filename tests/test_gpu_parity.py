@@ -652,28 +652,80 @@ def test_length_bucketed_sweep_matches_padded_sweep(gu, compute):
     eng.anchor_reset()
 
 
+def _by_length_reference(eng, ids, lens, min_tokens, max_tokens, max_batch, **want):
+    """The by-length rule restated test-side: rows ordered (stably) by the padded length of their own token count, a run of one padded length merged into
+    the next longer one while it holds fewer than min_tokens padded tokens, one ``forward`` per group at the group's width.  Returns the results in row
+    order, the groups (start, end, width) of that order and the encoder passes the groups take (``forward``: passes of max_rows_for(width) rows)."""
+    B, S = ids.shape
+    pl = np.where(lens <= 256, (np.maximum(lens, 1) + 63) // 64 * 64, (lens + 127) // 128 * 128)
+    order = np.argsort(pl, kind="stable")
+    spl = pl[order]
+    groups, start = [], 0
+    for end in [int(e) for e in np.flatnonzero(np.diff(spl)) + 1] + [B]:
+        if end < B and (end - start) * int(spl[end - 1]) < min_tokens:
+            continue  # too small a pass: these rows travel with the next longer group
+        groups.append((start, end, min(S, int(spl[end - 1]))))
+        start = end
+    out, passes = {}, 0
+    cap = (max_tokens + 255) // 256 * 256 + 256  # mv_create's activation rows
+    for s0, e0, width in groups:
+        rows = order[s0:e0]
+        r = eng.forward(np.ascontiguousarray(ids[rows, :width]), lens[rows], **want)
+        for k, v in r.items():
+            if v is not None:
+                out.setdefault(k, np.empty((B,) + v.shape[1:], v.dtype))[rows] = v
+        passes += -(-(e0 - s0) // min(max_batch, (cap - 256) // int(spl[e0 - 1])))
+    return out, groups, passes
+
+
+def _embed_ln_launches(eng, fn):
+    """fn()'s result and the encoder passes it ran (one embed_ln launch per pass)."""
+    eng.profile_read()
+    eng.profile_enable(True)
+    try:
+        r = fn()
+        return r, eng.profile_read()["embed_ln"][1]
+    finally:
+        eng.profile_enable(False)
+
+
 @pytest.mark.parametrize("compute", ["precise", "f16"])
 def test_forward_by_length_and_its_two_halves_match_the_padded_forward(gu, compute):
-    """Engine.forward_by_length (what ModelMemory.forward calls): the rows of a pad-to-longest batch grouped by their own padded length, one pass per group,
-    results back in place.  Same per-row mathematics as the one padded pass at a different padded length: probabilities agree at the fp16-operand level,
-    decisions wherever the top-2 margin is clear; rows of the longest group ran at the batch's own length in both forms and (MV_F16X8) agree bit for bit.
-    The one library call, the Python per-group walk and the two halves (begin / end, with every workspace set busy, and with one workspace set) give the
-    same bits."""
+    """Engine.forward_by_length (what ModelMemory.forward calls): the rows of a pad-to-longest batch grouped by their own padded length, each group run at
+    its own width, results back in place.  One library call gives the bits and the passes of one ``forward`` per group, also on a batch larger than one
+    upload whose groups span several passes.  Same per-row mathematics as the one padded pass at a different padded length: probabilities agree at the
+    fp16-operand level, decisions wherever the top-2 margin is clear; rows of the longest group ran at the batch's own length in both forms and (MV_F16X8)
+    agree bit for bit.  The two halves (begin / end, with every workspace set busy, and with one workspace set) give the same bits."""
     dk, wk = dict(layers=3, vocab_size=2048), dict(qk_scale=2.0, match_scale=6.0)
     dims, w = gu.weights_for(dk, wk)
-    eng = gu.engine_for(dk, wk, compute_dtype=compute, max_tokens=128 * 512, max_batch=128, max_anchors=32)
     ids, lens = synth.make_ids(128, 512, dims.vocab_size, ragged=True, min_len=5)
     ids = (ids * (np.arange(512)[None, :] < lens[:, None])).astype(np.int32)
+    B, S = ids.shape
+    # an engine of 8 192 tokens: B x S is eight times one upload and the groups of 256 / 384 / 512 tokens per row take two passes each
+    e8 = gu.engine_for(dk, wk, compute_dtype=compute, max_tokens=8192, max_batch=128, max_anchors=32)
+    e8.anchor_set(synth.make_anchor_bank(24))
+    ref, groups, ref_passes = _by_length_reference(e8, ids, lens, 4096, 8192, 128)
+    b16, passes = _embed_ln_launches(e8, lambda: e8.forward_by_length(ids, lens, min_tokens=4096))
+    assert all(np.array_equal(b16[k], ref[k]) for k in ("logits", "probs", "best", "best_idx")) and b16["embed"] is None
+    assert passes == ref_passes > len(groups)
+    widths = [g[2] for g in groups]
+    assert widths == sorted(widths) and set(widths) <= {64, 128, 192, 256, 384, 512} and groups[-1][1] == B
+    assert all((e0 - s0) * width >= 4096 for s0, e0, width in groups[:-1])  # every group but (possibly) the last is worth a launch
+    assert sum((e0 - s0) * width for s0, e0, width in groups) < 0.7 * B * S
+    t = e8.forward_by_length_begin(ids, lens, min_tokens=4096)
+    assert t[0] == "pending"
+    r = e8.forward_by_length_end(t)
+    assert all(np.array_equal(r[k], ref[k]) for k in ("logits", "probs", "best", "best_idx"))
+    # one pass each: a small batch (``forward``), a batch of one padded length (at that length), min_tokens >= B x S (``forward``)
+    for i, l, mt, width in ((ids[:16], lens[:16], None, S), (ids[:32], np.full(32, 200, np.int32), 4096, 256), (ids[:16], lens[:16], 16 * S, S)):
+        o, n = _embed_ln_launches(e8, lambda: e8.forward_by_length(i, l, min_tokens=mt))
+        f = e8.forward(np.ascontiguousarray(i[:, :width]), l)
+        assert n == 1 and all(np.array_equal(o[k], f[k]) for k in ("logits", "probs", "best", "best_idx"))
+    e8.anchor_reset()
+    eng = gu.engine_for(dk, wk, compute_dtype=compute, max_tokens=128 * 512, max_batch=128, max_anchors=32)
     eng.anchor_set(synth.make_anchor_bank(24))
     a = eng.forward(ids, lens)
     b = eng.forward_by_length(ids, lens, min_tokens=4096)
-    # b came from ONE mv_forward_ragged call; the same grouping done in Python around one mv_forward per group: the same bits
-    eng._forward_ragged = None
-    try:
-        d2 = eng.forward_by_length(ids, lens, min_tokens=4096)
-    finally:
-        del eng._forward_ragged
-    assert all(np.array_equal(b[k], d2[k]) for k in ("logits", "probs", "best", "best_idx"))
     e1 = eng.forward_by_length(ids, lens, want_logits=False, want_embed=True, min_tokens=4096)
     assert e1["logits"] is None and np.array_equal(e1["probs"], b["probs"]) and np.array_equal(e1["embed"], eng.forward_by_length(ids, lens, want_embed=True, min_tokens=4096)["embed"])
     d = float(np.abs(a["probs"] - b["probs"]).max())
@@ -713,6 +765,33 @@ def test_forward_by_length_and_its_two_halves_match_the_padded_forward(gu, compu
     for r in (eng1.forward_by_length_end(t1), eng1.forward_by_length_end(t2)):
         assert all(np.array_equal(r[k], b1[k]) for k in ("logits", "probs", "best", "best_idx"))
     eng1.anchor_reset()
+
+
+def test_anchor_append_waits_for_the_tickets_in_flight(gu):
+    """mv_anchor_append rewrites the anchor bank on workspace set 0's stream while a ticket of mv_forward_ragged_begin in flight on the other set may still
+    read it: the append waits for that ticket first.  Both tickets score against the bank they began with, bit for bit, and the new bank is the one the same
+    append gives with nothing in flight.  (This guards the wait; it cannot provoke the race on demand.)"""
+    dk, wk = dict(layers=3, vocab_size=2048), dict(qk_scale=2.0, match_scale=6.0)
+    dims, w = gu.weights_for(dk, wk)
+    eng = gu.engine_for(dk, wk, max_tokens=128 * 512, max_batch=128, max_anchors=32)
+    ids, lens = synth.make_ids(128, 512, dims.vocab_size, ragged=True, min_len=5)
+    aids, alens = synth.make_ids(20, 96, dims.vocab_size, seed=synth.SEED + 3, ragged=True, min_len=8)
+    eng.anchor_set(synth.make_anchor_bank(24))
+    ref = eng.forward_by_length(ids, lens, min_tokens=4096)
+    t1 = eng.forward_by_length_begin(ids, lens, min_tokens=4096)
+    t2 = eng.forward_by_length_begin(ids[::-1].copy(), lens[::-1].copy(), min_tokens=4096)
+    assert t1[0] == "pending" and t2[0] == "pending" and {t1[1], t2[1]} == {0, 1}
+    eng.anchor_reset()
+    eng.anchor_append(aids, alens)
+    r1, r2 = eng.forward_by_length_end(t1), eng.forward_by_length_end(t2)
+    for k in ("logits", "probs", "best", "best_idx"):
+        assert np.array_equal(r1[k], ref[k]) and np.array_equal(r2[k], ref[k][::-1]), k
+    bank = eng.anchor_get()
+    assert bank.shape[0] == 20
+    eng.anchor_reset()
+    eng.anchor_append(aids, alens)
+    assert np.array_equal(eng.anchor_get(), bank)
+    eng.anchor_reset()
 
 
 @pytest.mark.parametrize("gemm_tile,compute", PATHS)

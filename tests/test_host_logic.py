@@ -213,53 +213,6 @@ def test_documented_switch_defaults_match_the_library_source():
         assert src.count('"%s"' % k) == block.count('"%s"' % k) >= 1, k
 
 
-def test_forward_by_length_groups_rows_by_their_own_padded_length():
-    """binding.Engine.forward_by_length (ModelMemory.forward's engine call): a pad-to-longest batch of unsorted issue reports (predict_memory.py:97-101) is scored
-    in one pass per padded length of the rows' OWN token counts; groups too small to fill a pass travel with the next longer one; every row's result lands in
-    its place.  Host logic only: a recording stand-in for the engine."""
-    from memvul_amd.binding import Engine
-
-    class Rec:
-        P, n_anchors = 4, 3
-        BY_LENGTH_MIN_TOKENS = Engine.BY_LENGTH_MIN_TOKENS
-        forward_by_length = Engine.forward_by_length
-
-        def __init__(self):
-            self.calls = []
-
-        def forward(self, ids, lens, want_logits=True, want_probs=True, want_embed=False):
-            assert ids.flags["C_CONTIGUOUS"] and ids.dtype == np.int32 and int(lens.max()) <= ids.shape[1]
-            self.calls.append((ids.shape, lens.copy()))
-            key = ids[:, 0].astype(np.float32)  # a row's "result" = a function of the row alone
-            n = len(lens)
-            return {"logits": None, "probs": np.repeat(key, 6).reshape(n, 3, 2) if want_probs else None, "best": np.stack([key, lens.astype(np.float32)], 1),
-                    "best_idx": lens.astype(np.int32), "embed": None}
-
-    rng = np.random.default_rng(3)
-    B, S = 512, 512
-    lens = rng.integers(5, S + 1, B).astype(np.int32)
-    lens[7] = S
-    ids = np.zeros((B, S), np.int32)
-    ids[:, 0] = np.arange(B)
-    e = Rec()
-    out = e.forward_by_length(ids, lens, want_logits=False)
-    assert out["logits"] is None and out["embed"] is None
-    assert np.array_equal(out["best"][:, 0], np.arange(B)) and np.array_equal(out["best_idx"], lens) and np.array_equal(out["probs"][:, 2, 1], np.arange(B))
-    widths = [c[0][1] for c in e.calls]
-    assert widths == sorted(widths) and set(widths) <= {64, 128, 192, 256, 384, 512} and sum(c[0][0] for c in e.calls) == B
-    for (shape, ls) in e.calls[:-1]:
-        assert shape[0] * shape[1] >= Rec.BY_LENGTH_MIN_TOKENS  # every pass but (possibly) the last is worth a launch
-    for (shape, ls) in e.calls:
-        assert int(ls.max()) > (shape[1] - (64 if shape[1] <= 256 else 128))  # the pass runs at the padded length of its longest row
-    padded_tokens = sum(c[0][0] * c[0][1] for c in e.calls)
-    assert padded_tokens < 0.7 * B * S
-    # a small batch, and a batch of one padded length, stay ONE call (the second at its own width)
-    e = Rec(); e.forward_by_length(ids[:16], lens[:16]); assert len(e.calls) == 1 and e.calls[0][0] == (16, S)
-    e = Rec(); l2 = np.full(B, 200, np.int32); e.forward_by_length(ids, l2); assert len(e.calls) == 1 and e.calls[0][0] == (B, 256)
-    # min_tokens larger than the batch: everything travels together, at the longest row's length
-    e = Rec(); e.forward_by_length(ids, lens, min_tokens=B * S); assert [c[0] for c in e.calls] == [(B, S)]
-
-
 def test_native_record_formatter_prints_what_json_dumps_prints():
     """records.format_batch through mv_format_records (host-only code of libmemvul_hip.so: CPython's repr(float) restated in C++) gives the bytes of the Python
     formatter — i.e. of json.dumps(make_output_human_readable(...)) (model_memory.py:169-191 -> predict_memory.py:111; tests/test_plumbing.py pins that one) —
