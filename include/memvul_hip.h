@@ -75,7 +75,7 @@ typedef struct mv_config {
 
 /* Replaces Model.from_params + model.to(cuda_device) (predict_memory.py:62-70): binds `device`,
  * creates the stream and reserves all workspaces. */
-/* Environment switches read HERE — five, each with a tested default, each parsed strictly (a value the library does not understand fails mv_create with a
+/* Environment switches read HERE — six, each with a tested default, each parsed strictly (a value the library does not understand fails mv_create with a
  * message; a typo never selects other numerics silently):
  *   MEMVUL_CLS_ASIDE          1 (default) | 0.  MV_F16X8: 1 = the [CLS]-row form (every GEMM sweeps the weight-side correction term, the A-side term is
  *                             restored for the [CLS] row of each sequence alone: only that row reaches the pooler, model_memory.py:99); 0 = both first-order
@@ -86,7 +86,9 @@ typedef struct mv_config {
  *                             rows get it in every block either way; "q" = the default of rounds 4 - 6a: -2.7 % issue reports/s, 3 % less logit error).
  *   MEMVUL_CLS_PRUNE          1 (default) | 0: after the last layer's K / V projection only the [CLS] rows are processed.
  *   MEMVUL_STREAMS            2 (default) | 1: batches of the resident sweep in flight (mv_set_streams changes it later).
- * (The sixth switch of the product, MEMVUL_COMPUTE = precise | f16, is read by the Python surface: memvul_amd/binding.py default_compute.)
+ *   MEMVUL_FORM               default | safe: the form of MV_F16X8 the handle starts in (mv_set_form changes it later).  "safe" with mv_finalize_weights(MV_F16) fails.
+ *                             In the safe form MEMVUL_CLS_ASIDE, MEMVUL_CLS_ASIDE_MIN_LEN and MEMVUL_QKV_ASIDE have no effect (it is their most conservative setting).
+ * (The seventh switch of the product, MEMVUL_COMPUTE = precise | f16, is read by the Python surface: memvul_amd/binding.py default_compute.)
  * Development A/B knobs (kernel path forced at test sizes, raster, grid share, one-plane short passes) exist only in the -DMEMVUL_DEV_SWITCHES build
  * (libmemvul_hip_dev.so: memvul_amd/build.py, loaded by the GPU tests and A/B scripts that need them); this library does not read them. */
 int mv_create(int device, const mv_config* cfg, mv_handle** out);
@@ -114,6 +116,22 @@ int mv_load_tensor(mv_handle* h, const char* name, const void* host_ptr, int dty
  * and 2.5e-3 off even on random-init weights (oracle/precision_model.py), against a 1e-3 budget, at the
  * same MFMA rate as fp16.  Embeddings, LayerNorm, biases, pooler, header and matcher stay fp32. */
 int mv_finalize_weights(mv_handle* h, int compute_dtype);
+
+/* The two forms of compute dtype MV_F16X8: same weights, same planes, same handle; only the per-pass choices differ.
+ *   MV_FORM_DEFAULT  what bench.py's headline is measured in: the [CLS]-row form, the special rows, two fp16 planes through attention up to 128 keys.  Holds 1e-3
+ *                    on the logits for diffuse attention and for attention sinks on [CLS] / [SEP].
+ *   MV_FORM_SAFE     the form for models whose heads park most of their mass on an ORDINARY token (mv_attention_concentration reports them), where the default reads
+ *                    0.8 - 2.7e-3: both first-order correction terms in every row of every GEMM, the A-side term in all three blocks of the QKV projection, and
+ *                    Q, K, V, P as hi + lo fp16 planes through attention at EVERY padded length (the sink token's V reaches every row un-averaged: its single-plane
+ *                    fp16 storage is what is left otherwise) and through the single-query attention of the pruned last layer.  It costs the GEMMs their A-side sweep
+ *                    in every row and attention three times the MFMAs, twice the K / V bytes and one wave per SIMD above 128 keys; rate and error envelope as
+ *                    measured: DESIGN.md section 2, profiles/LEDGER.md.
+ * mv_set_form: MV_FORM_SAFE on a handle finalized as MV_F16 -> MV_ERR_STATE, an unknown value -> MV_ERR_INVALID.  The form of a pass is read on the host when the
+ * pass is enqueued: work already in flight keeps the form it was enqueued with.  mv_get_form returns the current form. */
+#define MV_FORM_DEFAULT 0
+#define MV_FORM_SAFE 1
+int mv_set_form(mv_handle* h, int form);
+int mv_get_form(mv_handle* h);
 
 /* ---- anchor memory (replaces ModelMemory.forward_gold_instances, model_memory.py:105-115, as
  *      driven by predict_memory.py:81-83 and callbacks.py:48-53) ------------------------------ */
@@ -202,6 +220,8 @@ int mv_x8_saturation(mv_handle* h, int64_t* clamped, int reset);
  * therefore keeps, at no measurable cost, *max_collision = the maximum over every (sequence, head, layer) processed since the handle was created (or the last reset)
  * of sum_{j >= 2} p[CLS row][j]^2 (>= f^2 when one ordinary token holds the share f), *items_over = how many of them exceeded 0.25 (f > 0.5) and *items_total = how
  * many were looked at (sequences of at least 16 tokens); synchronises.  The Python wrapper warns once when more than 2 % of the items are over (binding.Engine).
+ * The answer to a non-zero count is the safe form (mv_set_form(MV_FORM_SAFE) / MEMVUL_FORM=safe; the Python surface switches by itself under MEMVUL_ON_SINK=safe);
+ * the safe form keeps counting, with the same meaning.
  * No reference counterpart (the reference computes in fp32). */
 int mv_attention_concentration(mv_handle* h, float* max_collision, int64_t* items_over, int64_t* items_total, int reset);
 
@@ -245,7 +265,9 @@ const char* mv_kernel_class_name(int cls);
 /* Debug taps for per-kernel parity tests: run the encoder on (ids,lens) and stop after `n_layers`
  * encoder layers (0 = embeddings only, <0 = all), then copy an internal buffer to host.
  * buffer ids: 0 hidden fp32 [B*Sp,768]; 1 hidden fp16; 2 Q fp16 [B,12,Sp,64]; 3 K fp16 [B,12,Sp,64];
- * 4 V^T fp16 [B,12,64,Sp]; 5 attention context fp16 [B*Sp,768]; 6 FFN intermediate fp16 [B*Sp,3072].
+ * 4 V^T fp16 [B,12,64,Sp]; 5 attention context fp16 [B*Sp,768]; 6 FFN intermediate fp16 [B*Sp,3072];
+ * 7, 8, 9 (MV_F16X8) the second fp16 planes of Q, K, V^T, fp16(x - fp16(x)), in the layouts of 2, 3, 4: valid after a pass that wrote them (padded length
+ * <= 128 in the default form, every pass in the safe form); 10 the embedding fp32 [B, proj_dim] of a full run.
  * (Sp = S rounded up to a multiple of 64, above 256 to a multiple of 128; buffers hold the state of the LAST executed layer; Q carries
  * the folded 1/8.  The pass takes the path its size selects — persistent kernels or the small-pass kernels — with last-layer pruning
  * off and the final LayerNorm applied, so buffer 0 is the normalised output of layer n_layers.) */

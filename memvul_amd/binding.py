@@ -19,7 +19,11 @@ DEV_SWITCHES = ("MEMVUL_GEMM_TILE", "MEMVUL_SHORT_VLO", "MEMVUL_RASTER", "MEMVUL
 
 MV_F32, MV_F16, MV_BF16, MV_I32, MV_I64 = 0, 1, 2, 3, 4
 MV_F16X8 = 6  # compute dtype only ("precise"): fp16 MFMA sweep + one fp8 (e4m3) correction sweep per GEMM (include/memvul_hip.h)
-COMPUTE_DTYPES = {"f16": MV_F16, "fast": MV_F16, "f16x8": MV_F16X8, "precise": MV_F16X8}
+COMPUTE_DTYPES = {"f16": MV_F16, "fast": MV_F16, "f16x8": MV_F16X8, "precise": MV_F16X8, "safe": MV_F16X8}
+# the two forms of MV_F16X8 (include/memvul_hip.h mv_set_form).  "safe" as a compute dtype name = MV_F16X8 + the safe form set after finalize: both first-order
+# correction terms in every row and two fp16 planes through attention at every length — the form that holds 1e-3 with an attention sink on an ordinary token
+MV_FORM_DEFAULT, MV_FORM_SAFE = 0, 1
+FORMS = {"default": MV_FORM_DEFAULT, "safe": MV_FORM_SAFE}
 # The product's default is the compute dtype that holds the reference's 1e-3 logit tolerance on trained-like weights
 # (model_memory.py:133-147 at config_memory.json:38's temperature): MV_F16X8.  MV_F16 ("fast") is an explicit opt-in:
 # ~1.7x the rate, logits within 1e-3 only on small-logit models (measured 3.0-5.6e-3 at |logit| ~ 3).
@@ -27,7 +31,7 @@ DEFAULT_COMPUTE = "precise"
 
 
 def default_compute() -> str:
-    """$MEMVUL_COMPUTE (f16 | fast | f16x8 | precise) or the contract-holding default."""
+    """$MEMVUL_COMPUTE (f16 | fast | f16x8 | precise | safe) or the contract-holding default."""
     return os.environ.get("MEMVUL_COMPUTE", DEFAULT_COMPUTE)
 
 
@@ -45,6 +49,22 @@ def compute_dtype_of(name_or_code) -> int:
     return int(name_or_code)
 
 
+def on_sink_policy() -> str:
+    """$MEMVUL_ON_SINK = warn (default) | safe, parsed strictly: what an MV_F16X8 engine does when the concentration monitor reports attention sinks on ordinary
+    tokens — warn once and go on in the default form, or switch to the safe form (Engine._on_sink_trip)."""
+    v = os.environ.get("MEMVUL_ON_SINK", "warn")
+    if v not in ("warn", "safe"):
+        raise ValueError(f"MEMVUL_ON_SINK={v!r}: expected 'warn' or 'safe'")
+    return v
+
+
+def wants_safe_form(name_or_code) -> bool:
+    """True when the compute dtype asked for (None = default_compute()) is the name "safe": MV_F16X8 in the safe form."""
+    if name_or_code is None:
+        name_or_code = default_compute()
+    return isinstance(name_or_code, str) and name_or_code.lower() == "safe"
+
+
 NUM_KERNEL_CLASSES = 14
 
 # every symbol include/memvul_hip.h declares (tests check the .so exports all of them)
@@ -52,7 +72,7 @@ ABI_SYMBOLS = [
     "mv_create", "mv_destroy", "mv_last_error", "mv_sync", "mv_load_tensor", "mv_finalize_weights",
     "mv_anchor_reset", "mv_anchor_append", "mv_anchor_count", "mv_anchor_get", "mv_anchor_set",
     "mv_forward", "mv_forward_ragged", "mv_forward_ragged_begin", "mv_forward_ragged_end", "mv_encode", "mv_match", "mv_topk", "mv_corpus_upload", "mv_corpus_run", "mv_corpus_run_len",
-    "mv_corpus_results", "mv_x8_saturation", "mv_attention_concentration", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
+    "mv_corpus_results", "mv_x8_saturation", "mv_attention_concentration", "mv_set_form", "mv_get_form", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
     "mv_debug_encode", "mv_debug_read", "mv_test_gemm", "mv_test_gemm_pp", "mv_test_e4m3", "mv_format_records", "mv_comm_prepare", "mv_comm_unique_id", "mv_comm_init", "mv_comm_allgather",
     "mv_comm_destroy", "mv_comm_info", "mv_device_count",
 ]
@@ -115,6 +135,8 @@ def load_library(path: Optional[str] = None, dev: bool = False):
         "mv_x8_saturation": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int]),
         "mv_attention_concentration": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
         "mv_set_streams": (C.c_int, [vp, C.c_int]),
+        "mv_set_form": (C.c_int, [vp, C.c_int]),
+        "mv_get_form": (C.c_int, [vp]),
         "mv_profile_enable": (C.c_int, [vp, C.c_int]),
         "mv_profile_select": (C.c_int, [vp, C.c_uint32]),
         "mv_profile_read": (C.c_int, [vp, P(C.c_double), P(C.c_int64), C.c_int]),
@@ -171,6 +193,7 @@ class Engine:
         """proj_dim: width of the embedding the matcher runs on — 512 (the header output: use_header=True, every reference
         config) or 768 (use_header=False: the pooler output, no ``_projector_single`` in the state dict).  dev: load the development
         build (tests / A/B scripts: the only one that reads DEV_SWITCHES)."""
+        on_sink_policy()  # (a malformed MEMVUL_ON_SINK raises before anything is created)
         self._lib = load_library(dev=dev)
         self.P = int(proj_dim)
         self.cfg = MvConfig(vocab_size, 768, layers, 12, 3072, max_pos, type_vocab, self.P, ln_eps, max_tokens,
@@ -183,6 +206,15 @@ class Engine:
         self._h = h
         self.device = device
         self._tickets = []  # forward_by_length_begin: batches in flight, oldest first
+        self._init_sink_state()
+
+    def _init_sink_state(self):
+        """Host state of the MEMVUL_ON_SINK fall-back (no library call: a stand-in engine can use it)."""
+        self._on_sink = on_sink_policy()
+        self._form = "default"
+        self._anchor_log = []        # the (ids, lens) of every anchor_append since the last reset: what a switch of form re-encodes the bank from
+        self._bank_replayable = True  # False once anchor_set installed embeddings the binding cannot re-encode
+        self._corpus_runs = []       # the corpus_run calls since the last corpus_upload: what a switch of form sweeps once more
 
     # -- plumbing
     def _check(self, rc: int, what: str):
@@ -227,6 +259,29 @@ class Engine:
         self._check(self._lib.mv_finalize_weights(self._h, compute_dtype_of(compute_dtype)), "mv_finalize_weights")
         self._precise = compute_dtype_of(compute_dtype) == MV_F16X8
         self._sat_warned = False
+        if wants_safe_form(compute_dtype):
+            self.set_form("safe")
+        else:
+            self._form = "safe" if self._get_form() == MV_FORM_SAFE else "default"  # (MEMVUL_FORM, read by mv_create)
+
+    # -- the two forms of MV_F16X8
+    def _get_form(self) -> int:
+        return int(self._lib.mv_get_form(self._h))
+
+    def _set_form(self, code: int):
+        self._check(self._lib.mv_set_form(self._h, code), "mv_set_form")
+
+    @property
+    def form(self) -> str:
+        """"default" or "safe" (include/memvul_hip.h mv_set_form)."""
+        return self._form
+
+    def set_form(self, form: str):
+        """The form the passes enqueued from now on run in: "default" | "safe" (work in flight keeps its own).  "safe" on an MV_F16 engine raises."""
+        if form not in FORMS:
+            raise ValueError(f"unknown form {form!r}: expected one of {sorted(FORMS)}")
+        self._set_form(FORMS[form])
+        self._form = form
 
     def x8_saturation(self, reset: bool = False) -> int:
         """MV_F16X8: activation elements (raw stream, attention context, GELU output) that fell outside the +-112 range of the fp8
@@ -245,10 +300,16 @@ class Engine:
         return float(m.value), int(n.value), int(t.value)
 
     def _check_saturation(self):
-        """Called after the host-synchronous entry points of the precise mode: warn ONCE when the fp8 planes clamped anything."""
-        if getattr(self, "_precise", False) and not getattr(self, "_conc_warned", False):
+        """Called after the host-synchronous entry points of the precise mode: warn ONCE when the fp8 planes clamped anything, and once when the concentration
+        monitor trips.  Returns True when that trip switched the engine to the safe form (MEMVUL_ON_SINK=safe): the caller redoes its call."""
+        switched = False
+        if getattr(self, "_precise", False) and not getattr(self, "_conc_warned", False) and self._form != "safe":  # (the safe form keeps counting, trips nothing)
             m, n, t = self.attention_concentration()
-            if t >= 100 and n > 0.02 * t:  # systematic, not the odd head of the odd sequence
+            if t >= 100 and n > 0.02 * t and self._on_sink == "safe":
+                self._conc_warned = True
+                self._on_sink_trip(m, n, t)
+                switched = True
+            elif t >= 100 and n > 0.02 * t:  # systematic, not the odd head of the odd sequence
                 self._conc_warned = True
                 warnings.warn(f"MV_F16X8: in {n} of {t} (sequence, head, layer) items the [CLS] row puts more than half of a head's attention on ONE ordinary token "
                               f"(collision mass up to {m:.2f}): the 1e-3 logit tolerance of the default form is backed by measurement for diffuse attention and "
@@ -262,15 +323,45 @@ class Engine:
                 warnings.warn(f"MV_F16X8: {n} activation element(s) exceeded the +-112 range of the fp8 correction planes and were "
                               "computed at fp16 accuracy; the 1e-3 logit tolerance is not backed by measurement for this model "
                               "(include/memvul_hip.h mv_x8_saturation; Engine.x8_saturation())", RuntimeWarning, stacklevel=3)
+        return switched
+
+    def _on_sink_trip(self, m: float, n: int, t: int):
+        """MEMVUL_ON_SINK=safe, the monitor has tripped: the safe form for the rest of the engine's life, the counters reset, the anchor bank encoded again in
+        that form from the ids anchor_append was given (a bank installed with anchor_set is kept: there is nothing to encode it from), one warning."""
+        self.set_form("safe")
+        self.attention_concentration(reset=True)
+        n_bank = self.n_anchors
+        if self._bank_replayable:
+            log = self._anchor_log
+            self._anchor_reset()
+            for ids, lens in log:
+                self._anchor_append(ids, lens)
+            bank = f"the anchor bank ({n_bank} anchors) was encoded again in the safe form"
+        else:
+            bank = (f"the anchor bank ({n_bank} anchors) holds embeddings installed with anchor_set and was KEPT as it is: install a bank encoded in the safe form "
+                    "to have both sides of the match in it") if n_bank else "the anchor bank is empty"
+        warnings.warn(f"MV_F16X8: in {n} of {t} (sequence, head, layer) items the [CLS] row puts more than half of a head's attention on ONE ordinary token "
+                      f"(collision mass up to {m:.2f}), outside the measured envelope of the default form: MEMVUL_ON_SINK=safe switched this engine to the SAFE form "
+                      f"(include/memvul_hip.h mv_set_form) for the rest of its life; {bank}; the call that tripped is redone in the safe form",
+                      RuntimeWarning, stacklevel=4)
 
     # -- anchors
-    def anchor_reset(self):
+    def _anchor_reset(self):
         self._check(self._lib.mv_anchor_reset(self._h), "mv_anchor_reset")
+
+    def _anchor_append(self, ids: np.ndarray, lens: np.ndarray):
+        self._check(self._lib.mv_anchor_append(self._h, _ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1]), "mv_anchor_append")
+
+    def anchor_reset(self):
+        self._anchor_reset()
+        self._anchor_log, self._bank_replayable = [], True
 
     def anchor_append(self, ids: np.ndarray, lens: np.ndarray):
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
-        self._check(self._lib.mv_anchor_append(self._h, _ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1]), "mv_anchor_append")
-        self._check_saturation()
+        self._anchor_append(ids, lens)
+        if self._on_sink == "safe" and not getattr(self, "_conc_warned", False):  # (kept only while a switch of form may still need them)
+            self._anchor_log.append((ids.copy(), lens.copy()))
+        self._check_saturation()  # (a trip here encodes the whole bank again, these anchors included)
 
     @property
     def n_anchors(self) -> int:
@@ -289,6 +380,7 @@ class Engine:
         v = _as(v, np.float32)
         self._check_width(v, "anchor_set")
         self._check(self._lib.mv_anchor_set(self._h, _ptr(v), v.shape[0]), "mv_anchor_set")
+        self._anchor_log, self._bank_replayable = [], False
 
     # -- hot loop
     def forward(self, ids: np.ndarray, lens: np.ndarray, want_logits=True, want_probs=True, want_embed=False):
@@ -297,7 +389,8 @@ class Engine:
         out = _outputs(B, self.n_anchors, self.P, want_logits, want_probs, want_embed)
         self._check(self._lib.mv_forward(self._h, _ptr(ids), _ptr(lens), B, S, _ptr(out["logits"]), _ptr(out["probs"]), _ptr(out["best"]),
                                          _ptr(out["best_idx"]), _ptr(out["embed"])), "mv_forward")
-        self._check_saturation()
+        if self._check_saturation():
+            return self.forward(ids, lens, want_logits, want_probs, want_embed)
         return out
 
     # tokens below which one pad-to-longest pass is kept as it is (a pass of a few thousand tokens leaves most of the 256 persistent workgroups idle)
@@ -319,46 +412,60 @@ class Engine:
         out = _outputs(B, self.n_anchors, self.P, want_logits, want_probs, want_embed)
         self._check(self._lib.mv_forward_ragged(self._h, _ptr(ids), _ptr(lens), B, S, int(min_tokens), _ptr(out["logits"]), _ptr(out["probs"]),
                                                 _ptr(out["best"]), _ptr(out["best_idx"]), _ptr(out["embed"])), "mv_forward_ragged")
-        self._check_saturation()
+        if self._check_saturation():
+            return self.forward_by_length(ids, lens, want_logits, want_probs, want_embed, min_tokens)
         return out
 
     def forward_by_length_begin(self, ids: np.ndarray, lens: np.ndarray, want_logits=True, want_probs=True, want_embed=False, min_tokens: Optional[int] = None):
         """``forward_by_length`` handed over without waiting for it (mv_forward_ragged_begin): returns a ticket for ``forward_by_length_end``.  One batch per
         workspace set may be in flight (two by default); collect in the order of the calls.  A batch the asynchronous entry cannot take (too small to be
-        worth grouping, more than max_batch rows, every workspace set busy: the library's MV_ERR_CAPACITY) is scored at once and its ticket holds the results."""
+        worth grouping, more than max_batch rows, every workspace set busy: the library's MV_ERR_CAPACITY) is scored at once and its ticket holds the results.
+        MEMVUL_ON_SINK=safe: while the engine is in the default form a ticket remembers that and keeps its ``ids`` / ``lens`` — collected after the engine has
+        switched to the safe form, it is scored again (``forward_by_length_end``)."""
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         B, S = ids.shape
         mt = self.BY_LENGTH_MIN_TOKENS if min_tokens is None else min_tokens
+        redo = (self._form, ids, lens, bool(want_logits), bool(want_probs), bool(want_embed), min_tokens) if self._on_sink == "safe" and self._form != "safe" else None
         if B > 0 and B * S >= 2 * mt:
             t = C.c_int(-1)
             rc = self._lib.mv_forward_ragged_begin(self._h, _ptr(ids), _ptr(lens), B, S, int(mt), int(want_logits), int(want_probs), int(want_embed), C.byref(t))
             if rc == 0:
                 self._tickets.append(t.value)
-                return ("pending", t.value, B, self.n_anchors, bool(want_logits), bool(want_probs), bool(want_embed))
+                return ("pending", t.value, B, self.n_anchors, bool(want_logits), bool(want_probs), bool(want_embed), redo)
             if rc != -5:  # (MV_ERR_CAPACITY: below)
                 self._check(rc, "mv_forward_ragged_begin")
-        return ("done", self.forward_by_length(ids, lens, want_logits, want_probs, want_embed, min_tokens))
+        out = self.forward_by_length(ids, lens, want_logits, want_probs, want_embed, min_tokens)
+        return ("done", out, None if self._form == "safe" else redo)  # (a trip inside that call: the results are the safe form's already)
+
+    def _rescore(self, redo):
+        """A ticket begun in the default form, collected after the switch: its batch once more, synchronously, in the safe form."""
+        _, ids, lens, want_logits, want_probs, want_embed, min_tokens = redo
+        return self.forward_by_length(ids, lens, want_logits, want_probs, want_embed, min_tokens)
 
     def forward_by_length_end(self, ticket):
-        """The results of a ``forward_by_length_begin`` ticket.  Collecting consumes the ticket, also when this call raises."""
+        """The results of a ``forward_by_length_begin`` ticket.  Collecting consumes the ticket, also when this call raises.  MEMVUL_ON_SINK=safe: the monitor is
+        read at EVERY collection while the engine is in the default form (that read waits for the batch in flight behind this one: the price of the guarantee
+        that no result handed out after the trip comes from the default form), and a ticket begun in the default form is scored again after the switch."""
         if ticket[0] == "done":
-            return ticket[1]
-        _, t, B, G, want_logits, want_probs, want_embed = ticket  # (G: the anchors the batch began with, what the library scatters)
+            return self._rescore(ticket[2]) if ticket[2] is not None and self._form == "safe" else ticket[1]
+        _, t, B, G, want_logits, want_probs, want_embed, redo = ticket  # (G: the anchors the batch began with, what the library scatters)
         if not self._tickets or self._tickets[0] != t:
             raise RuntimeError("forward_by_length_end: tickets are collected in the order they were issued")
         out = _outputs(B, G, self.P, want_logits, want_probs, want_embed)
         self._tickets.pop(0)
         self._check(self._lib.mv_forward_ragged_end(self._h, t, _ptr(out["logits"]), _ptr(out["probs"]), _ptr(out["best"]), _ptr(out["best_idx"]), _ptr(out["embed"])),
                     "mv_forward_ragged_end")
-        if not self._tickets:  # (the counters are read after a synchronisation of EVERY stream: with the next batch in flight that would wait for it — holding the lock)
-            self._check_saturation()
-        return out
+        stale = redo is not None and self._form == "safe"  # begun before the switch: its results are the default form's
+        if not self._tickets or (redo is not None and not stale):  # (the counters are read after a synchronisation of EVERY stream: with the next batch in flight that would wait for it — holding the lock)
+            stale = self._check_saturation() or stale
+        return self._rescore(redo) if stale and redo is not None else out
 
     def encode(self, ids: np.ndarray, lens: np.ndarray) -> np.ndarray:
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         out = np.empty((ids.shape[0], self.P), np.float32)
         self._check(self._lib.mv_encode(self._h, _ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1], _ptr(out)), "mv_encode")
-        self._check_saturation()
+        if self._check_saturation():
+            return self.encode(ids, lens)
         return out
 
     def match(self, u: np.ndarray):
@@ -385,11 +492,14 @@ class Engine:
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         self._check(self._lib.mv_corpus_upload(self._h, _ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1]), "mv_corpus_upload")
         self._corpus_n = ids.shape[0]
+        self._corpus_runs = []
 
     def corpus_run(self, first: int, count: int, batch: int, keep_probs: bool = False, s_eff: int = 0):
         """Enqueue IRs [first, first+count) of the resident corpus in batches of `batch` (asynchronous).  s_eff > 0:
         process only the first s_eff tokens of each row (length-bucketed sweeps, see bucketed_sweep)."""
         self._check(self._lib.mv_corpus_run_len(self._h, first, count, batch, int(keep_probs), int(s_eff)), "mv_corpus_run_len")
+        if self._on_sink == "safe" and self._form != "safe":
+            self._corpus_runs.append((first, count, batch, keep_probs, s_eff))
 
     def bucketed_sweep(self, ids: np.ndarray, lens: np.ndarray, batch: int, with_probs: bool = False):
         """Score a ragged corpus with each batch padded to ITS longest member (the reference's pad-to-longest collation,
@@ -414,7 +524,11 @@ class Engine:
         idx = np.empty((count,), np.int32)
         ps = np.empty((count, self.n_anchors), np.float32) if with_probs else None
         self._check(self._lib.mv_corpus_results(self._h, first, count, _ptr(best), _ptr(idx), _ptr(ps)), "mv_corpus_results")
-        self._check_saturation()
+        if self._check_saturation():  # MEMVUL_ON_SINK=safe tripped: the sweeps over the resident corpus once more, in the safe form
+            runs, self._corpus_runs = self._corpus_runs, []
+            for r in runs:
+                self.corpus_run(*r)
+            self._check(self._lib.mv_corpus_results(self._h, first, count, _ptr(best), _ptr(idx), _ptr(ps)), "mv_corpus_results")
         return best, idx, ps
 
     # -- multi-GPU exchange (RCCL bound inside the library; no torch in the process)
@@ -493,7 +607,8 @@ class Engine:
         shapes = {
             0: ((B, Sp, 768), np.float32), 1: ((B, Sp, 768), np.float16), 2: ((B, 12, Sp, 64), np.float16),
             3: ((B, 12, Sp, 64), np.float16), 4: ((B, 12, 64, Sp), np.float16), 5: ((B, Sp, 768), np.float16),
-            6: ((B, Sp, 3072), np.float16), 7: ((B, self.P), np.float32),
+            6: ((B, Sp, 3072), np.float16), 7: ((B, 12, Sp, 64), np.float16), 8: ((B, 12, Sp, 64), np.float16), 9: ((B, 12, 64, Sp), np.float16),
+            10: ((B, self.P), np.float32),
         }
         shape, dt = shapes[buffer]
         out = np.empty(shape, dt)
@@ -514,7 +629,7 @@ class Engine:
                     out[tuple(i2)] = t
         return out
 
-    _TOKEN_AXIS = {0: 1, 1: 1, 2: 2, 3: 2, 4: 3, 5: 1, 6: 1}  # debug buffer -> its token axis
+    _TOKEN_AXIS = {0: 1, 1: 1, 2: 2, 3: 2, 4: 3, 5: 1, 6: 1, 7: 2, 8: 2, 9: 3}  # debug buffer -> its token axis (7 - 9: the lo planes of 2 - 4)
 
     def test_gemm(self, A16: np.ndarray, W16: np.ndarray, bias: Optional[np.ndarray], variant: int = 0, iters: int = 1):
         A16, W16 = _as(A16, np.float16), _as(W16, np.float16)

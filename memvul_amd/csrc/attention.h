@@ -19,7 +19,7 @@ struct AttnArgs {
   int B;
   uint8_t* ctx8;        // MV_F16X8 (attention_v2_kernel<.., X8 = 1>): [B*S][1536] = [lo8 (768) | hi8 (768)] planes of ctx (gemm_pp.h)
   unsigned long long* x8_sat; // MV_F16X8: device counter of context elements beyond the fp8 planes' range (common.h x8_planes4)
-  const half_t* vt_lo;  // attention_v2_kernel<.., VLO = 1> (MV_F16X8, padded length <= 128): V^T's second fp16 plane, fp16(V - fp16(V)), same layout as vt
+  const half_t* vt_lo;  // attention_v2_kernel<.., VLO = 1> (MV_F16X8: padded length <= 128 in the default form, every padded length in the safe form): V^T's second fp16 plane, fp16(V - fp16(V)), same layout as vt
   const half_t *q_lo, *k_lo;  // the same for Q and K
   // MV_F16X8, round 6 "special rows" (rows 0 and 1 of every sequence hold its [CLS] and [SEP] token: misc_kernels.h embed_ln_kernel):
   const half_t* vlo_sp;  // 2^11 x the low parts of V of those two keys, [b 12 + head][64 dims][2] fp16 (gemm_pp.h GemmArgs::vlo_sp): O += p[:, 0..1] V_lo[0..1] —
@@ -43,10 +43,14 @@ struct AttnArgs {
 // additive -10000 on padded keys.
 // q: [Bpad][768] fp32 (the Q projection of the gathered [CLS] rows, 1/8 already folded into W_q), ctx: [Bpad][768] fp16
 // (or ctx32: the same rows in fp32).
+// LO (the safe form of MV_F16X8, engine.hip mv_set_form): k_lo / vt_lo are the second fp16 planes of K and V^T and nothing of the row is rounded to fp16 — the fp32
+// query as it is, scores q . (k_hi + k_lo), context sum p (v_hi + v_lo) with the fp32 p.  LO = false is the kernel as it always was (the planes are not read).
+template <bool LO = false>
 __global__ __launch_bounds__(256) void attention_cls_kernel(const float* __restrict__ q, const half_t* __restrict__ k,
                                                             const half_t* __restrict__ vt, const int32_t* __restrict__ lens,
                                                             half_t* __restrict__ ctx, int S, int nbh, float* __restrict__ ctx32 = nullptr,
-                                                            const half_t* __restrict__ vlo_sp = nullptr) {
+                                                            const half_t* __restrict__ vlo_sp = nullptr, const half_t* __restrict__ k_lo = nullptr,
+                                                            const half_t* __restrict__ vt_lo = nullptr) {
   __shared__ float ps[4][512];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bh = blockIdx.x * 4 + wave;
@@ -61,6 +65,7 @@ __global__ __launch_bounds__(256) void attention_cls_kernel(const float* __restr
     const float4 t0 = qp[0], t1 = qp[1];
     qv[0] = (float)(half_t)t0.x; qv[1] = (float)(half_t)t0.y; qv[2] = (float)(half_t)t0.z; qv[3] = (float)(half_t)t0.w;
     qv[4] = (float)(half_t)t1.x; qv[5] = (float)(half_t)t1.y; qv[6] = (float)(half_t)t1.z; qv[7] = (float)(half_t)t1.w;
+    if constexpr (LO) { qv[0] = t0.x; qv[1] = t0.y; qv[2] = t0.z; qv[3] = t0.w; qv[4] = t1.x; qv[5] = t1.y; qv[6] = t1.z; qv[7] = t1.w; }
   }
   // ---- scores -> LDS (key = key0 + sub)
   const half_t* kb = k + (size_t)bh * S * MV_HEAD_DIM + (size_t)sub * MV_HEAD_DIM + 8 * c;
@@ -70,6 +75,13 @@ __global__ __launch_bounds__(256) void attention_cls_kernel(const float* __restr
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) s = __builtin_fmaf(qv[e], (float)kk[e], s);
+    if constexpr (LO) {
+      const half8_t kl = *(const half8_t*)(k_lo + (kb - k) + (size_t)key0 * MV_HEAD_DIM);
+      float sl = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sl = __builtin_fmaf(qv[e], (float)kl[e], sl);
+      s += sl;
+    }
     s += __shfl_xor(s, 1, 64);
     s += __shfl_xor(s, 2, 64);
     s += __shfl_xor(s, 4, 64);
@@ -84,7 +96,7 @@ __global__ __launch_bounds__(256) void attention_cls_kernel(const float* __restr
   for (int key = lane; key < S; key += 64) {
     const float p = __expf(pw[key] - mx);
     psum += p;
-    pw[key] = (float)(half_t)p;
+    pw[key] = LO ? p : (float)(half_t)p;
   }
   const float inv = 1.0f / wave_sum(psum);
   __builtin_amdgcn_wave_barrier();
@@ -102,6 +114,24 @@ __global__ __launch_bounds__(256) void attention_cls_kernel(const float* __restr
 #pragma unroll
       for (int e = 0; e < 8; ++e) acc[db] = __builtin_fmaf(pr[e], (float)vv[e], acc[db]);
     }
+  }
+  if constexpr (LO) {  // the low plane's sum on its own (small terms together), added to the high plane's
+    float accl[8];
+#pragma unroll
+    for (int db = 0; db < 8; ++db) accl[db] = 0.f;
+    const half_t* vlb = vt_lo + (vb - vt);
+    for (int kb0 = 0; kb0 < S; kb0 += 64) {
+      const float4 p0 = *(const float4*)(pw + kb0 + 8 * c), p1 = *(const float4*)(pw + kb0 + 8 * c + 4);
+      const float pr[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+#pragma unroll
+      for (int db = 0; db < 8; ++db) {
+        const half8_t vv = *(const half8_t*)(vlb + (size_t)(8 * db) * S + kb0);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) accl[db] = __builtin_fmaf(pr[e], (float)vv[e], accl[db]);
+      }
+    }
+#pragma unroll
+    for (int db = 0; db < 8; ++db) acc[db] += accl[db];
   }
   float out = 0.f;
 #pragma unroll

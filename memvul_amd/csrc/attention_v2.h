@@ -1,4 +1,4 @@
-// Persistent self-attention for padded lengths S <= 256 (HF BertSelfAttention as invoked from
+// Persistent self-attention for padded lengths S <= 512 (HF BertSelfAttention as invoked from
 // custom_PTM_embedder.py:228): ctx = softmax(Q K^T / 8 + (1 - mask) * -10000) V.  Same HBM layouts as attention.h
 // (Q, K [B][12][S][64] fp16 with 1/8 folded into Q; V^T [B][12][64][S] fp16; ctx [B*S][768] fp16).
 //
@@ -36,14 +36,19 @@
 // AttnArgs::ctx8 — e4m3 of (O - fp16(O)) 2^(11 + s) and of O 2^s, the A8 operand of the output projection's correction sweep
 // (16 more registers across the unit boundary, a second pass through the O image); a separate instantiation.
 // (The timing ablations of rounds 1-2 — no Q loads / O stores / DMA / exp / MFMA / fragment reads — were retired: git history before round 5.)
-// VLO 1 (MV_F16X8, padded length <= 128: NKB <= 2, NCH = 1): Q, K, V and P as hi + lo fp16 — S^T += K_lo Q_hi + K_hi Q_lo, O^T += V_lo P_hi + V_hi P_lo on top
+// VLO 1 (MV_F16X8; default form: padded length <= 128, NKB <= 2, NCH = 1): Q, K, V and P as hi + lo fp16 — S^T += K_lo Q_hi + K_hi Q_lo, O^T += V_lo P_hi + V_hi P_lo on top
 // of the hi x hi products.  What is left of the precise mode's error is the fp16 storage of Q, K, V and P, averaged by attention over the keys:
 // ~ 1 / sqrt(keys), so short sequences feel it most (profiles/r05_f_length_envelope.txt: 9.4e-4 on the logits at 8 tokens against 2.3e-4 at 256) — and
 // there the second planes are nearly free: the lo planes of K and V^T (written by the QKV projection's epilogue, GemmArgs::k_lo / vt_lo) ride through the
 // ring next to K and V^T, Q's lo fragments are prefetched with Q's, P_lo = fp16(p - fp16(p)) is formed with the packing.
+// VLO 1 with NCH > 1 (the SAFE form of MV_F16X8, engine.hip mv_set_form: padded lengths 192 .. 512 as <1, 3>, <2, 2>, <2, 3>, <2, 4>): the same two planes through the chunked
+// ring — a slot holds one chunk's K, V^T, V^T_lo, K_lo (32 NKB KiB), the lo products go into the accumulators the hi products go into, so the chunk rescale
+// exp2(m_old - m_new) carries them along, and P_lo is formed per chunk from that chunk's p.  A 128 KiB ring leaves room for ONE 4-wave workgroup per CU, one wave
+// per SIMD, so these instantiations take the whole 512-register budget (amdgpu_waves_per_eu(1, 1): at (2, 2) they spill 160 - 190 VGPRs); every other
+// instantiation keeps (2, 2) and its code.
 template <int NKB, int NCH = 1, int X8 = 0, int VLO = 0>  // chunk = 64 NKB keys = 2 NKB waves x 32 queries; padded length S = 64 NKB NCH
-__global__ __launch_bounds__(NKB * 128) __attribute__((amdgpu_waves_per_eu(2, 2))) void attention_v2_kernel(AttnArgs a, int nunits) {
-  static_assert(!VLO || (X8 && NCH == 1 && NKB <= 2), "the two-plane V / P path serves the precise mode's short passes");
+__global__ __launch_bounds__(NKB * 128) __attribute__((amdgpu_waves_per_eu((VLO && NCH > 1) ? 1 : 2, (VLO && NCH > 1) ? 1 : 2))) void attention_v2_kernel(AttnArgs a, int nunits) {
+  static_assert(!VLO || (X8 && NKB <= 2), "the two-plane path: MV_F16X8, a ring slot of at most 64 KiB");
   constexpr int S = NKB * 64;        // keys per chunk = queries per unit
   constexpr int ST = S * NCH;        // padded sequence length (row pitch of V^T, rows per head of Q / K)
   constexpr int NT = 2 * NKB;        // 32-key score fragments per chunk

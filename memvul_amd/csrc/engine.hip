@@ -141,7 +141,7 @@ struct Work {
   int32_t *d_ids = nullptr, *d_lens = nullptr;  // host-path inputs
   float* xres = nullptr;                        // residual stream fp32 [T][768]
   half_t *x16 = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *ctx = nullptr, *h16 = nullptr;
-  half_t *vt_lo = nullptr, *q_lo = nullptr, *k_lo = nullptr;  // MV_F16X8, passes of padded length <= 128: second fp16 planes of V^T, Q, K (attention_v2.h VLO)
+  half_t *vt_lo = nullptr, *q_lo = nullptr, *k_lo = nullptr;  // MV_F16X8, passes of padded length <= 128 (the safe form: every pass): second fp16 planes of V^T, Q, K (attention_v2.h VLO)
   float *u = nullptr, *pooled = nullptr;
   float *logits = nullptr, *probs = nullptr, *psame = nullptr, *best = nullptr;
   int32_t* best_idx = nullptr;
@@ -238,6 +238,12 @@ struct mv_handle {
                            // ordinary row's Q rounding, like its K and V rounding, reaches the pooler only through attention, averaged over the keys (model: q / none / qkv
                            // within 7 % of each other, scripts/r06_qkv_model.py; GPU, 60 draws: +3 % error for +2.7 % issue reports/s, profiles/r06_m_*).  Rounds 4 - 6a: Q ("q").
                            // env MEMVUL_QKV_ASIDE = a subset of "qkv", "" or "none" ("qkv" = round 3's form)
+
+  int form = MV_FORM_DEFAULT;  // MV_F16X8, mv_set_form / env MEMVUL_FORM: MV_FORM_SAFE = the form that holds 1e-3 with an attention sink on an ORDINARY token too — both
+                           // first-order terms in every row of every GEMM (no [CLS]-row form, no row terms), the A-side term in all three QKV blocks, and Q, K, V, P as
+                           // hi + lo fp16 planes through attention at EVERY padded length (attention_v2.h VLO, NCH > 1 above 128) and through the pruned last layer's
+                           // single-query attention.  Read on the host when a pass is enqueued (encode_dev); cls_aside / cls_min_len / qkv_aside_mask / short_vlo do
+                           // not reach it (it is their most conservative setting by construction)
 
   // profiling
   uint32_t prof_mask = 0xffffffffu;  // kernel classes that get HIP events while profiling is on
@@ -452,8 +458,11 @@ int pool_head(mv_handle* h, Work& wk, const float* x, size_t row_stride, int B, 
 // padded sequence length of a pass: attention_v2 runs 64-key blocks up to 256 and 128-key chunks above
 inline int padded_len(int S_in) { return (int)round_up(S_in, S_in <= 256 ? 64 : 128); }
 
-int launch_attention(mv_handle* h, Work& wk, const int32_t* d_lens, int B, int Sp, bool x8, bool sp_out = false) {
-  const bool vlo = x8 && h->short_vlo && Sp <= 128;  // the QKV projection of this pass wrote V^T's lo plane (encode_dev: the same predicate)
+// the two-plane attention (attention_v2.h VLO) serves this pass: the QKV projection wrote the lo planes of Q, K, V^T (encode_dev: the same predicate)
+inline bool two_plane_pass(const mv_handle* h, bool x8, bool safe, int Sp) { return x8 && (safe || (h->short_vlo && Sp <= 128)); }
+
+int launch_attention(mv_handle* h, Work& wk, const int32_t* d_lens, int B, int Sp, bool x8, bool sp_out = false, bool safe = false) {
+  const bool vlo = two_plane_pass(h, x8, safe, Sp);
   AttnArgs a{wk.q, wk.k, wk.vt, d_lens, wk.ctx, Sp, B, x8 ? wk.ctx8 : nullptr, h->x8_sat, vlo ? wk.vt_lo : nullptr,
              vlo ? wk.q_lo : nullptr, vlo ? wk.k_lo : nullptr,
              (x8 && !vlo) ? wk.vlo_sp : nullptr,     // special rows: V of keys 0, 1 as hi + lo (the two-plane short passes carry every key's lo plane)
@@ -461,7 +470,20 @@ int launch_attention(mv_handle* h, Work& wk, const int32_t* d_lens, int B, int S
              sp_out ? h->cls_min_len : 0,               // [CLS]-row form: no lo8 plane of the context for the sequences that take it
              sp_out ? wk.cls_lo : nullptr};
   ProfScope ps(h, wk.stream, KC_ATTENTION);
-  if (vlo) {
+  if (vlo && Sp > 128) {
+    // the safe form above 128 keys: chunks through the two-plane ring.  192 = 3 chunks of 64 keys (2 waves, a 64 KiB ring: two workgroups per CU), 256 / 384 / 512 =
+    // 2 / 3 / 4 chunks of 128 (4 waves, a 128 KiB ring: one workgroup per CU) — one wave per SIMD either way
+    const int nch = Sp == 192 ? 3 : Sp / 128, units = B * MV_HEADS * nch;
+    const int slots = h->num_cu * (Sp == 192 ? 2 : 1);
+    const int grid = units < slots ? units : slots;
+    switch (Sp) {
+      case 192: hipLaunchKernelGGL((attention_v2_kernel<1, 3, 1, 1>), dim3(grid), dim3(128), ATT2_LDS_BYTES_VLO(1), wk.stream, a, units); break;
+      case 256: hipLaunchKernelGGL((attention_v2_kernel<2, 2, 1, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES_VLO(2), wk.stream, a, units); break;
+      case 384: hipLaunchKernelGGL((attention_v2_kernel<2, 3, 1, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES_VLO(2), wk.stream, a, units); break;
+      case 512: hipLaunchKernelGGL((attention_v2_kernel<2, 4, 1, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES_VLO(2), wk.stream, a, units); break;
+      default: return fail(h, MV_ERR_INVALID, "internal: attention at a padded length other than 64 .. 256 / 384 / 512");
+    }
+  } else if (vlo) {
     const int nkb = Sp / 64, items = B * MV_HEADS;
     const int slots = h->num_cu * (nkb == 1 ? 2 : 1);  // resident workgroups by LDS: 64 / 128 KiB each
     const int grid = items < slots ? items : slots;
@@ -527,7 +549,10 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
   // construction (ModelMemory.sweep / Engine.bucketed_sweep: a pass at 192 holds 129 .. 192 tokens, at 384 257 .. 384) — else the both-terms form for the whole pass.
   const bool one_seq_tiles = Sp == 256 || Sp == 512;
   const bool whole_pass = (Sp == 192 || Sp == 384) && min_len >= h->cls_min_len;
-  const bool cls_as = big && x8 && h->cls_aside && (one_seq_tiles || whole_pass);
+  const bool safe = x8 && h->form == MV_FORM_SAFE;  // (read HERE, when the pass is enqueued: work in flight keeps the form it was enqueued with)
+  const bool cls_as = big && x8 && !safe && h->cls_aside && (one_seq_tiles || whole_pass);
+  const int qkv_mask = safe ? 7 : h->qkv_aside_mask;
+  const bool two_plane = two_plane_pass(h, x8, safe, Sp);
   if (cls_as && one_seq_tiles) {
     const int ntile = (int)(Mpad / 256);
     hipLaunchKernelGGL(cls_tile_flags_kernel, dim3((unsigned)((ntile + 255) / 256)), dim3(256), 0, wk.stream, d_lens, B, Sp, h->cls_min_len, ntile,
@@ -597,14 +622,15 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
       g.col0 = MV_HIDDEN;
       if (big) {
         g.lnstats = st_in;
-        if (x8) { g.A8 = wk.x8; g.W8 = w.wqkv_f8 + (size_t)MV_HIDDEN * 2 * MV_HIDDEN; g.x8_scale = w.sc_qkv; g.x8_terms = 3; g.x8_aside_mask = h->qkv_aside_mask; }
+        if (x8) { g.A8 = wk.x8; g.W8 = w.wqkv_f8 + (size_t)MV_HIDDEN * 2 * MV_HIDDEN; g.x8_scale = w.sc_qkv; g.x8_terms = 3; g.x8_aside_mask = qkv_mask; }
         if (special) {  // K and V of the special rows: row term wherever a block sweeps the weight-side term only; V also as hi + lo (the [CLS] query itself is fp32: the tail below)
-          if ((h->qkv_aside_mask & 6) != 6) {
+          if ((qkv_mask & 6) != 6) {
             if (int rc = row_term(wk.st_lo, g.W, g.N, g.K)) return rc;
             g.cls_corr = wk.cls_corr;
           }
-          g.vlo_sp = (h->short_vlo && Sp <= 128) ? nullptr : wk.vlo_sp;
+          g.vlo_sp = two_plane ? nullptr : wk.vlo_sp;
         }
+        if (safe) { g.vt_lo = wk.vt_lo; g.q_lo = wk.q_lo; g.k_lo = wk.k_lo; }  // the single-query attention below reads K and V as hi + lo
         if (int rc = launch_pp<PP_QK>(h, wk.stream, KC_GEMM_KV_LAST, g)) return rc;
       } else if (int rc = launch_small<EPI_QKV>(h, wk.stream, KC_GEMM_KV_LAST, g)) return rc;
       ProfScope tail(h, wk.stream, KC_CLS_TAIL);
@@ -623,8 +649,12 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
           hipLaunchKernelGGL((dense768_kernel<2, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.c32,
                              (size_t)MV_HIDDEN, B, (const float*)w.wqT32, (const float*)w.bqkv, MV_HIDDEN, wk.cq, (const float*)nullptr);
           if (int rc = launch_check(h, "cls q")) return rc;
-          hipLaunchKernelGGL(attention_cls_kernel, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt,
-                             d_lens, wk.cctx, Sp, B * MV_HEADS, wk.pooled, (const half_t*)g.vlo_sp);
+          if (safe)
+            hipLaunchKernelGGL(attention_cls_kernel<true>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt, d_lens, wk.cctx, Sp,
+                               B * MV_HEADS, wk.pooled, (const half_t*)g.vlo_sp, (const half_t*)wk.k_lo, (const half_t*)wk.vt_lo);
+          else
+            hipLaunchKernelGGL(attention_cls_kernel<false>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt, d_lens, wk.cctx, Sp,
+                               B * MV_HEADS, wk.pooled, (const half_t*)g.vlo_sp, (const half_t*)nullptr, (const half_t*)nullptr);
           if (int rc = launch_check(h, "attention_cls")) return rc;
           hipLaunchKernelGGL((dense768_kernel<4, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.pooled,
                              (size_t)MV_HIDDEN, B, (const float*)w.woT32, (const float*)w.bo, MV_HIDDEN, wk.c32, (const float*)wk.c32);
@@ -643,8 +673,8 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
         t.M = Bp; t.Mreal = B; t.S = 64;
         t.A = wk.c16; t.W = w.wqkv; t.bias = w.bqkv; t.N = MV_HIDDEN; t.K = MV_HIDDEN; t.outf = wk.cq;
         if (int rc = launch_small<EPI_F32>(h, wk.stream, KC_CLS_TAIL, t)) return rc;
-        hipLaunchKernelGGL(attention_cls_kernel, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt,
-                           d_lens, wk.cctx, Sp, B * MV_HEADS);
+        hipLaunchKernelGGL(attention_cls_kernel<false>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt,
+                           d_lens, wk.cctx, Sp, B * MV_HEADS, (float*)nullptr, (const half_t*)nullptr, (const half_t*)nullptr, (const half_t*)nullptr);
         if (int rc = launch_check(h, "attention_cls")) return rc;
         t.A = wk.cctx; t.W = w.wo; t.bias = w.bo; t.N = MV_HIDDEN; t.K = MV_HIDDEN; t.xres = wk.c32; t.outf = nullptr;
         if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_CLS_TAIL, t)) return rc;
@@ -662,14 +692,14 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
     if (big) {
       // K2: Q, K, V^T projection of the raw stream (LayerNorm folded into W'' / b')
       g.A = wk.x16; g.W = wqkv; g.bias = bqkv; g.N = 3 * MV_HIDDEN; g.K = MV_HIDDEN; g.lnstats = st_in;
-      if (x8) { g.A8 = wk.x8; g.W8 = w.wqkv_f8; g.x8_scale = w.sc_qkv; g.x8_terms = 3; g.x8_aside_mask = h->qkv_aside_mask; }
-      g.vt_lo = (x8 && h->short_vlo && Sp <= 128) ? wk.vt_lo : nullptr;  // short passes: Q, K, V^T as hi + lo planes (launch_attention: the same predicate)
+      if (x8) { g.A8 = wk.x8; g.W8 = w.wqkv_f8; g.x8_scale = w.sc_qkv; g.x8_terms = 3; g.x8_aside_mask = qkv_mask; }
+      g.vt_lo = two_plane ? wk.vt_lo : nullptr;  // short passes (the safe form: every pass): Q, K, V^T as hi + lo planes (launch_attention: the same predicate)
       g.q_lo = wk.q_lo; g.k_lo = wk.k_lo;
       // x8_terms stays 3 — a block of x8_aside_mask (Q by default) keeps its A-side term for EVERY row; the other blocks take it for the special rows from
       // the row term (the launch skips it in blocks that swept both terms: gemm_pp.h).  With diffuse attention K and V of one token are one key among S for
       // every query and the term buys nothing (round 5: model, four draws); with an attention sink on that token they reach every row un-averaged.
       if (special) {
-        if (h->qkv_aside_mask != 7) {
+        if (qkv_mask != 7) {
           if (int rc = row_term(wk.st_lo, g.W, g.N, g.K)) return rc;
           g.cls_corr = wk.cls_corr;
         }
@@ -678,7 +708,7 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
       if (int rc = launch_pp<PP_QK>(h, wk.stream, KC_GEMM_QKV, g)) return rc;
       g.cls_corr = nullptr; g.vlo_sp = nullptr;
       // K3: attention (cls_as: + the context's special rows' low parts for the output projection's row term)
-      if (int rc = launch_attention(h, wk, d_lens, B, Sp, x8, cls_as)) return rc;
+      if (int rc = launch_attention(h, wk, d_lens, B, Sp, x8, cls_as, safe)) return rc;
       // K4: attention output projection + bias + LayerNorm(residual), in place on the raw stream; + vstats of the new rows
       g.A = wk.ctx; g.W = w.wo; g.bias = w.bo; g.N = MV_HIDDEN; g.K = MV_HIDDEN;
       g.lnstats = st_in; g.lng = pend_g; g.lnb = pend_b; g.lnpart = st_mid; g.out16 = wk.x16; g.out16b = wk.xlo;
@@ -1142,6 +1172,10 @@ int mv_create(int device, const mv_config* cfg, mv_handle** out) try {
 #undef MV_ATT_ATTR
   hipFuncSetAttribute((const void*)attention_v2_kernel<1, 1, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(1));
   hipFuncSetAttribute((const void*)attention_v2_kernel<2, 1, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(2));
+  hipFuncSetAttribute((const void*)attention_v2_kernel<1, 3, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(1));  // the safe form above 128 keys
+  hipFuncSetAttribute((const void*)attention_v2_kernel<2, 2, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(2));
+  hipFuncSetAttribute((const void*)attention_v2_kernel<2, 3, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(2));
+  hipFuncSetAttribute((const void*)attention_v2_kernel<2, 4, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(2));
   (void)hipGetLastError();
   if (!env_flag("MEMVUL_CLS_PRUNE", &h->cls_prune)) return MV_ERR_INVALID;
   if (const char* e = getenv("MEMVUL_QKV_ASIDE")) {
@@ -1159,6 +1193,14 @@ int mv_create(int device, const mv_config* cfg, mv_handle** out) try {
   }
   if (!env_flag("MEMVUL_CLS_ASIDE", &h->cls_aside)) return MV_ERR_INVALID;
   if (!env_int("MEMVUL_CLS_ASIDE_MIN_LEN", 1, 512, &h->cls_min_len)) return MV_ERR_INVALID;
+  if (const char* e = getenv("MEMVUL_FORM")) {  // the form of MV_F16X8 the handle starts in (mv_set_form changes it later); MV_F16 has none: mv_finalize_weights
+    if (!strcmp(e, "safe")) h->form = MV_FORM_SAFE;
+    else if (!strcmp(e, "default")) h->form = MV_FORM_DEFAULT;
+    else {
+      g_create_error = std::string("MEMVUL_FORM=\"") + e + "\": expected \"default\" or \"safe\"";
+      return MV_ERR_INVALID;
+    }
+  }
   {
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) h->num_cu = ncu;
@@ -1286,6 +1328,8 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
     return fail(h, MV_ERR_INVALID, "compute_dtype must be MV_F16 (fp16 MFMA operands, fp32 accumulation) or MV_F16X8 (+ fp8 correction "
                                    "sweeps); bf16 is a storage dtype of mv_load_tensor only (include/memvul_hip.h)");
   const bool precise = compute_dtype == MV_F16X8;
+  if (!precise && h->form == MV_FORM_SAFE)
+    return fail(h, MV_ERR_STATE, "the safe form (MEMVUL_FORM=safe / mv_set_form) is a form of compute dtype MV_F16X8: it cannot be combined with MV_F16");
   HIPCHK(h, hipSetDevice(h->device));
   const hipStream_t s0 = h->work[0].stream;  // (the uploads)
   const mv_config& c = h->cfg;
@@ -1444,11 +1488,10 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
       if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.st_lo, 2 * (int64_t)round_up(h->cfg.max_batch, 256) * MV_HIDDEN);
       if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.vlo_sp, (int64_t)h->cfg.max_batch * MV_HEADS * MV_HEAD_DIM * 2);
       if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.tile_both, h->cap_tokens / 256 + 1);
-      if (h->short_vlo) {  // second fp16 planes of V^T, Q, K: read only by passes of padded length <= 128 in this compute dtype (attention_v2.h VLO)
-        if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.vt_lo, h->cap_tokens * MV_HIDDEN);
-        if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.q_lo, h->cap_tokens * MV_HIDDEN);
-        if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.k_lo, h->cap_tokens * MV_HIDDEN);
-      }
+      // second fp16 planes of V^T, Q, K: read by passes of padded length <= 128 in the default form, by every pass in the safe form (attention_v2.h VLO)
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.vt_lo, h->cap_tokens * MV_HIDDEN);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.q_lo, h->cap_tokens * MV_HIDDEN);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.k_lo, h->cap_tokens * MV_HIDDEN);
       if (rc == MV_OK && hipStreamSynchronize(wk.stream) != hipSuccess) rc = MV_ERR_HIP;
       if (rc != MV_OK) return rc;
     }
@@ -1870,6 +1913,20 @@ int mv_set_streams(mv_handle* h, int n) try {
   return MV_OK;
 } catch (...) { return on_exception(h); }
 
+int mv_set_form(mv_handle* h, int form) try {
+  if (!h) return MV_ERR_INVALID;
+  if (form != MV_FORM_DEFAULT && form != MV_FORM_SAFE) return fail(h, MV_ERR_INVALID, "mv_set_form: MV_FORM_DEFAULT (0) or MV_FORM_SAFE (1)");
+  if (form == MV_FORM_SAFE && h->finalized && !h->precise)
+    return fail(h, MV_ERR_STATE, "mv_set_form: MV_FORM_SAFE is a form of compute dtype MV_F16X8; this handle was finalized as MV_F16");
+  h->form = form;  // (no synchronisation: passes already enqueued were built with the form of their time)
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+int mv_get_form(mv_handle* h) try {
+  if (!h) return MV_ERR_INVALID;
+  return h->form;
+} catch (...) { return on_exception(h); }
+
 int mv_x8_saturation(mv_handle* h, int64_t* clamped, int reset) try {
   if (!h || !clamped) return fail(h, MV_ERR_INVALID, "mv_x8_saturation: bad argument");
   HIPCHK(h, hipSetDevice(h->device));
@@ -1940,9 +1997,13 @@ int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes) try {
     case 4: src = wk.vt; avail = T * MV_HIDDEN * 2; break;
     case 5: src = wk.ctx; avail = T * MV_HIDDEN * 2; break;
     case 6: src = wk.h16; avail = T * MV_INTER * 2; break;
-    case 7: src = wk.u; avail = (int64_t)h->dbg_B * h->P * 4; break;
+    case 7: src = wk.q_lo; avail = T * MV_HIDDEN * 2; break;
+    case 8: src = wk.k_lo; avail = T * MV_HIDDEN * 2; break;
+    case 9: src = wk.vt_lo; avail = T * MV_HIDDEN * 2; break;
+    case 10: src = wk.u; avail = (int64_t)h->dbg_B * h->P * 4; break;
     default: return fail(h, MV_ERR_INVALID, "mv_debug_read: unknown buffer");
   }
+  if (!src) return fail(h, MV_ERR_STATE, "mv_debug_read: this buffer does not exist in this compute dtype");
   if (bytes > avail) return fail(h, MV_ERR_INVALID, "mv_debug_read: more bytes requested than the buffer holds");
   HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, wk.stream));
   HIPCHK(h, hipStreamSynchronize(wk.stream));
