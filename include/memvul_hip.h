@@ -86,7 +86,8 @@ typedef struct mv_config {
  *                             rows get it in every block either way; "q" = the default of rounds 4 - 6a: -2.7 % issue reports/s, 3 % less logit error).
  *   MEMVUL_CLS_PRUNE          1 (default) | 0: after the last layer's K / V projection only the [CLS] rows are processed.
  *   MEMVUL_STREAMS            2 (default) | 1: batches of the resident sweep in flight (mv_set_streams changes it later).
- *   MEMVUL_FORM               default | safe: the form of MV_F16X8 the handle starts in (mv_set_form changes it later).  "safe" with mv_finalize_weights(MV_F16) fails.
+ *   MEMVUL_FORM               default | safe | guarded: the form of MV_F16X8 the handle starts in (mv_set_form changes it later).  "safe" and "guarded" with
+ *                             mv_finalize_weights(MV_F16) fail.
  *                             In the safe form MEMVUL_CLS_ASIDE, MEMVUL_CLS_ASIDE_MIN_LEN and MEMVUL_QKV_ASIDE have no effect (it is their most conservative setting).
  * (The seventh switch of the product, MEMVUL_COMPUTE = precise | f16, is read by the Python surface: memvul_amd/binding.py default_compute.)
  * Development A/B knobs (kernel path forced at test sizes, raster, grid share, one-plane short passes) exist only in the -DMEMVUL_DEV_SWITCHES build
@@ -117,7 +118,7 @@ int mv_load_tensor(mv_handle* h, const char* name, const void* host_ptr, int dty
  * same MFMA rate as fp16.  Embeddings, LayerNorm, biases, pooler, header and matcher stay fp32. */
 int mv_finalize_weights(mv_handle* h, int compute_dtype);
 
-/* The two forms of compute dtype MV_F16X8: same weights, same planes, same handle; only the per-pass choices differ.
+/* The three forms of compute dtype MV_F16X8: same weights, same planes, same handle; only the per-pass choices differ.
  *   MV_FORM_DEFAULT  what bench.py's headline is measured in: the [CLS]-row form, the special rows, two fp16 planes through attention up to 128 keys.  Holds 1e-3
  *                    on the logits for diffuse attention and for attention sinks on [CLS] / [SEP].
  *   MV_FORM_SAFE     the form for models whose heads park most of their mass on an ORDINARY token (mv_attention_concentration reports them), where the default reads
@@ -126,12 +127,31 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype);
  *                    fp16 storage is what is left otherwise) and through the single-query attention of the pruned last layer.  It costs the GEMMs their A-side sweep
  *                    in every row and attention three times the MFMAs, twice the K / V bytes and one wave per SIMD above 128 keys; rate and error envelope as
  *                    measured: DESIGN.md section 2, profiles/LEDGER.md.
- * mv_set_form: MV_FORM_SAFE on a handle finalized as MV_F16 -> MV_ERR_STATE, an unknown value -> MV_ERR_INVALID.  The form of a pass is read on the host when the
- * pass is enqueued: work already in flight keeps the form it was enqueued with.  mv_get_form returns the current form. */
+ *   MV_FORM_GUARDED  the choice between the two made per SEQUENCE: every sequence the handle encodes — issue report or anchor — runs in the default form with the
+ *                    concentration monitor also counting per sequence; a sequence with more than 2 % of its own monitored (head, layer) items above a collision mass of
+ *                    0.25 (mv_attention_concentration; a sequence of fewer than 16 tokens has no items) is encoded AGAIN in the safe form, at the width of the pass it
+ *                    first ran in, and only its results are replaced: it gets the bits a safe-form handle gives it through the same call, every other sequence the
+ *                    bits of the default form.  mv_forward / mv_forward_ragged / mv_encode / mv_anchor_append rescore before they return, mv_forward_ragged_end
+ *                    rescores the batch its ticket was started with (the form is the one in force at `begin`), the resident sweep records the counts while it runs
+ *                    and rescores everything swept since, in full batches, before mv_corpus_results copies anything.  The rescoring passes leave the global
+ *                    counters of mv_attention_concentration alone (a sequence is counted once).  Costs the default form's rate times (1 + 1.34 f) at a flagged
+ *                    share f: above f ~ 0.25 the safe form is the cheaper one.  mv_debug_encode ignores it (taps show the default form).
+ * mv_set_form: MV_FORM_SAFE / MV_FORM_GUARDED on a handle finalized as MV_F16 -> MV_ERR_STATE, an unknown value -> MV_ERR_INVALID.  The form of a pass is read on the
+ * host when the pass is enqueued: work already in flight keeps the form it was enqueued with.  mv_get_form returns the current form. */
 #define MV_FORM_DEFAULT 0
 #define MV_FORM_SAFE 1
+#define MV_FORM_GUARDED 2
 int mv_set_form(mv_handle* h, int form);
 int mv_get_form(mv_handle* h);
+/* MV_FORM_GUARDED: *sequences = the sequences encoded in the guarded form since the handle was created (or the last reset), *rescored = how many of them were
+ * encoded again in the safe form (corpus rows count as rescored once mv_corpus_results has run their rescoring). */
+int mv_form_stats(mv_handle* h, int64_t* sequences, int64_t* rescored, int reset);
+/* The form (MV_FORM_DEFAULT / MV_FORM_SAFE) that produced each row of the last mv_forward / mv_forward_ragged / mv_forward_ragged_end / mv_encode /
+ * mv_anchor_append, in the caller's row order; n = that call's row count (anything else -> MV_ERR_INVALID).  Outside the guarded form every row reads the
+ * handle's form. */
+int mv_last_row_forms(mv_handle* h, uint8_t* forms, int n);
+/* The same for rows [first, first + count) of the resident corpus: valid after mv_corpus_results (rows never swept read MV_FORM_DEFAULT). */
+int mv_corpus_row_forms(mv_handle* h, int64_t first, int64_t count, uint8_t* forms);
 
 /* ---- anchor memory (replaces ModelMemory.forward_gold_instances, model_memory.py:105-115, as
  *      driven by predict_memory.py:81-83 and callbacks.py:48-53) ------------------------------ */
@@ -221,7 +241,7 @@ int mv_x8_saturation(mv_handle* h, int64_t* clamped, int reset);
  * of sum_{j >= 2} p[CLS row][j]^2 (>= f^2 when one ordinary token holds the share f), *items_over = how many of them exceeded 0.25 (f > 0.5) and *items_total = how
  * many were looked at (sequences of at least 16 tokens); synchronises.  The Python wrapper warns once when more than 2 % of the items are over (binding.Engine).
  * The answer to a non-zero count is the safe form (mv_set_form(MV_FORM_SAFE) / MEMVUL_FORM=safe; the Python surface switches by itself under MEMVUL_ON_SINK=safe);
- * the safe form keeps counting, with the same meaning.
+ * the safe form keeps counting, with the same meaning.  MV_FORM_GUARDED makes that choice per sequence from the same items (mv_set_form).
  * No reference counterpart (the reference computes in fp32). */
 int mv_attention_concentration(mv_handle* h, float* max_collision, int64_t* items_over, int64_t* items_total, int reset);
 
@@ -270,7 +290,8 @@ const char* mv_kernel_class_name(int cls);
  * <= 128 in the default form, every pass in the safe form); 10 the embedding fp32 [B, proj_dim] of a full run.
  * (Sp = S rounded up to a multiple of 64, above 256 to a multiple of 128; buffers hold the state of the LAST executed layer; Q carries
  * the folded 1/8.  The pass takes the path its size selects — persistent kernels or the small-pass kernels — with last-layer pruning
- * off and the final LayerNorm applied, so buffer 0 is the normalised output of layer n_layers.) */
+ * off and the final LayerNorm applied, so buffer 0 is the normalised output of layer n_layers.  MV_FORM_GUARDED is ignored here: the taps show the default
+ * form, nothing is rescored.) */
 int mv_debug_encode(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int n_layers);
 int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes);
 /* Stand-alone GEMM check/bench on caller data: C[M,N] = A[M,K] (fp16 bits) x W[N,K]^T (fp16 bits)

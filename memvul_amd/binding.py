@@ -19,11 +19,15 @@ DEV_SWITCHES = ("MEMVUL_GEMM_TILE", "MEMVUL_SHORT_VLO", "MEMVUL_RASTER", "MEMVUL
 
 MV_F32, MV_F16, MV_BF16, MV_I32, MV_I64 = 0, 1, 2, 3, 4
 MV_F16X8 = 6  # compute dtype only ("precise"): fp16 MFMA sweep + one fp8 (e4m3) correction sweep per GEMM (include/memvul_hip.h)
-COMPUTE_DTYPES = {"f16": MV_F16, "fast": MV_F16, "f16x8": MV_F16X8, "precise": MV_F16X8, "safe": MV_F16X8}
-# the two forms of MV_F16X8 (include/memvul_hip.h mv_set_form).  "safe" as a compute dtype name = MV_F16X8 + the safe form set after finalize: both first-order
+COMPUTE_DTYPES = {"f16": MV_F16, "fast": MV_F16, "f16x8": MV_F16X8, "precise": MV_F16X8, "safe": MV_F16X8, "guarded": MV_F16X8}
+# the three forms of MV_F16X8 (include/memvul_hip.h mv_set_form).  "safe" as a compute dtype name = MV_F16X8 + the safe form set after finalize: both first-order
 # correction terms in every row and two fp16 planes through attention at every length — the form that holds 1e-3 with an attention sink on an ordinary token
-MV_FORM_DEFAULT, MV_FORM_SAFE = 0, 1
-FORMS = {"default": MV_FORM_DEFAULT, "safe": MV_FORM_SAFE}
+# ("guarded" likewise: the default form, and the safe form again for the sequences whose own monitor items report an ordinary-token sink)
+MV_FORM_DEFAULT, MV_FORM_SAFE, MV_FORM_GUARDED = 0, 1, 2
+FORMS = {"default": MV_FORM_DEFAULT, "safe": MV_FORM_SAFE, "guarded": MV_FORM_GUARDED}
+# the guarded form costs the default form's time x (1 + 1.34 f) at a rescored share f (14.65 / 10.95 k issue reports/s: DESIGN.md section 2): above this share
+# the safe form is the cheaper one, and Engine says so once
+GUARDED_WARN_SHARE = 0.25
 # The product's default is the compute dtype that holds the reference's 1e-3 logit tolerance on trained-like weights
 # (model_memory.py:133-147 at config_memory.json:38's temperature): MV_F16X8.  MV_F16 ("fast") is an explicit opt-in:
 # ~1.7x the rate, logits within 1e-3 only on small-logit models (measured 3.0-5.6e-3 at |logit| ~ 3).
@@ -31,7 +35,7 @@ DEFAULT_COMPUTE = "precise"
 
 
 def default_compute() -> str:
-    """$MEMVUL_COMPUTE (f16 | fast | f16x8 | precise | safe) or the contract-holding default."""
+    """$MEMVUL_COMPUTE (f16 | fast | f16x8 | precise | safe | guarded) or the contract-holding default."""
     return os.environ.get("MEMVUL_COMPUTE", DEFAULT_COMPUTE)
 
 
@@ -60,9 +64,16 @@ def on_sink_policy() -> str:
 
 def wants_safe_form(name_or_code) -> bool:
     """True when the compute dtype asked for (None = default_compute()) is the name "safe": MV_F16X8 in the safe form."""
+    return wanted_form(name_or_code) == "safe"
+
+
+def wanted_form(name_or_code) -> Optional[str]:
+    """The form a compute dtype NAME stands for ("safe" / "guarded": MV_F16X8 in that form), None for every other name or code."""
     if name_or_code is None:
         name_or_code = default_compute()
-    return isinstance(name_or_code, str) and name_or_code.lower() == "safe"
+    if isinstance(name_or_code, str) and name_or_code.lower() in ("safe", "guarded"):
+        return name_or_code.lower()
+    return None
 
 
 NUM_KERNEL_CLASSES = 14
@@ -72,7 +83,7 @@ ABI_SYMBOLS = [
     "mv_create", "mv_destroy", "mv_last_error", "mv_sync", "mv_load_tensor", "mv_finalize_weights",
     "mv_anchor_reset", "mv_anchor_append", "mv_anchor_count", "mv_anchor_get", "mv_anchor_set",
     "mv_forward", "mv_forward_ragged", "mv_forward_ragged_begin", "mv_forward_ragged_end", "mv_encode", "mv_match", "mv_topk", "mv_corpus_upload", "mv_corpus_run", "mv_corpus_run_len",
-    "mv_corpus_results", "mv_x8_saturation", "mv_attention_concentration", "mv_set_form", "mv_get_form", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
+    "mv_corpus_results", "mv_x8_saturation", "mv_attention_concentration", "mv_set_form", "mv_get_form", "mv_form_stats", "mv_last_row_forms", "mv_corpus_row_forms", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
     "mv_debug_encode", "mv_debug_read", "mv_test_gemm", "mv_test_gemm_pp", "mv_test_e4m3", "mv_format_records", "mv_comm_prepare", "mv_comm_unique_id", "mv_comm_init", "mv_comm_allgather",
     "mv_comm_destroy", "mv_comm_info", "mv_device_count",
 ]
@@ -137,6 +148,9 @@ def load_library(path: Optional[str] = None, dev: bool = False):
         "mv_set_streams": (C.c_int, [vp, C.c_int]),
         "mv_set_form": (C.c_int, [vp, C.c_int]),
         "mv_get_form": (C.c_int, [vp]),
+        "mv_form_stats": (C.c_int, [vp, P(C.c_int64), P(C.c_int64), C.c_int]),
+        "mv_last_row_forms": (C.c_int, [vp, vp, C.c_int]),
+        "mv_corpus_row_forms": (C.c_int, [vp, C.c_int64, C.c_int64, vp]),
         "mv_profile_enable": (C.c_int, [vp, C.c_int]),
         "mv_profile_select": (C.c_int, [vp, C.c_uint32]),
         "mv_profile_read": (C.c_int, [vp, P(C.c_double), P(C.c_int64), C.c_int]),
@@ -215,6 +229,8 @@ class Engine:
         self._anchor_log = []        # the (ids, lens) of every anchor_append since the last reset: what a switch of form re-encodes the bank from
         self._bank_replayable = True  # False once anchor_set installed embeddings the binding cannot re-encode
         self._corpus_runs = []       # the corpus_run calls since the last corpus_upload: what a switch of form sweeps once more
+        self._guard_warned = False   # the guarded form's one warning (more than GUARDED_WARN_SHARE of the sequences rescored)
+        self._last_rows = 0          # rows of the last call last_row_forms() speaks of
 
     # -- plumbing
     def _check(self, rc: int, what: str):
@@ -259,12 +275,12 @@ class Engine:
         self._check(self._lib.mv_finalize_weights(self._h, compute_dtype_of(compute_dtype)), "mv_finalize_weights")
         self._precise = compute_dtype_of(compute_dtype) == MV_F16X8
         self._sat_warned = False
-        if wants_safe_form(compute_dtype):
-            self.set_form("safe")
+        if wanted_form(compute_dtype):
+            self.set_form(wanted_form(compute_dtype))
         else:
-            self._form = "safe" if self._get_form() == MV_FORM_SAFE else "default"  # (MEMVUL_FORM, read by mv_create)
+            self._form = {v: k for k, v in FORMS.items()}.get(self._get_form(), "default")  # (MEMVUL_FORM, read by mv_create)
 
-    # -- the two forms of MV_F16X8
+    # -- the three forms of MV_F16X8
     def _get_form(self) -> int:
         return int(self._lib.mv_get_form(self._h))
 
@@ -273,15 +289,37 @@ class Engine:
 
     @property
     def form(self) -> str:
-        """"default" or "safe" (include/memvul_hip.h mv_set_form)."""
+        """"default", "safe" or "guarded" (include/memvul_hip.h mv_set_form)."""
         return self._form
 
     def set_form(self, form: str):
-        """The form the passes enqueued from now on run in: "default" | "safe" (work in flight keeps its own).  "safe" on an MV_F16 engine raises."""
+        """The form the passes enqueued from now on run in: "default" | "safe" | "guarded" (work in flight keeps its own).  "safe" and "guarded" on an MV_F16
+        engine raise."""
         if form not in FORMS:
             raise ValueError(f"unknown form {form!r}: expected one of {sorted(FORMS)}")
         self._set_form(FORMS[form])
         self._form = form
+
+    def form_stats(self, reset: bool = False):
+        """(sequences, rescored) of mv_form_stats: the sequences encoded in the guarded form so far and how many of them were encoded again in the safe form."""
+        n, r = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.quick.mv_form_stats(self._h, C.byref(n), C.byref(r), int(bool(reset))), "mv_form_stats")
+        return int(n.value), int(r.value)
+
+    def last_row_forms(self) -> list:
+        """The form ("default" / "safe") that produced each row of the last forward / forward_by_length / forward_by_length_end / encode / anchor_append, in
+        that call's row order (mv_last_row_forms)."""
+        n = self._last_rows
+        f = np.empty((n,), np.uint8)
+        self._check(self._lib.mv_last_row_forms(self._h, _ptr(f), n), "mv_last_row_forms")
+        return ["safe" if x == MV_FORM_SAFE else "default" for x in f]
+
+    def corpus_row_forms(self, first: int, count: int) -> list:
+        """The same for rows [first, first + count) of the resident corpus, valid after corpus_results (mv_corpus_row_forms).  After bucketed_sweep the rows are
+        those of the length-sorted upload: ``np.argsort(lens, kind="stable")``."""
+        f = np.empty((count,), np.uint8)
+        self._check(self._lib.mv_corpus_row_forms(self._h, first, count, _ptr(f)), "mv_corpus_row_forms")
+        return ["safe" if x == MV_FORM_SAFE else "default" for x in f]
 
     def x8_saturation(self, reset: bool = False) -> int:
         """MV_F16X8: activation elements (raw stream, attention context, GELU output) that fell outside the +-112 range of the fp8
@@ -303,7 +341,7 @@ class Engine:
         """Called after the host-synchronous entry points of the precise mode: warn ONCE when the fp8 planes clamped anything, and once when the concentration
         monitor trips.  Returns True when that trip switched the engine to the safe form (MEMVUL_ON_SINK=safe): the caller redoes its call."""
         switched = False
-        if getattr(self, "_precise", False) and not getattr(self, "_conc_warned", False) and self._form != "safe":  # (the safe form keeps counting, trips nothing)
+        if getattr(self, "_precise", False) and not getattr(self, "_conc_warned", False) and self._form == "default":  # (the safe form keeps counting, trips nothing; the guarded form answers per sequence)
             m, n, t = self.attention_concentration()
             if t >= 100 and n > 0.02 * t and self._on_sink == "safe":
                 self._conc_warned = True
@@ -316,6 +354,13 @@ class Engine:
                               "for attention sinks on [CLS] / [SEP] only (profiles/r06_n_sink_envelope.txt: 0.8 - 2.7e-3 for such a sink); "
                               "MEMVUL_CLS_ASIDE=0 MEMVUL_QKV_ASIDE=qkv is the most conservative form (include/memvul_hip.h mv_attention_concentration)",
                               RuntimeWarning, stacklevel=3)
+        if getattr(self, "_precise", False) and self._form == "guarded" and not self._guard_warned:
+            seqs, resc = self.form_stats()
+            if seqs >= 100 and resc > GUARDED_WARN_SHARE * seqs:
+                self._guard_warned = True
+                warnings.warn(f"MV_F16X8, guarded form: {resc} of {seqs} sequences were encoded again in the safe form — above a share of {GUARDED_WARN_SHARE} the safe "
+                              "form (compute dtype \"safe\" / set_form(\"safe\") / MEMVUL_FORM=safe) scores the same corpus faster: a guarded sequence costs "
+                              "1 + 1.34 x that share of a default-form one, a safe-form one 1.34 (include/memvul_hip.h mv_set_form)", RuntimeWarning, stacklevel=3)
         if getattr(self, "_precise", False) and not self._sat_warned:
             n = self.x8_saturation()
             if n:
@@ -359,6 +404,7 @@ class Engine:
     def anchor_append(self, ids: np.ndarray, lens: np.ndarray):
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         self._anchor_append(ids, lens)
+        self._last_rows = ids.shape[0]
         if self._on_sink == "safe" and not getattr(self, "_conc_warned", False):  # (kept only while a switch of form may still need them)
             self._anchor_log.append((ids.copy(), lens.copy()))
         self._check_saturation()  # (a trip here encodes the whole bank again, these anchors included)
@@ -389,6 +435,7 @@ class Engine:
         out = _outputs(B, self.n_anchors, self.P, want_logits, want_probs, want_embed)
         self._check(self._lib.mv_forward(self._h, _ptr(ids), _ptr(lens), B, S, _ptr(out["logits"]), _ptr(out["probs"]), _ptr(out["best"]),
                                          _ptr(out["best_idx"]), _ptr(out["embed"])), "mv_forward")
+        self._last_rows = B
         if self._check_saturation():
             return self.forward(ids, lens, want_logits, want_probs, want_embed)
         return out
@@ -412,6 +459,7 @@ class Engine:
         out = _outputs(B, self.n_anchors, self.P, want_logits, want_probs, want_embed)
         self._check(self._lib.mv_forward_ragged(self._h, _ptr(ids), _ptr(lens), B, S, int(min_tokens), _ptr(out["logits"]), _ptr(out["probs"]),
                                                 _ptr(out["best"]), _ptr(out["best_idx"]), _ptr(out["embed"])), "mv_forward_ragged")
+        self._last_rows = B
         if self._check_saturation():
             return self.forward_by_length(ids, lens, want_logits, want_probs, want_embed, min_tokens)
         return out
@@ -425,7 +473,7 @@ class Engine:
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         B, S = ids.shape
         mt = self.BY_LENGTH_MIN_TOKENS if min_tokens is None else min_tokens
-        redo = (self._form, ids, lens, bool(want_logits), bool(want_probs), bool(want_embed), min_tokens) if self._on_sink == "safe" and self._form != "safe" else None
+        redo = (self._form, ids, lens, bool(want_logits), bool(want_probs), bool(want_embed), min_tokens) if self._on_sink == "safe" and self._form == "default" else None
         if B > 0 and B * S >= 2 * mt:
             t = C.c_int(-1)
             rc = self._lib.mv_forward_ragged_begin(self._h, _ptr(ids), _ptr(lens), B, S, int(mt), int(want_logits), int(want_probs), int(want_embed), C.byref(t))
@@ -455,6 +503,7 @@ class Engine:
         self._tickets.pop(0)
         self._check(self._lib.mv_forward_ragged_end(self._h, t, _ptr(out["logits"]), _ptr(out["probs"]), _ptr(out["best"]), _ptr(out["best_idx"]), _ptr(out["embed"])),
                     "mv_forward_ragged_end")
+        self._last_rows = B
         stale = redo is not None and self._form == "safe"  # begun before the switch: its results are the default form's
         if not self._tickets or (redo is not None and not stale):  # (the counters are read after a synchronisation of EVERY stream: with the next batch in flight that would wait for it — holding the lock)
             stale = self._check_saturation() or stale
@@ -464,6 +513,7 @@ class Engine:
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         out = np.empty((ids.shape[0], self.P), np.float32)
         self._check(self._lib.mv_encode(self._h, _ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1], _ptr(out)), "mv_encode")
+        self._last_rows = ids.shape[0]
         if self._check_saturation():
             return self.encode(ids, lens)
         return out
@@ -498,7 +548,7 @@ class Engine:
         """Enqueue IRs [first, first+count) of the resident corpus in batches of `batch` (asynchronous).  s_eff > 0:
         process only the first s_eff tokens of each row (length-bucketed sweeps, see bucketed_sweep)."""
         self._check(self._lib.mv_corpus_run_len(self._h, first, count, batch, int(keep_probs), int(s_eff)), "mv_corpus_run_len")
-        if self._on_sink == "safe" and self._form != "safe":
+        if self._on_sink == "safe" and self._form == "default":
             self._corpus_runs.append((first, count, batch, keep_probs, s_eff))
 
     def bucketed_sweep(self, ids: np.ndarray, lens: np.ndarray, batch: int, with_probs: bool = False):

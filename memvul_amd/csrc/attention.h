@@ -31,7 +31,10 @@ struct AttnArgs {
   int lo8_min_len;       // X8: sequences of at least this many tokens get the hi8 plane of ctx8 alone (0: every sequence gets both planes): in the [CLS]-row form the
                          // output projection sweeps the weight-side term only and never reads a long sequence's lo8 plane (50 MB of 201 MB the launch writes)
   half_t* sp_lo_out;     // 2^11 x the low parts of the CONTEXT of those two rows, compact [2 b + row][768] fp16: the A operand of the output projection's row term
+  uint32_t* seq_over;    // X8, with conc (the guarded form, engine.hip): [B of the pass] — every item that adds 1 to conc[1] also adds 1 to its own sequence's slot (NULL: not kept)
 };
+// the collision mass of the [CLS] row on ordinary keys above which a (sequence, head, layer) item counts as an ordinary-token sink (conc[1], seq_over)
+#define MV_SINK_COLLISION 0.25f
 
 // Last encoder layer: only the [CLS] query (token 0) of each issue report is consumed downstream
 // (BertPooler takes hidden[:, 0], model_memory.py:99), so its attention is one query row per (batch row, head):

@@ -149,6 +149,19 @@ __global__ __launch_bounds__(NKB * 128) __attribute__((amdgpu_waves_per_eu((VLO 
   const uint32_t o_wr = (uint32_t)((32 * wave + ql) * 128 + 8 * hi);
   const uint32_t o_rd = (uint32_t)((32 * wave + (lane >> 3)) * 128 + (((lane & 7) ^ (lane >> 3)) << 4));
 
+  // AttnArgs::seq_over, for the one lane that found an item over the threshold.  Everything here lives in VECTOR registers inside that rare branch — the pointer
+  // is read from the kernel's argument block through a per-lane address, the sequence index is formed from a per-lane copy of the unit: as one more scalar
+  // register pair held across the kernel (like the other arguments) it cost the <2, 4, 1, 0> instantiation two spilled SGPRs and with them one more
+  // spilled VGPR (124 -> 128 B of scratch)
+  auto seq_over_add = [&](int u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    int uv = u, z = 0;
+    asm volatile("" : "+v"(uv), "+v"(z));
+    const char* kp = (const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(AttnArgs, seq_over) + z;  // (`a` is the kernel's first argument)
+    uint32_t* so = *(uint32_t* const*)kp;
+    if (so) atomicAdd(so + unit_bh(uv) / MV_HEADS, 1u);
+#endif
+  };
   const int first = blockIdx.x, stride = gridDim.x;
   if (first >= nunits) return;
   half8_t qf[4], qn[4];
@@ -371,7 +384,10 @@ __global__ __launch_bounds__(NKB * 128) __attribute__((amdgpu_waves_per_eu((VLO 
             const float coll = (u2f(cs[0]) + u2f(cs[1])) * linv * linv;
             if (lane == 0 && len >= 16) {  // query 0 of the sequence (a sequence of a handful of tokens concentrates by construction: not what is looked for)
               atomicMax(a.conc, (unsigned long long)f2u(fmaxf(coll, 0.f)));
-              if (coll > 0.25f) atomicAdd(a.conc + 1, 1ull);
+              if (coll > MV_SINK_COLLISION) {
+                atomicAdd(a.conc + 1, 1ull);
+                seq_over_add(unit);
+              }
               atomicAdd(a.conc + 2, 1ull);
             }
           } else {
@@ -461,7 +477,10 @@ __global__ __launch_bounds__(NKB * 128) __attribute__((amdgpu_waves_per_eu((VLO 
             const float coll = (u2f(cs[0]) + u2f(cs[1])) * inv * inv;
             if (lane == 0 && len >= 16) {  // query 0 of the sequence (a sequence of a handful of tokens concentrates by construction: not what is looked for)
               atomicMax(a.conc, (unsigned long long)f2u(fmaxf(coll, 0.f)));
-              if (coll > 0.25f) atomicAdd(a.conc + 1, 1ull);
+              if (coll > MV_SINK_COLLISION) {
+                atomicAdd(a.conc + 1, 1ull);
+                seq_over_add(unit);
+              }
               atomicAdd(a.conc + 2, 1ull);
             }
           }

@@ -121,6 +121,7 @@ struct ProfRec {
 struct Stage {
   int32_t *ids = nullptr, *lens = nullptr, *idx = nullptr;
   float *logits = nullptr, *probs = nullptr, *best = nullptr, *embed = nullptr;
+  uint32_t* over = nullptr;  // the guarded form: per row, the monitor items over MV_SINK_COLLISION (AttnArgs::seq_over)
 };
 
 // How a batch runs: its row order (plan row i = caller row order[i]; empty = the identity) and its passes, each rows [first, first + rows) of that order
@@ -139,6 +140,8 @@ struct Plan {
 struct Work {
   hipStream_t stream = nullptr;
   int32_t *d_ids = nullptr, *d_lens = nullptr;  // host-path inputs
+  uint32_t* seq_over = nullptr;                 // the guarded form: AttnArgs::seq_over of the passes of a host batch [max_batch]
+  int32_t* d_idx = nullptr;                     // ... and the corpus rows of one rescoring pass of the resident sweep [max_batch] (corpus_gather_kernel)
   float* xres = nullptr;                        // residual stream fp32 [T][768]
   half_t *x16 = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *ctx = nullptr, *h16 = nullptr;
   half_t *vt_lo = nullptr, *q_lo = nullptr, *k_lo = nullptr;  // MV_F16X8, passes of padded length <= 128 (the safe form: every pass): second fp16 planes of V^T, Q, K (attention_v2.h VLO)
@@ -168,6 +171,7 @@ struct Work {
   // in flight on this stream: batches of a resident sweep (check_ready waits for them) and / or a ticket of mv_forward_ragged_begin — its plan, anchor
   // count and staging `st`: `pin` (PINNED, allocated at the set's first ticket) without the outputs it was not asked for
   bool sweep = false, ticket = false;
+  bool guard = false, safe = false;  // the form the ticket was started in: mv_forward_ragged_end rescores the flagged rows of a guarded one
   Plan plan;
   int G = 0;
   Stage pin, st;
@@ -203,7 +207,11 @@ struct mv_handle {
   struct {
     std::vector<int32_t> ids, lens, idx;
     std::vector<float> logits, probs, best, embed;
-  } stage;
+    std::vector<uint32_t> over;
+  } stage, stage2;         // stage2 / plan2: the guarded form's rescoring batch (the flagged rows of the batch just run, in plan order)
+  Plan plan2;
+  std::vector<uint8_t> last_forms;             // mv_last_row_forms: the form that produced each row of the last host-buffer call, caller's row order
+  int64_t guard_seqs = 0, guard_rescored = 0;  // mv_form_stats
   float* anchors = nullptr;
   int n_anchors = 0;
   unsigned long long* attn_conc = nullptr;  // MV_F16X8: [0] max collision mass of the [CLS] row on ordinary keys (float bits), [1] items above 0.25 (AttnArgs::conc)
@@ -220,6 +228,13 @@ struct mv_handle {
   float* c_psame = nullptr;
   int64_t c_psame_rows = 0;
   int c_G = 0;
+  // the guarded form on the resident corpus: the sweep records the per-row monitor counts and which rows it ran at which width; rescore_corpus (mv_corpus_results)
+  // encodes the flagged ones again
+  uint32_t* c_over = nullptr;           // [c_n] AttnArgs::seq_over of the row's last guarded run
+  std::vector<int16_t> c_pend_w;        // [c_n] the width (s_eff) of the row's guarded run not yet rescored; 0 = none
+  std::vector<uint8_t> c_pend_keep;     // ... and whether that run kept P(same)
+  std::vector<uint8_t> c_forms;         // mv_corpus_row_forms
+  bool c_pending = false;
 
   // last-layer pruning ([CLS] rows only after the last layer's K / V projection) and its compact buffers
   bool cls_prune = true;   // env MEMVUL_CLS_PRUNE=0 disables
@@ -243,7 +258,8 @@ struct mv_handle {
                            // first-order terms in every row of every GEMM (no [CLS]-row form, no row terms), the A-side term in all three QKV blocks, and Q, K, V, P as
                            // hi + lo fp16 planes through attention at EVERY padded length (attention_v2.h VLO, NCH > 1 above 128) and through the pruned last layer's
                            // single-query attention.  Read on the host when a pass is enqueued (encode_dev); cls_aside / cls_min_len / qkv_aside_mask / short_vlo do
-                           // not reach it (it is their most conservative setting by construction)
+                           // not reach it (it is their most conservative setting by construction).  MV_FORM_GUARDED = the default form, then the safe form again
+                           // for the sequences whose own monitor items ask for it (Job::guard, rescore_rows / rescore_corpus)
 
   // profiling
   uint32_t prof_mask = 0xffffffffu;  // kernel classes that get HIP events while profiling is on
@@ -461,14 +477,23 @@ inline int padded_len(int S_in) { return (int)round_up(S_in, S_in <= 256 ? 64 : 
 // the two-plane attention (attention_v2.h VLO) serves this pass: the QKV projection wrote the lo planes of Q, K, V^T (encode_dev: the same predicate)
 inline bool two_plane_pass(const mv_handle* h, bool x8, bool safe, int Sp) { return x8 && (safe || (h->short_vlo && Sp <= 128)); }
 
-int launch_attention(mv_handle* h, Work& wk, const int32_t* d_lens, int B, int Sp, bool x8, bool sp_out = false, bool safe = false) {
+// How a pass of MV_F16X8 runs: its form, and what the concentration monitor keeps of it
+struct PassForm {
+  bool safe = false;
+  bool monitor = true;           // false: the monitor detached (a rescoring pass of the guarded form: a sequence is counted once)
+  uint32_t* seq_over = nullptr;  // device [rows of the pass], zeroed by the caller: AttnArgs::seq_over
+};
+
+int launch_attention(mv_handle* h, Work& wk, const int32_t* d_lens, int B, int Sp, bool x8, bool sp_out = false, const PassForm& pf = PassForm()) {
+  const bool safe = pf.safe;
   const bool vlo = two_plane_pass(h, x8, safe, Sp);
   AttnArgs a{wk.q, wk.k, wk.vt, d_lens, wk.ctx, Sp, B, x8 ? wk.ctx8 : nullptr, h->x8_sat, vlo ? wk.vt_lo : nullptr,
              vlo ? wk.q_lo : nullptr, vlo ? wk.k_lo : nullptr,
              (x8 && !vlo) ? wk.vlo_sp : nullptr,     // special rows: V of keys 0, 1 as hi + lo (the two-plane short passes carry every key's lo plane)
-             x8 ? h->attn_conc : nullptr,               // concentration monitor (mv_attention_concentration)
+             (x8 && pf.monitor) ? h->attn_conc : nullptr,  // concentration monitor (mv_attention_concentration)
              sp_out ? h->cls_min_len : 0,               // [CLS]-row form: no lo8 plane of the context for the sequences that take it
-             sp_out ? wk.cls_lo : nullptr};
+             sp_out ? wk.cls_lo : nullptr,
+             (x8 && pf.monitor) ? pf.seq_over : nullptr};
   ProfScope ps(h, wk.stream, KC_ATTENTION);
   if (vlo && Sp > 128) {
     // the safe form above 128 keys: chunks through the two-plane ring.  192 = 3 chunks of 64 keys (2 waves, a 64 KiB ring: two workgroups per CU), 256 / 384 / 512 =
@@ -526,7 +551,7 @@ int launch_attention(mv_handle* h, Work& wk, const int32_t* d_lens, int B, int S
 // The last layer is pruned to the [CLS] rows when the pooler follows (cls_prune); `full` (debug taps) disables that and
 // leaves the normalised fp32 stream of the last layer run in xres.
 int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_lens, int min_len, int B, int S_in, int n_layers, float* u_out,
-               bool full = false, int pitch = 0) {  // min_len: the shortest sequence of the pass as the HOST knows it (Pass::min_len; 0 = unknown)
+               const PassForm& pf = PassForm(), bool full = false, int pitch = 0) {  // min_len: the shortest sequence of the pass as the HOST knows it (Pass::min_len; 0 = unknown)
   if (pitch <= 0) pitch = S_in;  // ints between the rows of d_ids
   const mv_config& c = h->cfg;
   const int Sp = padded_len(S_in);
@@ -549,7 +574,7 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
   // construction (ModelMemory.sweep / Engine.bucketed_sweep: a pass at 192 holds 129 .. 192 tokens, at 384 257 .. 384) — else the both-terms form for the whole pass.
   const bool one_seq_tiles = Sp == 256 || Sp == 512;
   const bool whole_pass = (Sp == 192 || Sp == 384) && min_len >= h->cls_min_len;
-  const bool safe = x8 && h->form == MV_FORM_SAFE;  // (read HERE, when the pass is enqueued: work in flight keeps the form it was enqueued with)
+  const bool safe = x8 && pf.safe;  // (the form of the planned job, read from the handle when the job was made: work in flight keeps the form it was enqueued with)
   const bool cls_as = big && x8 && !safe && h->cls_aside && (one_seq_tiles || whole_pass);
   const int qkv_mask = safe ? 7 : h->qkv_aside_mask;
   const bool two_plane = two_plane_pass(h, x8, safe, Sp);
@@ -708,7 +733,7 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
       if (int rc = launch_pp<PP_QK>(h, wk.stream, KC_GEMM_QKV, g)) return rc;
       g.cls_corr = nullptr; g.vlo_sp = nullptr;
       // K3: attention (cls_as: + the context's special rows' low parts for the output projection's row term)
-      if (int rc = launch_attention(h, wk, d_lens, B, Sp, x8, cls_as, safe)) return rc;
+      if (int rc = launch_attention(h, wk, d_lens, B, Sp, x8, cls_as, pf)) return rc;
       // K4: attention output projection + bias + LayerNorm(residual), in place on the raw stream; + vstats of the new rows
       g.A = wk.ctx; g.W = w.wo; g.bias = w.bo; g.N = MV_HIDDEN; g.K = MV_HIDDEN;
       g.lnstats = st_in; g.lng = pend_g; g.lnb = pend_b; g.lnpart = st_mid; g.out16 = wk.x16; g.out16b = wk.xlo;
@@ -999,7 +1024,16 @@ struct Job {
   bool match = false;                             // + the matcher: the best anchor always, logits / probs where `out` asks for them
   float* u_dev = nullptr;                         // the encoder's output to the device here (mv_anchor_append: the bank) instead of wk.u
   int n_layers = -1; bool full = false;           // mv_debug_encode: the layers to run, and the full last layer (encode_dev)
+  bool safe = false;                              // the form of its passes (job_form: from the handle, when the job is made)
+  bool guard = false;                             // the guarded form: default-form passes with the per-sequence monitor counts kept (out.over / the corpus' c_over)
+  bool monitor = true;                            // false: a rescoring job (PassForm::monitor)
 };
+
+// The form in force when a job is made (MV_F16 has none)
+void job_form(const mv_handle* h, Job& j) {
+  j.safe = h->precise && h->form == MV_FORM_SAFE;
+  j.guard = h->precise && h->form == MV_FORM_GUARDED;
+}
 
 // The one pass loop: the passes [p0, p1) of pl enqueued on workspace set wk without waiting; after a failure it waits for what was enqueued.  Host ids /
 // lengths: one upload when they fit wk's buffers, else one per pass at its own width.  Host results: one download each when the rows fit wk's max_batch
@@ -1024,6 +1058,7 @@ int run_passes(mv_handle* h, Work& wk, const Plan& pl, size_t p0, size_t p1, con
     if (o.best) HIPCHK(h, hipMemcpyAsync(o.best + (size_t)first * 2, wk.best, (size_t)n * 8, hipMemcpyDeviceToHost, wk.stream));
     if (o.idx) HIPCHK(h, hipMemcpyAsync(o.idx + first, wk.best_idx, (size_t)n * 4, hipMemcpyDeviceToHost, wk.stream));
     if (o.embed) HIPCHK(h, hipMemcpyAsync(o.embed + (size_t)first * P, wk.u, (size_t)n * P * 4, hipMemcpyDeviceToHost, wk.stream));
+    if (o.over) HIPCHK(h, hipMemcpyAsync(o.over + first, wk.seq_over, (size_t)n * 4, hipMemcpyDeviceToHost, wk.stream));
     return MV_OK;
   };
   auto run = [&]() -> int {
@@ -1037,7 +1072,13 @@ int run_passes(mv_handle* h, Work& wk, const Plan& pl, size_t p0, size_t p1, con
         if (int rc = upload(p.first, p.rows, p.tok, (int64_t)p.rows * p.width)) return rc;
       const size_t r = one_down ? (size_t)(p.first - a.first) : 0;  // the pass's first row in wk's buffers
       float* u = j.u_dev ? j.u_dev + (size_t)p.first * P : wk.u + r * P;
-      if (int rc = encode_dev(h, wk, ids, lens, p.min_len, p.rows, p.width, j.n_layers, u, j.full, j.ids ? p.width : h->c_S)) return rc;
+      PassForm pf;
+      pf.safe = j.safe; pf.monitor = j.monitor;
+      if (j.guard) {
+        pf.seq_over = j.ids ? wk.seq_over + r : h->c_over + j.c_row + p.first;
+        HIPCHK(h, hipMemsetAsync(pf.seq_over, 0, (size_t)p.rows * 4, wk.stream));
+      }
+      if (int rc = encode_dev(h, wk, ids, lens, p.min_len, p.rows, p.width, j.n_layers, u, pf, j.full, j.ids ? p.width : h->c_S)) return rc;
       if (!j.ids) {
         const size_t c = (size_t)(j.c_row + p.first);
         if (int rc = match_dev(h, wk, u, p.rows, nullptr, nullptr, j.keep_psame ? h->c_psame + c * G : nullptr, 1, h->c_best + c * 2, h->c_idx + c)) return rc;
@@ -1055,12 +1096,139 @@ int run_passes(mv_handle* h, Work& wk, const Plan& pl, size_t p0, size_t p1, con
   return rc;
 }
 
-// mv_forward / mv_encode / mv_anchor_append / mv_debug_encode: the rows in their own order, the pass loop on workspace set 0, then wait.
+// ---- the guarded form -------------------------------------------------------------------------------------------------------------------------------------
+// The rule, per sequence: rescored in the safe form when more than kGuardShare of the (head, layer) items the monitor looked at for it are over MV_SINK_COLLISION
+// (attention.h) — the 2 % rule of binding.Engine._check_saturation applied to one sequence.  The monitor looks at every head of every layer whose attention runs
+// through attention_v2_kernel (the pruned last layer's single-query attention feeds none), for sequences of at least 16 tokens.
+constexpr double kGuardShare = 0.02;
+bool guard_flagged(const mv_handle* h, uint32_t over, int len) {
+  const int layers = h->cfg.layers - ((h->cls_prune && h->cfg.layers > 0) ? 1 : 0);
+  const int items = len >= 16 ? MV_HEADS * layers : 0;
+  return (double)over > kGuardShare * (double)items;
+}
+
+// After the default-form passes of a guarded job (j.out.over holds the counts, the stream is idle): a second plan over the flagged rows — each at the width of
+// the pass it first ran in, the flagged rows of every pass of one width sharing passes — run in the safe form with the monitor detached; those rows' results in
+// j.out (and in the bank, j.u_dev) are overwritten.  Records the form of each of the B rows in the caller's order (mv_last_row_forms).
+int rescore_rows(mv_handle* h, Work& wk, const Plan& pl, const Job& j, int B) {
+  h->last_forms.assign((size_t)B, (uint8_t)(j.safe ? MV_FORM_SAFE : MV_FORM_DEFAULT));
+  if (!j.guard) return MV_OK;
+  h->guard_seqs += B;
+  Plan& p2 = h->plan2;
+  auto& v = h->stage2;
+  p2.order.clear(), p2.passes.clear(), p2.tokens = 0;
+  v.ids.clear(), v.lens.clear();
+  std::vector<int> widths;
+  for (const Pass& p : pl.passes)
+    if (std::find(widths.begin(), widths.end(), p.width) == widths.end()) widths.push_back(p.width);
+  for (const int w : widths) {
+    const int start = (int)p2.order.size();
+    for (const Pass& p : pl.passes) {
+      if (p.width != w) continue;
+      for (int i = 0; i < p.rows; ++i) {
+        const int r = p.first + i;
+        if (!guard_flagged(h, j.out.over[r], j.lens[r])) continue;
+        p2.order.push_back(r);
+        v.lens.push_back(j.lens[r]);
+        const int32_t* src = j.ids + p.tok + (int64_t)i * w;
+        v.ids.insert(v.ids.end(), src, src + w);
+      }
+    }
+    const int end = (int)p2.order.size(), rows = max_rows_for(h, w);
+    for (int first = start; first < end; first += rows) {
+      const int n = end - first < rows ? end - first : rows;
+      int m = INT32_MAX;
+      for (int i = first; i < first + n; ++i) m = std::min(m, v.lens[i]);
+      p2.passes.push_back({first, n, w, m, p2.tokens});
+      p2.tokens += (int64_t)n * w;
+    }
+  }
+  const size_t n2 = p2.order.size();
+  if (!n2) return MV_OK;
+  const size_t g2 = (size_t)h->n_anchors * 2, P = (size_t)h->P;
+  const bool want_embed = j.out.embed || j.u_dev;
+  Job r;
+  r.ids = v.ids.data(); r.lens = v.lens.data(); r.match = j.match; r.safe = true; r.monitor = false;
+  if (j.out.logits) { v.logits.resize(n2 * g2); r.out.logits = v.logits.data(); }
+  if (j.out.probs) { v.probs.resize(n2 * g2); r.out.probs = v.probs.data(); }
+  if (j.out.best) { v.best.resize(n2 * 2); r.out.best = v.best.data(); }
+  if (j.out.idx) { v.idx.resize(n2); r.out.idx = v.idx.data(); }
+  if (want_embed) { v.embed.resize(n2 * P); r.out.embed = v.embed.data(); }
+  if (int rc = run_passes(h, wk, p2, 0, p2.passes.size(), r)) return rc;
+  HIPCHK(h, hipStreamSynchronize(wk.stream));
+  for (size_t i = 0; i < n2; ++i) {
+    const size_t o = (size_t)p2.order[i];
+    if (j.out.logits) std::memcpy(j.out.logits + o * g2, r.out.logits + i * g2, g2 * 4);
+    if (j.out.probs) std::memcpy(j.out.probs + o * g2, r.out.probs + i * g2, g2 * 4);
+    if (j.out.best) { j.out.best[o * 2] = r.out.best[i * 2]; j.out.best[o * 2 + 1] = r.out.best[i * 2 + 1]; }
+    if (j.out.idx) j.out.idx[o] = r.out.idx[i];
+    if (j.out.embed) std::memcpy(j.out.embed + o * P, r.out.embed + i * P, P * 4);
+    if (j.u_dev) HIPCHK(h, hipMemcpyAsync(j.u_dev + o * P, r.out.embed + i * P, P * 4, hipMemcpyHostToDevice, wk.stream));
+    h->last_forms[pl.order.empty() ? o : (size_t)pl.order[o]] = MV_FORM_SAFE;
+  }
+  if (j.u_dev) HIPCHK(h, hipStreamSynchronize(wk.stream));
+  h->guard_rescored += (int64_t)n2;
+  return MV_OK;
+}
+
+// The resident corpus: every row a guarded sweep ran since the last rescoring (c_pend_w) whose count (c_over) flags it — gathered by index list into a pass
+// buffer at the s_eff width of its run, in full batches, encoded in the safe form with the monitor detached, matched, and scattered back to its corpus slots
+// (P(same) rows too where the run kept them).  On workspace set 0, after every batch of the sweep has finished; waits.
+int rescore_corpus(mv_handle* h) {
+  if (!h->c_pending) return MV_OK;
+  if (int rc = sync_all(h)) return rc;
+  h->c_pending = false;
+  Work& wk = h->work[0];
+  std::vector<uint32_t> over((size_t)h->c_n);
+  HIPCHK(h, hipMemcpyAsync(over.data(), h->c_over, (size_t)h->c_n * 4, hipMemcpyDeviceToHost, wk.stream));
+  HIPCHK(h, hipStreamSynchronize(wk.stream));
+  std::map<int, std::vector<int32_t>> groups;  // 2 width + keep -> corpus rows (alive until the last upload from them has been waited for)
+  for (int64_t r = 0; r < h->c_n; ++r) {
+    const int w = h->c_pend_w[(size_t)r];
+    if (!w) continue;
+    h->c_pend_w[(size_t)r] = 0;
+    if (guard_flagged(h, over[(size_t)r], h->c_lens_host[(size_t)r])) groups[2 * w + h->c_pend_keep[(size_t)r]].push_back((int32_t)r);
+  }
+  const int G = h->n_anchors;
+  PassForm pf;
+  pf.safe = true; pf.monitor = false;
+  for (auto& kv : groups) {
+    const int w = kv.first >> 1;
+    const bool keep = (kv.first & 1) && h->c_psame && h->c_G == G;
+    const std::vector<int32_t>& idx = kv.second;
+    const int rows = max_rows_for(h, w);
+    if (rows <= 0) return fail(h, MV_ERR_CAPACITY, "mv_config.max_tokens too small for one row of this length");
+    for (size_t first = 0; first < idx.size(); first += (size_t)rows) {
+      const int n = (int)std::min((size_t)rows, idx.size() - first);
+      int m = INT32_MAX;
+      for (int i = 0; i < n; ++i) m = std::min(m, h->c_lens_host[(size_t)idx[first + i]]);
+      HIPCHK(h, hipMemcpyAsync(wk.d_idx, idx.data() + first, (size_t)n * 4, hipMemcpyHostToDevice, wk.stream));
+      const int64_t nt = (int64_t)n * w;
+      hipLaunchKernelGGL(corpus_gather_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, wk.stream, (const int32_t*)h->c_ids, (const int32_t*)h->c_lens,
+                         h->c_S, (const int32_t*)wk.d_idx, n, w, wk.d_ids, wk.d_lens);
+      if (int rc = launch_check(h, "corpus_gather")) return rc;
+      if (int rc = encode_dev(h, wk, wk.d_ids, wk.d_lens, m, n, w, -1, wk.u, pf, false, w)) return rc;
+      if (int rc = match_dev(h, wk, wk.u, n, nullptr, nullptr, keep ? wk.psame : nullptr, 1, wk.best, wk.best_idx)) return rc;
+      const int64_t ns = (int64_t)n * (keep ? G : 1);
+      hipLaunchKernelGGL(corpus_scatter_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, wk.stream, (const float*)wk.best, (const int32_t*)wk.best_idx,
+                         keep ? (const float*)wk.psame : (const float*)nullptr, (const int32_t*)wk.d_idx, n, G, h->c_best, h->c_idx, h->c_psame);
+      if (int rc = launch_check(h, "corpus_scatter")) return rc;
+      for (int i = 0; i < n; ++i) h->c_forms[(size_t)idx[first + i]] = MV_FORM_SAFE;
+      h->guard_rescored += n;
+    }
+  }
+  HIPCHK(h, hipStreamSynchronize(wk.stream));
+  return MV_OK;
+}
+
+// mv_forward / mv_encode / mv_anchor_append / mv_debug_encode: the rows in their own order, the pass loop on workspace set 0, then wait (and, in the guarded
+// form, rescore the flagged rows).
 int run_in_order(mv_handle* h, const int32_t* lens, int B, int S, Job& j) {
+  if (j.guard) { h->stage.over.resize((size_t)B); j.out.over = h->stage.over.data(); }
   if (int rc = plan_batch(h, lens, B, S, 0, false, 0, h->plan)) return rc;
   if (int rc = run_passes(h, h->work[0], h->plan, 0, h->plan.passes.size(), j)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->work[0].stream));
-  return MV_OK;
+  return j.full ? MV_OK : rescore_rows(h, h->work[0], h->plan, j, B);
 }
 
 // The rows of a by-length batch gathered into plan order: each pass's ids at its own width (ids [B][S]).
@@ -1196,8 +1364,9 @@ int mv_create(int device, const mv_config* cfg, mv_handle** out) try {
   if (const char* e = getenv("MEMVUL_FORM")) {  // the form of MV_F16X8 the handle starts in (mv_set_form changes it later); MV_F16 has none: mv_finalize_weights
     if (!strcmp(e, "safe")) h->form = MV_FORM_SAFE;
     else if (!strcmp(e, "default")) h->form = MV_FORM_DEFAULT;
+    else if (!strcmp(e, "guarded")) h->form = MV_FORM_GUARDED;
     else {
-      g_create_error = std::string("MEMVUL_FORM=\"") + e + "\": expected \"default\" or \"safe\"";
+      g_create_error = std::string("MEMVUL_FORM=\"") + e + "\": expected \"default\", \"safe\" or \"guarded\"";
       return MV_ERR_INVALID;
     }
   }
@@ -1233,6 +1402,8 @@ int mv_create(int device, const mv_config* cfg, mv_handle** out) try {
     Work& wk = h->work[wi];
     A(dev_alloc(h, wk.stream, &wk.d_ids, T));
     A(dev_alloc(h, wk.stream, &wk.d_lens, (int64_t)cfg->max_batch + 16));
+    A(dev_alloc(h, wk.stream, &wk.seq_over, (int64_t)cfg->max_batch));
+    A(dev_alloc(h, wk.stream, &wk.d_idx, (int64_t)cfg->max_batch));
     A(dev_alloc(h, wk.stream, &wk.xres, T * MV_HIDDEN));
     A(dev_alloc(h, wk.stream, &wk.x16, T * MV_HIDDEN));
     A(dev_alloc(h, wk.stream, &wk.q, T * MV_HIDDEN));
@@ -1328,8 +1499,8 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
     return fail(h, MV_ERR_INVALID, "compute_dtype must be MV_F16 (fp16 MFMA operands, fp32 accumulation) or MV_F16X8 (+ fp8 correction "
                                    "sweeps); bf16 is a storage dtype of mv_load_tensor only (include/memvul_hip.h)");
   const bool precise = compute_dtype == MV_F16X8;
-  if (!precise && h->form == MV_FORM_SAFE)
-    return fail(h, MV_ERR_STATE, "the safe form (MEMVUL_FORM=safe / mv_set_form) is a form of compute dtype MV_F16X8: it cannot be combined with MV_F16");
+  if (!precise && h->form != MV_FORM_DEFAULT)
+    return fail(h, MV_ERR_STATE, "the safe and the guarded form (MEMVUL_FORM / mv_set_form) are forms of compute dtype MV_F16X8: they cannot be combined with MV_F16");
   HIPCHK(h, hipSetDevice(h->device));
   const hipStream_t s0 = h->work[0].stream;  // (the uploads)
   const mv_config& c = h->cfg;
@@ -1505,6 +1676,10 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
 
 int mv_anchor_reset(mv_handle* h) try {
   if (!h) return MV_ERR_INVALID;
+  if (h->c_pending) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = rescore_corpus(h)) return rc;
+  }
   h->n_anchors = 0;
   return MV_OK;
 } catch (...) { return on_exception(h); }
@@ -1518,8 +1693,10 @@ int mv_anchor_append(mv_handle* h, const int32_t* ids, const int32_t* lens, int 
   HIPCHK(h, hipSetDevice(h->device));
   for (int wi = 1; wi < h->n_alloc; ++wi)  // a ticket in flight on another set still reads the bank this call writes
     if (h->work[wi].ticket) HIPCHK(h, hipStreamSynchronize(h->work[wi].stream));
+  if (int rc = rescore_corpus(h)) return rc;  // (a guarded sweep not yet collected is rescored against the bank it ran on)
   Job j;
   j.ids = ids; j.lens = lens; j.u_dev = h->anchors + (size_t)h->n_anchors * h->P;
+  job_form(h, j);
   if (int rc = run_in_order(h, lens, n, S, j)) return rc;
   h->n_anchors += n;
   return MV_OK;
@@ -1540,6 +1717,7 @@ int mv_anchor_set(mv_handle* h, const float* v, int G) try {
   if (G > h->cfg.max_anchors) return fail(h, MV_ERR_CAPACITY, "anchor bank capacity (mv_config.max_anchors) exceeded");
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = sync_all(h)) return rc;  // batches of a resident sweep in flight read the bank
+  if (int rc = rescore_corpus(h)) return rc;
   Work& wk = h->work[0];
   HIPCHK(h, hipMemcpyAsync(h->anchors, v, (size_t)G * h->P * 4, hipMemcpyHostToDevice, wk.stream));
   HIPCHK(h, hipStreamSynchronize(wk.stream));
@@ -1554,6 +1732,7 @@ int mv_encode(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int 
   HIPCHK(h, hipSetDevice(h->device));
   Job j;
   j.ids = ids; j.lens = lens; j.out.embed = embed;
+  job_form(h, j);
   return run_in_order(h, lens, B, S, j);
 } catch (...) { return on_exception(h); }
 
@@ -1567,6 +1746,7 @@ int mv_forward(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int
   Job j;
   j.ids = ids; j.lens = lens; j.match = true;
   j.out.logits = logits; j.out.probs = probs; j.out.best = best; j.out.idx = best_idx; j.out.embed = embed;
+  job_form(h, j);
   return run_in_order(h, lens, B, S, j);
 } catch (...) { return on_exception(h); }
 
@@ -1597,8 +1777,11 @@ int mv_forward_ragged(mv_handle* h, const int32_t* ids, const int32_t* lens, int
   Job j;
   j.ids = v.ids.data(); j.lens = v.lens.data(); j.match = true;
   j.out = Stage{nullptr, nullptr, v.idx.data(), logits ? v.logits.data() : nullptr, probs ? v.probs.data() : nullptr, v.best.data(), embed ? v.embed.data() : nullptr};
+  job_form(h, j);
+  if (j.guard) { v.over.resize(B); j.out.over = v.over.data(); }
   if (int rc = run_passes(h, h->work[0], pl, 0, pl.passes.size(), j)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->work[0].stream));
+  if (int rc = rescore_rows(h, h->work[0], pl, j, B)) return rc;
   scatter(h, pl.order, G, j.out, logits, probs, best, best_idx, embed);
   return MV_OK;
 } catch (...) { return on_exception(h); }
@@ -1635,6 +1818,7 @@ int mv_forward_ragged_begin(mv_handle* h, const int32_t* ids, const int32_t* len
     if (!rc) rc = pin((void**)&s.probs, bg2 * 4);
     if (!rc) rc = pin((void**)&s.best, mb * 2 * 4);
     if (!rc) rc = pin((void**)&s.embed, mb * (size_t)h->P * 4);
+    if (!rc) rc = pin((void**)&s.over, mb * 4);
     if (rc) return rc;
     wk.pin = s;
   }
@@ -1644,9 +1828,11 @@ int mv_forward_ragged_begin(mv_handle* h, const int32_t* ids, const int32_t* len
   if (!want_embed) st.embed = nullptr;
   gather(wk.plan, ids, lens, S, st.ids, st.lens);
   Job j;
+  job_form(h, j);  // (the form in force HERE is the ticket's: mv_forward_ragged_end rescores a guarded one)
+  if (!j.guard) st.over = nullptr;
   j.ids = st.ids; j.lens = st.lens; j.match = true; j.out = st;
   if (int rc = run_passes(h, wk, wk.plan, 0, wk.plan.passes.size(), j)) return rc;
-  wk.ticket = true; wk.G = h->n_anchors; wk.st = st;
+  wk.ticket = true; wk.G = h->n_anchors; wk.st = st; wk.guard = j.guard; wk.safe = j.safe;
   *ticket = set;
   return MV_OK;
 } catch (...) { return on_exception(h); }
@@ -1660,6 +1846,16 @@ int mv_forward_ragged_end(mv_handle* h, int ticket, float* logits, float* probs,
   if (e != hipSuccess) return fail(h, MV_ERR_HIP, std::string("mv_forward_ragged_end: ") + hipGetErrorString(e));
   if (!best || !best_idx || (wk.st.logits && !logits) || (wk.st.probs && !probs) || (wk.st.embed && !embed))
     return fail(h, MV_ERR_INVALID, "mv_forward_ragged_end: an output the batch was started with is missing");
+  {
+    // the batch's ids are still in the pinned staging; the bank rows the batch was matched against are the first wk.G of whatever the bank holds now
+    Job j;
+    j.ids = wk.st.ids; j.lens = wk.st.lens; j.match = true; j.out = wk.st; j.guard = wk.guard; j.safe = wk.safe;
+    const int G_now = h->n_anchors;
+    h->n_anchors = wk.G;
+    const int rc = rescore_rows(h, wk, wk.plan, j, (int)wk.plan.order.size());
+    h->n_anchors = G_now;
+    if (rc) return rc;
+  }
   scatter(h, wk.plan.order, wk.G, wk.st, logits, probs, best, best_idx, embed);
   return MV_OK;
 } catch (...) { return on_exception(h); }
@@ -1707,13 +1903,18 @@ int mv_corpus_upload(mv_handle* h, const int32_t* ids, const int32_t* lens, int6
   HIPCHK(h, hipSetDevice(h->device));
   const hipStream_t s0 = h->work[0].stream;
   HIPCHK(h, hipStreamSynchronize(s0));
-  dev_free(h, h->c_ids); dev_free(h, h->c_lens); dev_free(h, h->c_best); dev_free(h, h->c_idx); dev_free(h, h->c_psame);
-  h->c_ids = nullptr; h->c_lens = nullptr; h->c_best = nullptr; h->c_idx = nullptr; h->c_psame = nullptr;
+  dev_free(h, h->c_ids); dev_free(h, h->c_lens); dev_free(h, h->c_best); dev_free(h, h->c_idx); dev_free(h, h->c_psame); dev_free(h, h->c_over);
+  h->c_ids = nullptr; h->c_lens = nullptr; h->c_best = nullptr; h->c_idx = nullptr; h->c_psame = nullptr; h->c_over = nullptr;
+  h->c_pending = false;
   h->c_psame_rows = 0;
   if (int rc = dev_alloc(h, s0, &h->c_ids, n * S, false)) return rc;
   if (int rc = dev_alloc(h, s0, &h->c_lens, n, false)) return rc;
   if (int rc = dev_alloc(h, s0, &h->c_best, n * 2)) return rc;
   if (int rc = dev_alloc(h, s0, &h->c_idx, n)) return rc;
+  if (int rc = dev_alloc(h, s0, &h->c_over, n)) return rc;
+  h->c_pend_w.assign((size_t)n, 0);
+  h->c_pend_keep.assign((size_t)n, 0);
+  h->c_forms.assign((size_t)n, MV_FORM_DEFAULT);
   HIPCHK(h, hipMemcpyAsync(h->c_ids, ids, (size_t)n * S * 4, hipMemcpyHostToDevice, s0));
   HIPCHK(h, hipMemcpyAsync(h->c_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, s0));
   HIPCHK(h, hipStreamSynchronize(s0));
@@ -1753,6 +1954,14 @@ int mv_corpus_run_len(mv_handle* h, int64_t first, int64_t count, int batch, int
   // flight at once; their results go to disjoint slices of the resident arrays
   Job j;
   j.c_row = first; j.keep_psame = keep_probs != 0;
+  job_form(h, j);
+  // the guarded form: the sweep stays asynchronous and only records the per-row counts (c_over) and what it ran (c_pend_w): rescore_corpus, from mv_corpus_results
+  for (int64_t r = first; r < first + count; ++r) {
+    h->c_pend_w[(size_t)r] = (int16_t)(j.guard ? S_use : 0);
+    h->c_pend_keep[(size_t)r] = (uint8_t)(keep_probs != 0);
+    h->c_forms[(size_t)r] = (uint8_t)(j.safe ? MV_FORM_SAFE : MV_FORM_DEFAULT);
+  }
+  if (j.guard) { h->c_pending = true; h->guard_seqs += count; }
   for (size_t i = 0; i < pl.passes.size(); ++i) {
     Work& wk = h->work[h->rr];
     wk.sweep = true;
@@ -1768,6 +1977,7 @@ int mv_corpus_results(mv_handle* h, int64_t first, int64_t count, float* best, i
   if (first < 0 || count <= 0 || first + count > h->c_n) return fail(h, MV_ERR_INVALID, "mv_corpus_results: bad range");
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = sync_all(h)) return rc;
+  if (int rc = rescore_corpus(h)) return rc;
   const hipStream_t s0 = h->work[0].stream;
   if (best) HIPCHK(h, hipMemcpyAsync(best, h->c_best + (size_t)first * 2, (size_t)count * 8, hipMemcpyDeviceToHost, s0));
   if (best_idx) HIPCHK(h, hipMemcpyAsync(best_idx, h->c_idx + first, (size_t)count * 4, hipMemcpyDeviceToHost, s0));
@@ -1915,9 +2125,10 @@ int mv_set_streams(mv_handle* h, int n) try {
 
 int mv_set_form(mv_handle* h, int form) try {
   if (!h) return MV_ERR_INVALID;
-  if (form != MV_FORM_DEFAULT && form != MV_FORM_SAFE) return fail(h, MV_ERR_INVALID, "mv_set_form: MV_FORM_DEFAULT (0) or MV_FORM_SAFE (1)");
-  if (form == MV_FORM_SAFE && h->finalized && !h->precise)
-    return fail(h, MV_ERR_STATE, "mv_set_form: MV_FORM_SAFE is a form of compute dtype MV_F16X8; this handle was finalized as MV_F16");
+  if (form != MV_FORM_DEFAULT && form != MV_FORM_SAFE && form != MV_FORM_GUARDED)
+    return fail(h, MV_ERR_INVALID, "mv_set_form: MV_FORM_DEFAULT (0), MV_FORM_SAFE (1) or MV_FORM_GUARDED (2)");
+  if (form != MV_FORM_DEFAULT && h->finalized && !h->precise)
+    return fail(h, MV_ERR_STATE, "mv_set_form: MV_FORM_SAFE and MV_FORM_GUARDED are forms of compute dtype MV_F16X8; this handle was finalized as MV_F16");
   h->form = form;  // (no synchronisation: passes already enqueued were built with the form of their time)
   return MV_OK;
 } catch (...) { return on_exception(h); }
@@ -1925,6 +2136,29 @@ int mv_set_form(mv_handle* h, int form) try {
 int mv_get_form(mv_handle* h) try {
   if (!h) return MV_ERR_INVALID;
   return h->form;
+} catch (...) { return on_exception(h); }
+
+int mv_form_stats(mv_handle* h, int64_t* sequences, int64_t* rescored, int reset) try {
+  if (!h || !sequences || !rescored) return fail(h, MV_ERR_INVALID, "mv_form_stats: bad argument");
+  *sequences = h->guard_seqs;
+  *rescored = h->guard_rescored;
+  if (reset) h->guard_seqs = h->guard_rescored = 0;
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+int mv_last_row_forms(mv_handle* h, uint8_t* forms, int n) try {
+  if (!h || !forms || n < 0 || (size_t)n != h->last_forms.size()) return fail(h, MV_ERR_INVALID, "mv_last_row_forms: n is not the row count of the last call");
+  std::memcpy(forms, h->last_forms.data(), (size_t)n);
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+int mv_corpus_row_forms(mv_handle* h, int64_t first, int64_t count, uint8_t* forms) try {
+  if (!h || !forms) return fail(h, MV_ERR_INVALID, "mv_corpus_row_forms: bad argument");
+  if (!h->c_ids) return fail(h, MV_ERR_STATE, "no resident corpus (mv_corpus_upload)");
+  if (first < 0 || count <= 0 || first + count > h->c_n) return fail(h, MV_ERR_INVALID, "mv_corpus_row_forms: bad range");
+  if (h->c_pending) return fail(h, MV_ERR_STATE, "mv_corpus_row_forms: a guarded sweep has not been collected yet (mv_corpus_results)");
+  std::memcpy(forms, h->c_forms.data() + first, (size_t)count);
+  return MV_OK;
 } catch (...) { return on_exception(h); }
 
 int mv_x8_saturation(mv_handle* h, int64_t* clamped, int reset) try {
@@ -1980,6 +2214,7 @@ int mv_debug_encode(mv_handle* h, const int32_t* ids, const int32_t* lens, int B
   HIPCHK(h, hipSetDevice(h->device));
   Job j;  // (on workspace set 0: what mv_debug_read reads)
   j.ids = ids; j.lens = lens; j.n_layers = n_layers < 0 ? h->cfg.layers : n_layers; j.full = true;
+  j.safe = h->precise && h->form == MV_FORM_SAFE;  // (MV_FORM_GUARDED: the taps show the default form, nothing is rescored)
   return run_in_order(h, lens, B, S, j);
 } catch (...) { return on_exception(h); }
 

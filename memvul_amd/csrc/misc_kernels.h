@@ -353,3 +353,31 @@ __global__ __launch_bounds__(512) void dense768_kernel(const float* __restrict__
 }
 
 // K9 + K10 (anchor match, softmax_2, best anchor / top-k): match_topk.h
+
+// The guarded form on the resident corpus (engine.hip rescore_corpus): rows idx[0 .. n) of the corpus' ids (rows of S ints) into a pass buffer at `width` ints per
+// row (width <= S), their lengths beside them ...
+__global__ __launch_bounds__(256) void corpus_gather_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ lens, int S, const int32_t* __restrict__ idx,
+                                                            int n, int width, int32_t* __restrict__ ids_out, int32_t* __restrict__ lens_out) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (int64_t)n * width) return;
+  const int i = (int)(t / width), c = (int)(t - (int64_t)i * width);
+  const int64_t r = idx[i];
+  ids_out[t] = ids[r * S + c];
+  if (c == 0) lens_out[i] = lens[r];
+}
+// ... and the rescored rows' best P(same), best anchor and (psame != NULL) P(same) rows [n][G] back to their corpus slots
+__global__ __launch_bounds__(256) void corpus_scatter_kernel(const float* __restrict__ best, const int32_t* __restrict__ best_idx, const float* __restrict__ psame,
+                                                             const int32_t* __restrict__ idx, int n, int G, float* __restrict__ c_best,
+                                                             int32_t* __restrict__ c_idx, float* __restrict__ c_psame) {
+  const int cols = psame ? G : 1;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (int64_t)n * cols) return;
+  const int i = (int)(t / cols), c = (int)(t - (int64_t)i * cols);
+  const int64_t r = idx[i];
+  if (psame) c_psame[r * G + c] = psame[t];
+  if (c == 0) {
+    c_best[2 * r] = best[2 * i];
+    c_best[2 * r + 1] = best[2 * i + 1];
+    c_idx[r] = best_idx[i];
+  }
+}

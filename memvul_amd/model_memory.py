@@ -26,7 +26,7 @@ from typing import Any, Dict, List, Optional
 
 import numpy as np
 
-from .binding import Engine, compute_dtype_of, wants_safe_form
+from .binding import Engine, compute_dtype_of, wanted_form
 from .custom_metric import SiameseMeasureV1
 from .data import Instance, collate
 from .registry import HAVE_ALLENNLP, Model, TextFieldEmbedder, TokenEmbedder, Vocabulary, register_builtin
@@ -185,11 +185,11 @@ class ModelMemory(Model):
         opts["proj_dim"] = 512 if self._use_header else 768
         # compute dtype: MV_F16X8 ("precise", the DEFAULT: fp16 sweep + one fp8 correction sweep per GEMM — the mode that holds the
         # reference's 1e-3 on trained-like logits; include/memvul_hip.h) or MV_F16 ("fast": explicit opt-in, 3.0-5.6e-3 there);
-        # engine_options["compute_dtype"] or $MEMVUL_COMPUTE = precise | f16x8 | f16 | fast | safe.  An unknown name raises here
+        # engine_options["compute_dtype"] or $MEMVUL_COMPUTE = precise | f16x8 | f16 | fast | safe | guarded.  An unknown name raises here
         # (ValueError), not inside ctypes.
-        # "safe" = MV_F16X8 in its safe form (include/memvul_hip.h mv_set_form): the name itself goes to Engine.load_state_dict, which sets the form.
+        # "safe" / "guarded" = MV_F16X8 in that form (include/memvul_hip.h mv_set_form): the name itself goes to Engine.load_state_dict, which sets the form.
         cd = opts.pop("compute_dtype", None)
-        cd = "safe" if wants_safe_form(cd) else compute_dtype_of(cd)
+        cd = wanted_form(cd) or compute_dtype_of(cd)
         if self._engine is not None:
             self._engine.close()
         self._engine = Engine(self._device_index, vocab_size=vocab_size, layers=layers, max_pos=max_pos, type_vocab=type_vocab,

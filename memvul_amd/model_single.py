@@ -17,7 +17,7 @@ from typing import Any, Dict, List, Optional
 
 import numpy as np
 
-from .binding import Engine, compute_dtype_of, wants_safe_form
+from .binding import Engine, compute_dtype_of, wanted_form
 from .model_memory import PFX_BERT, _ClassificationCounts, _np
 from .registry import Model, TextFieldEmbedder, Vocabulary
 
@@ -70,7 +70,7 @@ class ModelSingle(Model):
         self._engine = Engine(self._device_index, vocab_size=sd[PFX_BERT + "embeddings.word_embeddings.weight"].shape[0], layers=layers,
                               max_pos=min(512, sd[PFX_BERT + "embeddings.position_embeddings.weight"].shape[0]),
                               type_vocab=sd[PFX_BERT + "embeddings.token_type_embeddings.weight"].shape[0], **opts)
-        self._engine.load_state_dict(eng_sd, "safe" if wants_safe_form(opts_compute) else compute_dtype_of(opts_compute))
+        self._engine.load_state_dict(eng_sd, wanted_form(opts_compute) or compute_dtype_of(opts_compute))
         return self
 
     @property
