@@ -42,6 +42,9 @@ typedef enum mv_status {
   MV_ERR_INTERNAL = -7        /* a C++ exception was caught at the ABI boundary (never propagated to the caller) */
 } mv_status;
 
+/* MV_F32 is a storage dtype of mv_load_tensor AND the third compute dtype of mv_finalize_weights — the reference form: the arithmetic the reference runs
+ * (fp32 operands, fp32 accumulation, erf GELU, max-subtracted softmax), on the fp32-input MFMA (v_mfma_f32_32x32x2_f32); 1/16 of the 16-bit matrix rate; for
+ * audits and envelope work (memvul_amd/audit.py measures the other compute dtypes against it on the model and the data a user has), not for throughput. */
 typedef enum mv_dtype { MV_F32 = 0, MV_F16 = 1, MV_BF16 = 2, MV_I32 = 3, MV_I64 = 4,
                         /* compute dtype only ("precise"): the fp16 MFMA sweep of every encoder GEMM plus ONE correction sweep on the
                          * fp8 matrix path (OCP e4m3, v_mfma_scale_f32_16x16x128_f8f6f4) over the first-order terms of the split-operand
@@ -89,7 +92,7 @@ typedef struct mv_config {
  *   MEMVUL_FORM               default | safe | guarded: the form of MV_F16X8 the handle starts in (mv_set_form changes it later).  "safe" and "guarded" with
  *                             mv_finalize_weights(MV_F16) fail.
  *                             In the safe form MEMVUL_CLS_ASIDE, MEMVUL_CLS_ASIDE_MIN_LEN and MEMVUL_QKV_ASIDE have no effect (it is their most conservative setting).
- * (The seventh switch of the product, MEMVUL_COMPUTE = precise | f16, is read by the Python surface: memvul_amd/binding.py default_compute.)
+ * (The seventh switch of the product, MEMVUL_COMPUTE = precise | f16 | f32 (+ aliases), is read by the Python surface: memvul_amd/binding.py default_compute.)
  * Development A/B knobs (kernel path forced at test sizes, raster, grid share, one-plane short passes) exist only in the -DMEMVUL_DEV_SWITCHES build
  * (libmemvul_hip_dev.so: memvul_amd/build.py, loaded by the GPU tests and A/B scripts that need them); this library does not read them. */
 int mv_create(int device, const mv_config* cfg, mv_handle** out);
@@ -112,7 +115,10 @@ int mv_load_tensor(mv_handle* h, const char* name, const void* host_ptr, int dty
  * `compute_dtype` and uploads.  Compute dtypes: MV_F16X8 (fp16 MFMA sweep + an fp8 correction sweep per GEMM, see mv_dtype:
  * what the Python surface passes by default and what bench.py's headline is measured in — it holds the 1e-3 logit tolerance of
  * model_memory.py:133-147 on trained-like weights) and MV_F16 (one fp16 sweep, fp32 accumulation: the explicit "fast" opt-in,
- * 3.0-5.6e-3 on such weights); anything else returns MV_ERR_INVALID.  MV_BF16 is a STORAGE dtype of mv_load_tensor only (bf16 checkpoints load): as MFMA
+ * 3.0-5.6e-3 on such weights) and MV_F32 (the reference form, see mv_dtype: the four GEMM weights of every layer stay fp32 and un-folded, Q | K | V, the
+ * attention context and the FFN intermediate are fp32 planes allocated here, 6144 floats per token of max_tokens and workspace set; no forms, no monitors — they
+ * read 0 —, no last-layer pruning, natural token order; within 3e-5 of a float64 evaluation on the logits); anything else returns
+ * MV_ERR_INVALID.  MV_BF16 is a STORAGE dtype of mv_load_tensor only (bf16 checkpoints load): as MFMA
  * operand format it was measured and rejected — 8 significand bits put the match logits 1.5e-2 off at |logit| ~ 3
  * and 2.5e-3 off even on random-init weights (oracle/precision_model.py), against a 1e-3 budget, at the
  * same MFMA rate as fp16.  Embeddings, LayerNorm, biases, pooler, header and matcher stay fp32. */
@@ -136,7 +142,7 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype);
  *                    and rescores everything swept since, in full batches, before mv_corpus_results copies anything.  The rescoring passes leave the global
  *                    counters of mv_attention_concentration alone (a sequence is counted once).  Costs the default form's rate times (1 + 1.34 f) at a flagged
  *                    share f: above f ~ 0.25 the safe form is the cheaper one.  mv_debug_encode ignores it (taps show the default form).
- * mv_set_form: MV_FORM_SAFE / MV_FORM_GUARDED on a handle finalized as MV_F16 -> MV_ERR_STATE, an unknown value -> MV_ERR_INVALID.  The form of a pass is read on the
+ * mv_set_form: MV_FORM_SAFE / MV_FORM_GUARDED on a handle finalized as MV_F16 or MV_F32 -> MV_ERR_STATE, an unknown value -> MV_ERR_INVALID.  The form of a pass is read on the
  * host when the pass is enqueued: work already in flight keeps the form it was enqueued with.  mv_get_form returns the current form. */
 #define MV_FORM_DEFAULT 0
 #define MV_FORM_SAFE 1
@@ -291,7 +297,8 @@ const char* mv_kernel_class_name(int cls);
  * (Sp = S rounded up to a multiple of 64, above 256 to a multiple of 128; buffers hold the state of the LAST executed layer; Q carries
  * the folded 1/8.  The pass takes the path its size selects — persistent kernels or the small-pass kernels — with last-layer pruning
  * off and the final LayerNorm applied, so buffer 0 is the normalised output of layer n_layers.  MV_FORM_GUARDED is ignored here: the taps show the default
- * form, nothing is rescored.) */
+ * form, nothing is rescored.  An MV_F32 handle has buffers 0 and 10 only: its Q, K, V, context and intermediate are fp32 planes, and mv_debug_read of the
+ * fp16 taps 1 - 9 returns MV_ERR_INVALID with a message that says so.) */
 int mv_debug_encode(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int n_layers);
 int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes);
 /* Stand-alone GEMM check/bench on caller data: C[M,N] = A[M,K] (fp16 bits) x W[N,K]^T (fp16 bits)
@@ -304,6 +311,10 @@ int mv_test_gemm(mv_handle* h, int variant, int M, int N, int K, const uint16_t*
  * planes on the host) and, with out8, returns the [lo8 | hi8] e4m3 planes of the output [M][2 N].  M,N % 256, K % 128, K >= 256. */
 int mv_test_gemm_pp(mv_handle* h, int x8, int M, int N, int K, const float* A, const float* W, const float* bias, uint16_t* out16,
                     uint8_t* out8, int iters, float* ms);
+/* The MV_F32 GEMM (ref_f32.h) on caller data, all fp32: C [M][N] = act(A [M][K] W [N][K]^T + bias) (+ res [M][N]); act 0 = bias only, 1 = erf GELU,
+ * 2 = + res (required then).  bias may be NULL (zeros).  M, N % 128, K % 32.  Works on a handle of any compute dtype.  iters / ms as mv_test_gemm. */
+int mv_test_gemm_f32(mv_handle* h, int act, int M, int N, int K, const float* A, const float* W, const float* bias, const float* res, float* C, int iters,
+                     float* ms);
 /* The host-side e4m3 encoder used for the MV_F16X8 weight planes (needs no GPU, h may be NULL elsewhere): out[i] = OCP e4m3fn bits of in[i]. */
 int mv_test_e4m3(const float* in, uint8_t* out, int64_t n);
 

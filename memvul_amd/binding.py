@@ -19,7 +19,10 @@ DEV_SWITCHES = ("MEMVUL_GEMM_TILE", "MEMVUL_SHORT_VLO", "MEMVUL_RASTER", "MEMVUL
 
 MV_F32, MV_F16, MV_BF16, MV_I32, MV_I64 = 0, 1, 2, 3, 4
 MV_F16X8 = 6  # compute dtype only ("precise"): fp16 MFMA sweep + one fp8 (e4m3) correction sweep per GEMM (include/memvul_hip.h)
-COMPUTE_DTYPES = {"f16": MV_F16, "fast": MV_F16, "f16x8": MV_F16X8, "precise": MV_F16X8, "safe": MV_F16X8, "guarded": MV_F16X8}
+COMPUTE_DTYPES = {"f16": MV_F16, "fast": MV_F16, "f16x8": MV_F16X8, "precise": MV_F16X8, "safe": MV_F16X8, "guarded": MV_F16X8,
+                  # the reference form: the encoder in fp32 on the fp32-input MFMA — what memvul_amd/audit.py measures the other dtypes against; 1/16 of the
+                  # 16-bit matrix rate, for audits and envelope work, not for throughput
+                  "f32": MV_F32, "reference": MV_F32}
 # the three forms of MV_F16X8 (include/memvul_hip.h mv_set_form).  "safe" as a compute dtype name = MV_F16X8 + the safe form set after finalize: both first-order
 # correction terms in every row and two fp16 planes through attention at every length — the form that holds 1e-3 with an attention sink on an ordinary token
 # ("guarded" likewise: the default form, and the safe form again for the sequences whose own monitor items report an ordinary-token sink)
@@ -35,12 +38,12 @@ DEFAULT_COMPUTE = "precise"
 
 
 def default_compute() -> str:
-    """$MEMVUL_COMPUTE (f16 | fast | f16x8 | precise | safe | guarded) or the contract-holding default."""
+    """$MEMVUL_COMPUTE (f16 | fast | f16x8 | precise | safe | guarded | f32 | reference) or the contract-holding default."""
     return os.environ.get("MEMVUL_COMPUTE", DEFAULT_COMPUTE)
 
 
 def compute_dtype_of(name_or_code) -> int:
-    """"f16" (alias "fast") | "f16x8" (alias "precise") or the numeric mv_dtype -> the code mv_finalize_weights takes; None = the
+    """"f16" (alias "fast") | "f16x8" (alias "precise") | "f32" (alias "reference") or the numeric mv_dtype -> the code mv_finalize_weights takes; None = the
     default (default_compute()); anything else raises."""
     if name_or_code is None:
         name_or_code = default_compute()
@@ -48,8 +51,8 @@ def compute_dtype_of(name_or_code) -> int:
         if name_or_code.lower() not in COMPUTE_DTYPES:
             raise ValueError(f"unknown compute dtype {name_or_code!r}: expected one of {sorted(COMPUTE_DTYPES)}")
         return COMPUTE_DTYPES[name_or_code.lower()]
-    if int(name_or_code) not in (MV_F16, MV_F16X8):
-        raise ValueError(f"unknown compute dtype code {name_or_code!r}: MV_F16 = {MV_F16} or MV_F16X8 = {MV_F16X8}")
+    if int(name_or_code) not in (MV_F16, MV_F16X8, MV_F32):
+        raise ValueError(f"unknown compute dtype code {name_or_code!r}: MV_F16 = {MV_F16}, MV_F16X8 = {MV_F16X8} or MV_F32 = {MV_F32}")
     return int(name_or_code)
 
 
@@ -84,7 +87,7 @@ ABI_SYMBOLS = [
     "mv_anchor_reset", "mv_anchor_append", "mv_anchor_count", "mv_anchor_get", "mv_anchor_set",
     "mv_forward", "mv_forward_ragged", "mv_forward_ragged_begin", "mv_forward_ragged_end", "mv_encode", "mv_match", "mv_topk", "mv_corpus_upload", "mv_corpus_run", "mv_corpus_run_len",
     "mv_corpus_results", "mv_x8_saturation", "mv_attention_concentration", "mv_set_form", "mv_get_form", "mv_form_stats", "mv_last_row_forms", "mv_corpus_row_forms", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
-    "mv_debug_encode", "mv_debug_read", "mv_test_gemm", "mv_test_gemm_pp", "mv_test_e4m3", "mv_format_records", "mv_comm_prepare", "mv_comm_unique_id", "mv_comm_init", "mv_comm_allgather",
+    "mv_debug_encode", "mv_debug_read", "mv_test_gemm", "mv_test_gemm_pp", "mv_test_gemm_f32", "mv_test_e4m3", "mv_format_records", "mv_comm_prepare", "mv_comm_unique_id", "mv_comm_init", "mv_comm_allgather",
     "mv_comm_destroy", "mv_comm_info", "mv_device_count",
 ]
 
@@ -159,6 +162,7 @@ def load_library(path: Optional[str] = None, dev: bool = False):
         "mv_debug_read": (C.c_int, [vp, C.c_int, vp, C.c_int64]),
         "mv_test_gemm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, P(C.c_float)]),
         "mv_test_gemm_pp": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, P(C.c_float)]),
+        "mv_test_gemm_f32": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, P(C.c_float)]),
         "mv_test_e4m3": (C.c_int, [vp, vp, C.c_int64]),
         "mv_format_records": (C.c_int, [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_char_p, vp, vp, C.c_int64, P(C.c_int64)]),
         "mv_comm_prepare": (C.c_int, [vp]),
@@ -705,6 +709,21 @@ class Engine:
         self._check(self._lib.mv_test_gemm_pp(self._h, int(x8), M, N, K, _ptr(A), _ptr(W), _ptr(bias), _ptr(out), _ptr(out8), iters,
                                               C.byref(ms)), "mv_test_gemm_pp")
         return out, out8, float(ms.value)
+
+    GEMM_F32_ACTS = {"bias": 0, "gelu": 1, "res": 2}
+
+    def test_gemm_f32(self, A: np.ndarray, W: np.ndarray, bias: Optional[np.ndarray], res: Optional[np.ndarray] = None, act: str = "bias", iters: int = 1):
+        """The MV_F32 GEMM on fp32 operands: act(A W^T + bias) (+ res) [M][N] fp32; act "bias" | "gelu" | "res" (M, N % 128, K % 32)."""
+        A, W = _as(A, np.float32), _as(W, np.float32)
+        M, K = A.shape
+        N = W.shape[0]
+        bias = None if bias is None else _as(bias, np.float32)
+        res = None if res is None else _as(res, np.float32)
+        out = np.empty((M, N), np.float32)
+        ms = C.c_float(0)
+        self._check(self._lib.mv_test_gemm_f32(self._h, self.GEMM_F32_ACTS[act], M, N, K, _ptr(A), _ptr(W), _ptr(bias), _ptr(res), _ptr(out), iters,
+                                               C.byref(ms)), "mv_test_gemm_f32")
+        return out, float(ms.value)
 
 
 def device_count() -> int:

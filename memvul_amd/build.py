@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libmemvul_hip.so")
 LIB_PATH_DEV = os.path.join(LIB_DIR, "libmemvul_hip_dev.so")
 DEV_FLAGS = ("-DMEMVUL_DEV_SWITCHES",)
 SOURCES = ["engine.hip"]
-HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", os.path.join(ROOT, "include", "memvul_hip.h")]
+HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", os.path.join(ROOT, "include", "memvul_hip.h")]
 ARCH = "gfx950"
 
 
@@ -68,17 +68,13 @@ def build_fingerprint(extra_flags=()) -> str:
     return "src %s\ncc %s" % (source_fingerprint(extra_flags), hashlib.sha256(cc).hexdigest() if cc is not None else "unknown")
 
 
-def device_code_fingerprint(lib_path: str = None) -> str:
-    """sha256 of the gfx950 code object(s) embedded in the shared library (the clang offload bundle inside .hip_fatbin): what the
-    GPU executes.  Host-only edits of engine.hip leave it unchanged, any kernel change moves it — bench.py keys the counter
-    figures of profiles/pmc_current.json on this line of the stamp."""
-    import hashlib
+def device_code_objects(lib_path: str = None) -> list:
+    """The gfx950 code object(s) embedded in the shared library (the clang offload bundle inside .hip_fatbin), as bytes: what the GPU executes."""
     import struct
 
     data = open(lib_path or LIB_PATH, "rb").read()
     magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    h = hashlib.sha256()
-    found = 0
+    found = []
     i = data.find(magic)
     while i >= 0:
         if i + 32 > len(data):
@@ -97,11 +93,21 @@ def device_code_fingerprint(lib_path: str = None) -> str:
             triple = data[off:off + tsz]
             off += tsz
             if ARCH.encode() in triple:
-                h.update(data[i + o:i + o + size])
-                found += 1
+                found.append(data[i + o:i + o + size])
         i = data.find(magic, i + len(magic))
     if not found:
         raise RuntimeError(f"no {ARCH} code object found in {lib_path or LIB_PATH}")
+    return found
+
+
+def device_code_fingerprint(lib_path: str = None) -> str:
+    """sha256 of the gfx950 code object(s) embedded in the shared library: what the GPU executes.  Host-only edits of engine.hip leave it unchanged,
+    any kernel change moves it — bench.py keys the counter figures of profiles/pmc_current.json on this line of the stamp."""
+    import hashlib
+
+    h = hashlib.sha256()
+    for co in device_code_objects(lib_path):
+        h.update(co)
     return h.hexdigest()
 
 

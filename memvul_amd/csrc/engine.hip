@@ -25,6 +25,7 @@
 #include "attention_v2.h"
 #include "misc_kernels.h"
 #include "match_topk.h"
+#include "ref_f32.h"
 
 namespace {
 
@@ -55,6 +56,8 @@ struct LayerW {
   int sc_qkv = 0, sc_o = 0, sc_1 = 0, sc_2 = 0;
   // MV_F16X8, last layer only: fp32 transposed ([k][n]) weights of the [CLS] tail (misc_kernels.h dense768_kernel)
   float *wqT32 = nullptr, *woT32 = nullptr, *w1T32 = nullptr, *w2T32 = nullptr;
+  // MV_F32 (ref_f32.h): the four GEMM weights as loaded, [n][k] fp32, no LayerNorm folded in (packed QKV with the 1/8 on the Q block: exact)
+  float *wqkv32 = nullptr, *wo32 = nullptr, *w132 = nullptr, *w232 = nullptr;
   float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr;
 };
 
@@ -167,6 +170,7 @@ struct Work {
                               // with the stream of every other row being hi + the lo8 plane of its fp8 planes (gemm.h GemmArgs::out16b) — what the residual GEMMs read back
   float* cls_corr = nullptr;  // ... and 2^11 x their A-side correction term A_lo W_hi^T [2 Bp][3072] (GemmArgs::cls_corr)
   half_t* vlo_sp = nullptr;   // 2^11 x the low parts of V of the special rows [B 12][64][2] (GemmArgs::vlo_sp -> AttnArgs::vlo_sp)
+  float *qkv32 = nullptr, *ctx32 = nullptr, *h32 = nullptr;  // MV_F32: Q | K | V [T][2304], attention context [T][768], GELU output [T][3072], allocated by mv_finalize_weights
   int32_t* tile_both = nullptr;  // cls_aside: per 256-row tile of the pass, non-zero = its sequence is shorter than cls_min_len (GemmArgs::tile_both)
   // in flight on this stream: batches of a resident sweep (check_ready waits for them) and / or a ticket of mv_forward_ragged_begin — its plan, anchor
   // count and staging `st`: `pin` (PINNED, allocated at the set's first ticket) without the outputs it was not asked for
@@ -184,6 +188,7 @@ struct mv_handle {
   bool finalized = false;
   int compute_dtype = MV_F16;
   bool precise = false;    // MV_F16X8: every persistent GEMM adds the fp8 correction sweep (gemm_pp.h X8)
+  bool f32 = false;        // MV_F32: the reference form — every pass through encode_f32_dev (ref_f32.h)
   std::map<std::string, HostTensor> staged;
   std::vector<void*> allocs;
 
@@ -543,6 +548,63 @@ int launch_attention(mv_handle* h, Work& wk, const int32_t* d_lens, int B, int S
   return launch_check(h, "attention");
 }
 
+// ---- MV_F32: the encoder in fp32 (ref_f32.h) ---------------------------------------------------------------------------------------------
+template <int ACT>
+int launch_gemm_f32(mv_handle* h, hipStream_t stream, int cls, const float* A, const float* W, const float* bias, const float* res, float* C, int M, int N, int K) {
+  if (M <= 0 || M % 128 || N <= 0 || N % 128 || K <= 0 || K % 32) return fail(h, MV_ERR_INVALID, "gemm_f32: M,N % 128, K % 32 required");
+  if (ACT == RF_ACT_RES && !res) return fail(h, MV_ERR_STATE, "internal: gemm_f32 residual epilogue without a residual");
+  ProfScope ps(h, stream, cls);
+  hipLaunchKernelGGL((gemm_f32_kernel<ACT>), dim3((unsigned)((M / 128) * (N / 128))), dim3(256), 0, stream, A, W, bias, res, C, M, N, K);
+  return launch_check(h, "gemm_f32");
+}
+
+// One pass in the reference form: the small-pass structure (fp32 stream xres, explicit LayerNorm kernels, natural token order) with every GEMM and the
+// attention in fp32.  No last-layer pruning in this dtype (1/12 of the time of a form that is not run for throughput; one code path): after the last layer
+// xres holds the normalised stream of every token, which is also what the debug taps read.
+int encode_f32_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_lens, int B, int S_in, int n_layers, float* u_out, int pitch) {
+  const mv_config& c = h->cfg;
+  const int Sp = padded_len(S_in);
+  const int64_t M = (int64_t)B * Sp, Mpad = round_up(M, 256);
+  if (S_in > c.max_pos) return fail(h, MV_ERR_INVALID, "sequence longer than max_pos");
+  if (Mpad > h->cap_tokens) return fail(h, MV_ERR_CAPACITY, "B*S exceeds mv_config.max_tokens");
+  if (n_layers < 0 || n_layers > c.layers) n_layers = c.layers;
+  h->dbg_B = B;
+  h->dbg_Sp = Sp;
+  {
+    ProfScope ps(h, wk.stream, KC_EMBED_LN);
+    hipLaunchKernelGGL(embed_ln_kernel<false>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, wk.stream, d_ids, pitch, S_in, Sp, (int)M, c.vocab_size,
+                       h->wemb, h->pemb, h->temb, h->embg, h->embb, c.ln_eps, wk.xres, wk.x16, (float*)nullptr,
+                       (half_t*)nullptr, (uint8_t*)nullptr, (unsigned long long*)nullptr);
+    if (int rc = launch_check(h, "embed_ln")) return rc;
+  }
+  auto run_ln = [&](const float* g, const float* b) -> int {  // all Mpad rows: the rows past M take the residual GEMMs' output like any other and must stay bounded
+    ProfScope ps(h, wk.stream, KC_LN);
+    hipLaunchKernelGGL(ln_kernel<true>, dim3((unsigned)(Mpad / 4)), dim3(256), 0, wk.stream, wk.xres, wk.x16, (int)Mpad, g, b, c.ln_eps, (float*)nullptr);
+    return launch_check(h, "layernorm");
+  };
+  const int Mp = (int)Mpad, H = MV_HIDDEN, I = MV_INTER;
+  for (int l = 0; l < n_layers; ++l) {
+    const LayerW& w = h->L[l];
+    if (int rc = launch_gemm_f32<RF_ACT_NONE>(h, wk.stream, KC_GEMM_QKV, wk.xres, w.wqkv32, w.bqkv, nullptr, wk.qkv32, Mp, 3 * H, H)) return rc;
+    {
+      ProfScope ps(h, wk.stream, KC_ATTENTION);
+      const int units = B * MV_HEADS * (Sp / 32);
+      hipLaunchKernelGGL(attention_f32_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, wk.stream, (const float*)wk.qkv32, d_lens, wk.ctx32, Sp, units);
+      if (int rc = launch_check(h, "attention_f32")) return rc;
+    }
+    if (int rc = launch_gemm_f32<RF_ACT_RES>(h, wk.stream, KC_GEMM_OUT, wk.ctx32, w.wo32, w.bo, wk.xres, wk.xres, Mp, H, H)) return rc;
+    if (int rc = run_ln(w.ln1g, w.ln1b)) return rc;
+    if (int rc = launch_gemm_f32<RF_ACT_GELU>(h, wk.stream, KC_GEMM_FFN1, wk.xres, w.w132, w.b1, nullptr, wk.h32, Mp, I, H)) return rc;
+    if (int rc = launch_gemm_f32<RF_ACT_RES>(h, wk.stream, KC_GEMM_FFN2, wk.h32, w.w232, w.b2, wk.xres, wk.xres, Mp, H, I)) return rc;
+    if (int rc = run_ln(w.ln2g, w.ln2b)) return rc;
+  }
+  if (u_out) {
+    ProfScope ps(h, wk.stream, KC_POOL_HEAD);
+    if (int rc = pool_head(h, wk, wk.xres, (size_t)Sp * MV_HIDDEN, B, u_out)) return rc;
+  }
+  return MV_OK;
+}
+
 // ---- encoder: ids (device) -> u (device, [B][512]); stops after n_layers (<0: all) ------------
 // Two paths, chosen by the size of the pass (pp_selected):
 //   * bench scale: the persistent GEMMs on the two-plane raw stream with the virtual LayerNorm (gemm_pp.h), five launches per
@@ -553,6 +615,7 @@ int launch_attention(mv_handle* h, Work& wk, const int32_t* d_lens, int B, int S
 int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_lens, int min_len, int B, int S_in, int n_layers, float* u_out,
                const PassForm& pf = PassForm(), bool full = false, int pitch = 0) {  // min_len: the shortest sequence of the pass as the HOST knows it (Pass::min_len; 0 = unknown)
   if (pitch <= 0) pitch = S_in;  // ints between the rows of d_ids
+  if (h->f32) return encode_f32_dev(h, wk, d_ids, d_lens, B, S_in, n_layers, u_out, pitch);  // MV_F32: no forms, no monitors, no pruning
   const mv_config& c = h->cfg;
   const int Sp = padded_len(S_in);
   const int64_t M = (int64_t)B * Sp, Mpad = round_up(M, 256);
@@ -1495,12 +1558,13 @@ int mv_load_tensor(mv_handle* h, const char* name, const void* host_ptr, int dty
 int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
   if (!h) return MV_ERR_INVALID;
   if (h->finalized) return fail(h, MV_ERR_STATE, "weights already finalized");
-  if (compute_dtype != MV_F16 && compute_dtype != MV_F16X8)
-    return fail(h, MV_ERR_INVALID, "compute_dtype must be MV_F16 (fp16 MFMA operands, fp32 accumulation) or MV_F16X8 (+ fp8 correction "
-                                   "sweeps); bf16 is a storage dtype of mv_load_tensor only (include/memvul_hip.h)");
+  if (compute_dtype != MV_F16 && compute_dtype != MV_F16X8 && compute_dtype != MV_F32)
+    return fail(h, MV_ERR_INVALID, "compute_dtype must be MV_F16 (fp16 MFMA operands, fp32 accumulation), MV_F16X8 (+ fp8 correction "
+                                   "sweeps) or MV_F32 (the reference form); bf16 is a storage dtype of mv_load_tensor only (include/memvul_hip.h)");
   const bool precise = compute_dtype == MV_F16X8;
+  const bool f32 = compute_dtype == MV_F32;  // the 16-bit weights, the folded ones and the second stream plane are not built
   if (!precise && h->form != MV_FORM_DEFAULT)
-    return fail(h, MV_ERR_STATE, "the safe and the guarded form (MEMVUL_FORM / mv_set_form) are forms of compute dtype MV_F16X8: they cannot be combined with MV_F16");
+    return fail(h, MV_ERR_STATE, "the safe and the guarded form (MEMVUL_FORM / mv_set_form) are forms of compute dtype MV_F16X8: they cannot be combined with MV_F16 or MV_F32");
   HIPCHK(h, hipSetDevice(h->device));
   const hipStream_t s0 = h->work[0].stream;  // (the uploads)
   const mv_config& c = h->cfg;
@@ -1540,7 +1604,8 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
         pack[(size_t)(H * H + i)] = t2->data[(size_t)i];
         pack[(size_t)(2 * H * H + i)] = t3->data[(size_t)i];
       }
-      if ((rc = upload_f16(h, s0, &w.wqkv, pack.data(), 3 * H * H))) return rc;
+      if (f32 && (rc = upload_f32(h, s0, &w.wqkv32, pack.data(), 3 * H * H))) return rc;
+      if (!f32 && (rc = upload_f16(h, s0, &w.wqkv, pack.data(), 3 * H * H))) return rc;
       wqkv_host = pack;
     }
     if ((rc = need(h, q + "attention.self.query.bias", {H}, &t))) return rc;
@@ -1556,7 +1621,7 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
       if ((rc = upload_f32(h, s0, &w.bqkv, pack.data(), 3 * H))) return rc;
       bqkv_host = pack;
     }
-    {  // the LayerNorm in front of this layer's QKV projection: the embedding LayerNorm or the previous layer's output LayerNorm
+    if (!f32) {  // the LayerNorm in front of this layer's QKV projection: the embedding LayerNorm or the previous layer's output LayerNorm
       const std::string lnk = l == 0 ? P + "embeddings.LayerNorm." : P + "encoder.layer." + std::to_string(l - 1) + ".output.LayerNorm.";
       const HostTensor *tg = nullptr, *tb = nullptr;
       if ((rc = need(h, lnk + "weight", {H}, &tg))) return rc;
@@ -1568,7 +1633,8 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
       if ((rc = upload_f32(h, s0, &w.bqkv_f, bf.data(), 3 * H))) return rc;
     }
     NEED(q + "attention.output.dense.weight", H, H);
-    if ((rc = upload_f16(h, s0, &w.wo, t->data.data(), H * H))) return rc;
+    if (f32 && (rc = upload_f32(h, s0, &w.wo32, t->data.data(), H * H))) return rc;
+    if (!f32 && (rc = upload_f16(h, s0, &w.wo, t->data.data(), H * H))) return rc;
     if (precise && (rc = upload_x8_weight(h, s0, &w.wo8, &w.sc_o, t->data.data(), H, H))) return rc;
     NEED(q + "attention.output.dense.bias", H);
     if ((rc = upload_f32(h, s0, &w.bo, t->data.data(), H))) return rc;
@@ -1577,10 +1643,11 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
     NEED(q + "attention.output.LayerNorm.bias", H);
     if ((rc = upload_f32(h, s0, &w.ln1b, t->data.data(), H))) return rc;
     NEED(q + "intermediate.dense.weight", I, H);
-    if ((rc = upload_f16(h, s0, &w.w1, t->data.data(), I * H))) return rc;
+    if (f32 && (rc = upload_f32(h, s0, &w.w132, t->data.data(), I * H))) return rc;
+    if (!f32 && (rc = upload_f16(h, s0, &w.w1, t->data.data(), I * H))) return rc;
     NEED(q + "intermediate.dense.bias", I);
     if ((rc = upload_f32(h, s0, &w.b1, t->data.data(), I))) return rc;
-    {  // FFN-1 with the attention-output LayerNorm folded in
+    if (!f32) {  // FFN-1 with the attention-output LayerNorm folded in
       const HostTensor *tw = nullptr, *tg = nullptr, *tb = nullptr;
       if ((rc = need(h, q + "intermediate.dense.weight", {I, H}, &tw))) return rc;
       if ((rc = need(h, q + "attention.output.LayerNorm.weight", {H}, &tg))) return rc;
@@ -1592,7 +1659,8 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
       if ((rc = upload_f32(h, s0, &w.b1_f, bf.data(), I))) return rc;
     }
     NEED(q + "output.dense.weight", H, I);
-    if ((rc = upload_f16(h, s0, &w.w2, t->data.data(), H * I))) return rc;
+    if (f32 && (rc = upload_f32(h, s0, &w.w232, t->data.data(), H * I))) return rc;
+    if (!f32 && (rc = upload_f16(h, s0, &w.w2, t->data.data(), H * I))) return rc;
     if (precise && (rc = upload_x8_weight(h, s0, &w.w28, &w.sc_2, t->data.data(), H, I))) return rc;
     NEED(q + "output.dense.bias", H);
     if ((rc = upload_f32(h, s0, &w.b2, t->data.data(), H))) return rc;
@@ -1638,7 +1706,17 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
   NEED("_projector.weight", 2, 3 * (int64_t)h->P);
   if ((rc = upload_f32(h, s0, &h->Wm, t->data.data(), 2 * 3 * (int64_t)h->P))) return rc;
 #undef NEED
-  if (!precise) {  // MV_F16: the lo fp16 plane of the two-plane raw stream (MV_F16X8 keeps the stream's low part in the lo8 plane of x8 + st_lo: gemm.h GemmArgs::out16b)
+  if (f32) {  // MV_F32: the fp32 planes of one pass, 6144 floats per token (1.6 GB per workspace set at 65 536 tokens)
+    for (int wi = 0; wi < h->n_alloc; ++wi) {
+      Work& wk = h->work[wi];
+      rc = dev_alloc(h, wk.stream, &wk.qkv32, h->cap_tokens * 3 * MV_HIDDEN);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.ctx32, h->cap_tokens * MV_HIDDEN);
+      if (rc == MV_OK) rc = dev_alloc(h, wk.stream, &wk.h32, h->cap_tokens * MV_INTER);
+      if (rc == MV_OK && hipStreamSynchronize(wk.stream) != hipSuccess) rc = MV_ERR_HIP;
+      if (rc != MV_OK) return rc;
+    }
+  }
+  if (!precise && !f32) {  // MV_F16: the lo fp16 plane of the two-plane raw stream (MV_F16X8 keeps the stream's low part in the lo8 plane of x8 + st_lo: gemm.h GemmArgs::out16b)
     for (int wi = 0; wi < h->n_alloc; ++wi) {
       Work& wk = h->work[wi];
       rc = dev_alloc(h, wk.stream, &wk.xlo, h->cap_tokens * MV_HIDDEN);
@@ -1668,6 +1746,7 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype) try {
     }
   }
   h->precise = precise;
+  h->f32 = f32;
   h->staged.clear();
   h->compute_dtype = compute_dtype;
   h->finalized = true;
@@ -2128,7 +2207,7 @@ int mv_set_form(mv_handle* h, int form) try {
   if (form != MV_FORM_DEFAULT && form != MV_FORM_SAFE && form != MV_FORM_GUARDED)
     return fail(h, MV_ERR_INVALID, "mv_set_form: MV_FORM_DEFAULT (0), MV_FORM_SAFE (1) or MV_FORM_GUARDED (2)");
   if (form != MV_FORM_DEFAULT && h->finalized && !h->precise)
-    return fail(h, MV_ERR_STATE, "mv_set_form: MV_FORM_SAFE and MV_FORM_GUARDED are forms of compute dtype MV_F16X8; this handle was finalized as MV_F16");
+    return fail(h, MV_ERR_STATE, "mv_set_form: MV_FORM_SAFE and MV_FORM_GUARDED are forms of compute dtype MV_F16X8; this handle was finalized as MV_F16 or MV_F32");
   h->form = form;  // (no synchronisation: passes already enqueued were built with the form of their time)
   return MV_OK;
 } catch (...) { return on_exception(h); }
@@ -2224,6 +2303,8 @@ int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes) try {
   const int64_t T = (int64_t)h->dbg_B * h->dbg_Sp;
   const void* src = nullptr;
   int64_t avail = 0;
+  if (h->f32 && buffer >= 1 && buffer <= 9)
+    return fail(h, MV_ERR_INVALID, "mv_debug_read: buffers 1 - 9 are the fp16 planes of MV_F16 / MV_F16X8; an MV_F32 handle has buffer 0 (hidden fp32) and 10 (embedding)");
   switch (buffer) {
     case 0: src = wk.xres; avail = T * MV_HIDDEN * 4; break;
     case 1: src = wk.x16; avail = T * MV_HIDDEN * 2; break;
@@ -2287,6 +2368,57 @@ int mv_test_gemm(mv_handle* h, int variant, int M, int N, int K, const uint16_t*
     if (se != hipSuccess) rc = fail(h, MV_ERR_HIP, std::string("test gemm copy: ") + hipGetErrorString(se));
   }
   dev_free(h, dA); dev_free(h, dW); dev_free(h, dB); dev_free(h, dC);
+  return rc;
+} catch (...) { return on_exception(h); }
+
+// The MV_F32 GEMM (ref_f32.h) on caller data: C = act(A W^T + bias) (+ res), everything fp32.  act 0 bias only, 1 GELU, 2 + res.
+int mv_test_gemm_f32(mv_handle* h, int act, int M, int N, int K, const float* A, const float* W, const float* bias, const float* res, float* C, int iters,
+                     float* ms) try {
+  if (!h || !A || !W || M <= 0 || N <= 0 || K <= 0) return fail(h, MV_ERR_INVALID, "mv_test_gemm_f32: bad argument");
+  if (act < RF_ACT_NONE || act > RF_ACT_RES || (act == RF_ACT_RES && !res)) return fail(h, MV_ERR_INVALID, "mv_test_gemm_f32: act 0 (bias), 1 (GELU) or 2 (+ res, res required)");
+  if (M % 128 || N % 128 || K % 32) return fail(h, MV_ERR_INVALID, "mv_test_gemm_f32: M,N % 128 and K % 32 required");
+  HIPCHK(h, hipSetDevice(h->device));
+  const hipStream_t s0 = h->work[0].stream;
+  float *dA = nullptr, *dW = nullptr, *dB = nullptr, *dR = nullptr, *dC = nullptr;
+  int rc;
+  if ((rc = dev_alloc(h, s0, &dA, (int64_t)M * K, false))) return rc;
+  if ((rc = dev_alloc(h, s0, &dW, (int64_t)N * K, false))) return rc;
+  if ((rc = dev_alloc(h, s0, &dB, N))) return rc;
+  if ((rc = dev_alloc(h, s0, &dR, (int64_t)M * N))) return rc;
+  if ((rc = dev_alloc(h, s0, &dC, (int64_t)M * N))) return rc;
+  HIPCHK(h, hipMemcpyAsync(dA, A, (size_t)M * K * 4, hipMemcpyHostToDevice, s0));
+  HIPCHK(h, hipMemcpyAsync(dW, W, (size_t)N * K * 4, hipMemcpyHostToDevice, s0));
+  if (bias) HIPCHK(h, hipMemcpyAsync(dB, bias, (size_t)N * 4, hipMemcpyHostToDevice, s0));
+  if (res) HIPCHK(h, hipMemcpyAsync(dR, res, (size_t)M * N * 4, hipMemcpyHostToDevice, s0));
+  if (iters < 1) iters = 1;
+  hipEvent_t e0, e1;
+  hipEventCreate(&e0);
+  hipEventCreate(&e1);
+  auto run = [&]() -> int {
+    switch (act) {
+      case RF_ACT_GELU: return launch_gemm_f32<RF_ACT_GELU>(h, s0, KC_TEST_GEMM, dA, dW, dB, nullptr, dC, M, N, K);
+      case RF_ACT_RES: return launch_gemm_f32<RF_ACT_RES>(h, s0, KC_TEST_GEMM, dA, dW, dB, dR, dC, M, N, K);
+      default: return launch_gemm_f32<RF_ACT_NONE>(h, s0, KC_TEST_GEMM, dA, dW, dB, nullptr, dC, M, N, K);
+    }
+  };
+  rc = run();  // warm-up / correctness launch
+  if (rc == MV_OK) {
+    hipEventRecord(e0, s0);
+    for (int i = 0; i < iters && rc == MV_OK; ++i) rc = run();
+    hipEventRecord(e1, s0);
+  }
+  hipError_t se = hipStreamSynchronize(s0);
+  float t = 0.f;
+  hipEventElapsedTime(&t, e0, e1);
+  hipEventDestroy(e0);
+  hipEventDestroy(e1);
+  if (ms) *ms = t / (float)iters;
+  if (rc == MV_OK && se != hipSuccess) rc = fail(h, MV_ERR_HIP, std::string("test gemm_f32: ") + hipGetErrorString(se));
+  if (rc == MV_OK && C) {
+    se = hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost);
+    if (se != hipSuccess) rc = fail(h, MV_ERR_HIP, std::string("test gemm_f32 copy: ") + hipGetErrorString(se));
+  }
+  dev_free(h, dA); dev_free(h, dW); dev_free(h, dB); dev_free(h, dR); dev_free(h, dC);
   return rc;
 } catch (...) { return on_exception(h); }
 
