@@ -137,6 +137,7 @@ def test_the_rounding_model_prices_the_per_sequence_rule(golden_dir):
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
     import r06_make_sink_refs as mk6
     from memvul_amd import synth
+    from oracle import concentration as conc
     from oracle import memvul_oracle as orc
     from oracle import precision_model as pm
 
@@ -150,23 +151,10 @@ def test_the_rounding_model_prices_the_per_sequence_rule(golden_dir):
     mask, amask = synth.mask_from_lens(lens, ids.shape[1]), synth.mask_from_lens(alens, LA)
 
     def items_over(I, L, M):
-        """(exact embeddings, items over 0.25 per sequence): a recording format in the place of P's rounding, for the length of this call."""
-        spy = []
-        pm.FORMATS["spy"] = lambda x: (spy.append(x.copy()), x)[1]
-        try:
-            u = pm.instance_forward(w, I, M, pm.engine_formats(12, "exact", p="spy"))
-        finally:
-            del pm.FORMATS["spy"]
-        assert len(spy) == 12
-        over = np.zeros(len(L), int)
-        for e in spy:
-            p = e[:, :, 0, :] / e[:, :, 0, :].sum(-1, keepdims=True)  # [B, heads, S]: the [CLS] row
-            for b in range(len(L)):
-                q = p[b].copy()
-                q[:, 0] = 0
-                q[:, L[b] - 1] = 0
-                over[b] += int(((q ** 2).sum(-1) > 0.25).sum())
-        return u, over
+        """(exact embeddings, items over 0.25 per sequence): oracle/concentration.py, a recording format in the place of P's rounding, for the length of this call."""
+        coll, u = conc.cls_collision(w, I, L, forward=pm.instance_forward, with_output=True)
+        assert coll.shape == (12, len(L), 12) and np.array_equal(conc.orc_mask(L, I.shape[1]), M)
+        return u, (coll > 0.25).sum(axis=(0, 2))
 
     u_ref, over = items_over(ids, lens, mask)
     v_ref, a_over = items_over(aids, alens, amask)
