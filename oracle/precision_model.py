@@ -245,7 +245,7 @@ def _ln_stats(x, eps):
 
 
 def encode(w, ids, mask, cfg: Optional[Dict[str, List[str]]], heads=12, eps=1e-12, fold_ln=True, cls_side=None, cls_raw_kv=False,
-           cls_from_layer=0, cls_fix=False, special="cls", special_v=None, special_a_qkv=True, res_special=None):
+           cls_from_layer=0, cls_fix=False, special="cls", special_v=None, special_a_qkv=True, res_special=None, taps: Optional[dict] = None):
     """float64 BERT forward with the engine's rounding points (``cfg`` None = exact).  ``fold_ln``: the QKV / FFN-1
     weights are rounded AFTER the preceding LayerNorm is folded in (W'' = W gamma - rowmean, gemm_pp.h) and the A operand
     is the raw (pre-LayerNorm) stream, as on the engine's persistent-GEMM path.  ``cls_fix``: the [CLS]-row A-side term of the shipped form
@@ -253,7 +253,8 @@ def encode(w, ids, mask, cfg: Optional[Dict[str, List[str]]], heads=12, eps=1e-1
     also its last token: the two tokens trained BERT heads use as attention sinks).  ``special_v`` (a format name, e.g. "f16x2"): V of the special rows is
     stored in that format instead of the ``v`` knob's (the attention kernel adds p[:, special] V_lo[special]: two rank-1 updates per head).  ``res_special`` (a format
     name): the special rows of the STORED residual stream keep that format while every other row follows the ``res`` knob (a model-side experiment of round 6: the stream
-    of the ordinary rows as its hi plane alone)."""
+    of the ordinary rows as its hi plane alone).  ``taps`` (a dict): receives the NORMALISED stream of the main path after the embeddings (key 0) and after every
+    layer (key n = after n layers: what the engine's debug tap 0 holds after ``debug_encode(ids, lens, n)``); nothing else changes."""
     W = lambda k: w[PFX + k].astype(np.float64)  # noqa: E731
     L = orc.n_layers(w)
     if cfg is None:
@@ -285,6 +286,13 @@ def encode(w, ids, mask, cfg: Optional[Dict[str, List[str]]], heads=12, eps=1e-1
     rc = r[:, 0].copy()
     gc, bc = g, b
     RS = FORMATS[cls_side] if cls_side else None
+
+    def tap(n, r, g, b):
+        if taps is not None:
+            mu, rstd = _ln_stats(r, eps)
+            taps[n] = (r - mu) * rstd * g + b
+
+    tap(0, r, g, b)
 
     def consumer(r_raw, g, b, Wm, bias, wknob, aknob, l):
         """rstd * (W'' · round(r)) + b'  ==  W · LN(r) + bias  up to the roundings"""
@@ -353,6 +361,7 @@ def encode(w, ids, mask, cfg: Optional[Dict[str, List[str]]], heads=12, eps=1e-1
             rc = RS(hc) @ RS(W(p + "output.dense.weight")).T + W(p + "output.dense.bias") + x1c
         g, b = W(p + "output.LayerNorm.weight"), W(p + "output.LayerNorm.bias")
         gc, bc = g, b
+        tap(l + 1, r, g, b)
     if cls_side:
         r = r.copy()
         r[:, 0] = rc

@@ -204,10 +204,16 @@ def test_attention_persistent_item_loop(gu, B, S, compute):
     assert err < (8e-3 if compute == "precise" else 1.2e-2)  # measured 5.4e-3 / 9.4e-3 (profiles/r04_f_parity_records.jsonl)
 
 
-def test_match_and_topk_vs_oracle(gu):
+def _same_engine(gu, same_idx, **kw):
+    """same_idx = 0: the engine every matcher test uses; 1: one created with mv_config.same_idx = 1 — the index of "same" in the label vocabulary
+    (model_memory.py:61), which a real archive can have either way.  match_topk_kernel branches on it for ps / pq and for the best[2 b + same_idx] writes."""
+    return gu.engine_for(L2, WK, **kw) if same_idx == 0 else gu.engine_for(L2, WK, same_idx=1, **kw)
+
+
+def _match_and_topk_vs_oracle(gu, same_idx):
     rng = np.random.default_rng(5)
     dims, w = gu.weights_for(L2, WK)
-    eng = gu.engine_for(L2, WK, max_anchors=128)
+    eng = _same_engine(gu, same_idx, max_anchors=128)
     for B, G in [(1, 1), (5, 7), (37, 124), (64, 64)]:
         u = np.maximum(rng.standard_normal((B, 512)), 0).astype(np.float32)
         v = np.maximum(rng.standard_normal((G, 512)), 0).astype(np.float32)
@@ -215,15 +221,21 @@ def test_match_and_topk_vs_oracle(gu):
             v[3] = v[1]  # exact tie between anchors 1 and 3: the lower index must win
         eng.anchor_set(v)
         out = eng.match(u)
-        logits, p, best, idx = orc.match(u, v, w[synth.KEY_MATCH_W], same_idx=0)
+        logits, p, best, idx = orc.match(u, v, w[synth.KEY_MATCH_W], same_idx=same_idx)
         e = float(np.abs(out["logits"] - logits).max())
-        gu.record("match", B=B, G=G, max_err=e)
+        gu.record("match", B=B, G=G, same_idx=same_idx, max_err=e)
         assert e < 2e-5
         assert np.abs(out["probs"] - p).max() < 1e-5
         # GPU-side consistency (bit-exact): best is the row of probs at best_idx, best_idx the first arg-max
-        ps = out["probs"][:, :, 0]
+        ps = out["probs"][:, :, same_idx]
         assert np.array_equal(out["best_idx"], np.argmax(ps, axis=1).astype(np.int32))
         assert np.array_equal(out["best"], out["probs"][np.arange(B), out["best_idx"]])
+        if G > 3:  # the tie: anchor 3 scores exactly what anchor 1 scores and never wins over it
+            assert np.array_equal(ps[:, 1], ps[:, 3]) and not (out["best_idx"] == 3).any()
+        if same_idx == 1:  # (against the oracle's own selection wherever its margin is clear)
+            srt = -np.sort(-p[:, :, 1], axis=1)
+            clear = np.ones(B, bool) if G == 1 else (srt[:, 0] - srt[:, 1] > 1e-5)
+            assert np.array_equal(out["best_idx"][clear], idx[clear].astype(np.int32)) and np.abs(out["best"] - best)[clear].max() < 1e-5
         k = min(5, G)
         tp, ti = eng.topk(u, k)
         rp, ri = orc.topk_match(ps, k)
@@ -231,26 +243,33 @@ def test_match_and_topk_vs_oracle(gu):
     eng.anchor_reset()
 
 
-@pytest.mark.parametrize("B,G", [(256, 1000), (512, 1000), (37, 257), (300, 124), (3, 1024), (5, 128), (9, 129), (4, 256), (66, 513)])
-def test_fused_match_topk_at_configs4_size(gu, B, G):
-    """BASELINE.json configs[4]: 1000-anchor synthetic bank, fused match + top-k (k = 1, 5, 10): the k best anchors per
-    issue report against the oracle (argsort of the oracle's own P(same), ties to the lower index), the best-anchor
-    outputs of mv_match against the same kernel's full probabilities, exact duplicates in the bank (ties across chunk
-    boundaries) and a NaN row (ranks first, index stays valid)."""
+def test_match_and_topk_vs_oracle(gu):
+    _match_and_topk_vs_oracle(gu, 0)
+
+
+def test_match_and_topk_vs_oracle_same_idx_1(gu):
+    """mv_config.same_idx = 1: logits / probs as ever, P(same) = column 1 in best_idx, best, top-k and the duplicate-anchor tie."""
+    _match_and_topk_vs_oracle(gu, 1)
+
+
+FUSED_SHAPES = [(256, 1000), (512, 1000), (37, 257), (300, 124), (3, 1024), (5, 128), (9, 129), (4, 256), (66, 513)]
+
+
+def _fused_match_topk(gu, B, G, same_idx):
     rng = np.random.default_rng(G + B)
     dims, w = gu.weights_for(L2, WK)
-    eng = gu.engine_for(L2, WK, max_anchors=1024, max_batch=512)
+    eng = _same_engine(gu, same_idx, max_anchors=1024, max_batch=512)
     u = np.maximum(rng.standard_normal((B, 512)), 0).astype(np.float32) * np.float32(0.5)
     v = synth.make_anchor_bank(G)
     if G > 300:
         v[290] = v[7]; v[G - 1] = v[7]   # the same anchor in three different 256-anchor chunks
     eng.anchor_set(v)
     out = eng.match(u)
-    logits, p, best, idx = orc.match(u, v, w[synth.KEY_MATCH_W], same_idx=0)
+    logits, p, best, idx = orc.match(u, v, w[synth.KEY_MATCH_W], same_idx=same_idx)
     e = float(np.abs(out["logits"] - logits).max())
-    gu.record("match_topk", B=B, G=G, max_logit_err=e)
+    gu.record("match_topk", B=B, G=G, same_idx=same_idx, max_logit_err=e)
     assert e < 2e-5 and np.abs(out["probs"] - p).max() < 1e-5
-    ps = out["probs"][:, :, 0]
+    ps = out["probs"][:, :, same_idx]
     assert np.array_equal(out["best_idx"], np.argmax(ps, axis=1).astype(np.int32))
     assert np.array_equal(out["best"], out["probs"][np.arange(B), out["best_idx"]])
     for k in (1, 5, 10, 64):  # 64 = MK_KMAX (chunks x k <= 1024, match_dev: four chunks x 64 = one merge pass of four candidates per lane)
@@ -259,15 +278,94 @@ def test_fused_match_topk_at_configs4_size(gu, B, G):
         tp, ti = eng.topk(u, k)
         rp, ri = orc.topk_match(ps, k)          # the GPU's own probabilities: the selection must be exact
         assert np.array_equal(ti, ri.astype(np.int32)) and np.array_equal(tp, rp), k
-        op, oi = orc.topk_match(p[:, :, 0], k)  # and against the oracle's probabilities wherever the margins are clear
-        srt = -np.sort(-p[:, :, 0], axis=1)[:, :k + 1]
+        op, oi = orc.topk_match(p[:, :, same_idx], k)  # and against the oracle's probabilities wherever the margins are clear
+        srt = -np.sort(-p[:, :, same_idx], axis=1)[:, :k + 1]
         clear = (np.abs(np.diff(srt, axis=1)) > 1e-5).all(1) if G > k else np.ones(B, bool)
         assert np.array_equal(ti[clear], oi[clear].astype(np.int32))
     if G > 300:
         assert (np.diff(np.stack([ps[:, 7], ps[:, 290], ps[:, G - 1]]), axis=0) == 0).all()  # duplicates score identically
+        assert not np.isin(out["best_idx"], (290, G - 1)).any()  # ... and the lowest index of the three is the one that can win
     # a NaN issue report: every score NaN -> torch.argmax semantics (index 0), no out-of-range index
     un = u[:2].copy()
     un[0, 5] = np.nan
     o2 = eng.match(un)
     assert o2["best_idx"][0] == 0 and np.isnan(o2["best"][0]).all() and o2["best_idx"][1] == out["best_idx"][1]
+    assert np.isnan(o2["probs"][0, :, same_idx]).all() and np.array_equal(o2["best"][1], out["best"][1])
+    eng.anchor_reset()
+
+
+@pytest.mark.parametrize("B,G", FUSED_SHAPES)
+def test_fused_match_topk_at_configs4_size(gu, B, G):
+    """BASELINE.json configs[4]: 1000-anchor synthetic bank, fused match + top-k (k = 1, 5, 10): the k best anchors per
+    issue report against the oracle (argsort of the oracle's own P(same), ties to the lower index), the best-anchor
+    outputs of mv_match against the same kernel's full probabilities, exact duplicates in the bank (ties across chunk
+    boundaries) and a NaN row (ranks first, index stays valid)."""
+    _fused_match_topk(gu, B, G, 0)
+
+
+@pytest.mark.parametrize("B,G", FUSED_SHAPES)
+def test_fused_match_topk_at_configs4_size_same_idx_1(gu, B, G):
+    """The same with mv_config.same_idx = 1: P(same) is column 1 — the rank key, the chunk candidates (part_p / part_q), the merge and the best[2 b + same_idx]
+    writes all take the other branch."""
+    _fused_match_topk(gu, B, G, 1)
+
+
+def test_same_idx_1_at_the_768_wide_instantiation(gu):
+    """use_header = False (mv_config.proj_dim = 768) with same_idx = 1, once: the matcher alone through the 256-anchor chunks + merge (G = 300)."""
+    dk, wk = dict(layers=2, vocab_size=2048), dict(qk_scale=3.0, match_scale=4.0, use_header=False)
+    dims, w = gu.weights_for(dk, wk)
+    eng = gu.engine_for(dk, wk, proj_dim=768, same_idx=1, max_tokens=16384, max_batch=64, max_anchors=300)
+    rng = np.random.default_rng(11)
+    uu = np.tanh(rng.standard_normal((37, 768))).astype(np.float32)
+    vv = np.tanh(rng.standard_normal((300, 768))).astype(np.float32)
+    vv[290] = vv[7]
+    eng.anchor_set(vv)
+    o = eng.match(uu)
+    lg, pp, bb, ii = orc.match(uu, vv, w[synth.KEY_MATCH_W], same_idx=1)
+    assert np.abs(o["logits"] - lg).max() < 5e-5 and np.abs(o["probs"] - pp).max() < 1e-5
+    ps = o["probs"][:, :, 1]
+    assert np.array_equal(o["best_idx"], np.argmax(ps, axis=1).astype(np.int32))
+    assert np.array_equal(o["best"], o["probs"][np.arange(37), o["best_idx"]])
+    assert np.array_equal(ps[:, 7], ps[:, 290]) and not (o["best_idx"] == 290).any()
+    tp, ti = eng.topk(uu, 5)
+    rp, ri = orc.topk_match(ps, 5)
+    assert np.array_equal(ti, ri.astype(np.int32)) and np.array_equal(tp, rp)
+    un = uu[:2].copy()
+    un[0, 5] = np.nan
+    o2 = eng.match(un)
+    assert o2["best_idx"][0] == 0 and np.isnan(o2["best"][0]).all() and o2["best_idx"][1] == o["best_idx"][1]
+    eng.anchor_reset()
+
+
+@pytest.mark.parametrize("compute", ["precise", "f16"])
+def test_same_idx_1_through_forward_and_the_resident_sweep(gu, compute):
+    """P(same) as mv_forward's best / best_idx and as the resident sweep hands it out (best, best_idx, the kept probabilities; one and two streams) must be
+    probs[:, :, 1] bit for bit on an engine created with same_idx = 1 — and the full logits / probs must be those of a same_idx = 0 engine (the index selects
+    a column, it changes no arithmetic)."""
+    dk, wk = dict(layers=2, vocab_size=2048), dict(qk_scale=2.0, match_scale=6.0)
+    dims, w = gu.weights_for(dk, wk)
+    kw = dict(max_tokens=24 * 256, max_batch=512, max_anchors=32)
+    ids, lens = synth.make_ids(70, 256, dims.vocab_size, ragged=True, min_len=120)
+    bank = synth.make_anchor_bank(9)
+    e0 = gu.engine_for(dk, wk, compute_dtype=compute, **kw)
+    e0.anchor_set(bank)
+    ref0 = e0.forward(ids, lens)
+    e0.anchor_reset()
+    eng = gu.engine_for(dk, wk, compute_dtype=compute, same_idx=1, **kw)
+    eng.anchor_set(bank)
+    ref = eng.forward(ids, lens)
+    assert np.array_equal(ref["logits"], ref0["logits"]) and np.array_equal(ref["probs"], ref0["probs"])
+    p1 = ref["probs"][:, :, 1]
+    n = np.arange(len(lens))
+    assert np.array_equal(ref["best_idx"], np.argmax(p1, axis=1).astype(np.int32))
+    assert np.array_equal(ref["best"], ref["probs"][n, ref["best_idx"]])
+    assert not np.array_equal(ref["best_idx"], ref0["best_idx"])  # (the two columns rank the anchors in opposite orders: the index does something)
+    for streams in (1, 2):
+        eng.set_streams(streams)
+        eng.corpus_upload(ids, lens)
+        eng.corpus_run(0, len(lens), 512, keep_probs=True)
+        best, idx, ps = eng.corpus_results(0, len(lens), with_probs=True)
+        assert np.array_equal(ps, p1), streams
+        assert np.array_equal(idx, ref["best_idx"]) and np.array_equal(best, ref["best"]), streams
+    eng.set_streams(2)
     eng.anchor_reset()

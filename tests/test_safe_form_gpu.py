@@ -14,6 +14,8 @@ import pytest
 from memvul_amd import synth
 from oracle import memvul_oracle as orc
 
+from stage_kit import attention64 as _attention64  # (shared with tests/test_stage_parity_gpu.py)
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -185,17 +187,6 @@ def test_attention_item_loop_in_the_safe_form(gu, B, S):
     err = float(np.abs(ctx - taps["l0_ctx"])[mask].max())
     gu.record("safe_form_attention_items", B=B, S=S, max_err=err)
     assert err < 8e-3, err
-
-
-def _attention64(q, k, v, lens, round_p):
-    """softmax(q k^T + additive mask) v in float64 per (row, head): q, k [B, 12, S, 64] (q carries the folded 1 / 8), v [B, 12, S, 64].  round_p: the
-    un-normalised probabilities exp(s - max) rounded to fp16 in the numerator, the row sum from the unrounded ones (what a one-plane kernel computes)."""
-    B, H, S, D = q.shape
-    s = np.einsum("bhqd,bhkd->bhqk", q, k)
-    s = s + np.where(np.arange(S)[None, :] < np.asarray(lens)[:, None], 0.0, -10000.0)[:, None, None, :]
-    p = np.exp(s - s.max(-1, keepdims=True))
-    num = p.astype(np.float16).astype(np.float64) if round_p else p
-    return np.einsum("bhqk,bhkd->bhqd", num, v) / p.sum(-1, keepdims=True)
 
 
 @pytest.mark.parametrize("S", [128, 192, 256, 384, 512])
