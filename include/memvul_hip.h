@@ -93,6 +93,8 @@ typedef struct mv_config {
  *                             mv_finalize_weights(MV_F16) fail.
  *                             In the safe form MEMVUL_CLS_ASIDE, MEMVUL_CLS_ASIDE_MIN_LEN and MEMVUL_QKV_ASIDE have no effect (it is their most conservative setting).
  * (The seventh switch of the product, MEMVUL_COMPUTE = precise | f16 | f32 (+ aliases), is read by the Python surface: memvul_amd/binding.py default_compute.)
+ * (So are MEMVUL_ON_SINK = warn | safe and MEMVUL_SINK_CENSUS = 0 | 1 — binding.py on_sink_policy / sink_census_policy; the latter calls mv_sink_census_enable
+ * after mv_finalize_weights.)
  * Development A/B knobs (kernel path forced at test sizes, raster, grid share, one-plane short passes) exist only in the -DMEMVUL_DEV_SWITCHES build
  * (libmemvul_hip_dev.so: memvul_amd/build.py, loaded by the GPU tests and A/B scripts that need them); this library does not read them. */
 int mv_create(int device, const mv_config* cfg, mv_handle** out);
@@ -250,6 +252,20 @@ int mv_x8_saturation(mv_handle* h, int64_t* clamped, int reset);
  * the safe form keeps counting, with the same meaning.  MV_FORM_GUARDED makes that choice per sequence from the same items (mv_set_form).
  * No reference counterpart (the reference computes in fp32). */
 int mv_attention_concentration(mv_handle* h, float* max_collision, int64_t* items_over, int64_t* items_total, int reset);
+
+/* MV_F16X8 only, in the default, safe and guarded forms (MV_ERR_STATE on a handle finalized as MV_F16 or MV_F32, and before mv_finalize_weights).  The sink
+ * census: WHICH token the items counted by *items_over above sit on.  While it is on, every pass adds one small kernel per layer whose attention feeds the
+ * concentration monitor (memvul_amd/csrc/sink_census.h: a reader of the Q / K planes the pass holds; the rescoring passes of the guarded form add nothing): for
+ * every (sequence, head, layer) item whose collision mass of the [CLS] row on ordinary keys exceeds 0.25 it finds the ordinary token position with the largest
+ * share p* of that row (ties: the lowest position) and adds, with integer atomics (the result depends on neither scheduling nor batching nor streams),
+ * items[token id] += 1, share_q20[token id] += round(p* 2^20) and by_head[layer][head] += 1.  The buffers are allocated at the first enable, sized by
+ * mv_config.vocab_size; `on` is read on the host when a pass is enqueued.  Off (the default) costs a pass one host-side test per layer.  The kernel recomputes
+ * the row from the hi planes of Q and K: an item within rounding of the threshold may be counted here and not by the monitor, or the other way round.
+ * mv_sink_census_read waits for the work in flight, then copies items uint32 [vocab], share_q20 uint64 [vocab] and by_head uint32 [layers][12] (any of them may
+ * be NULL); vocab != mv_config.vocab_size or layers_x_heads != mv_config.layers * 12 -> MV_ERR_INVALID; before the first enable -> MV_ERR_STATE; reset != 0
+ * zeroes all three.  No reference counterpart (the reference computes in fp32). */
+int mv_sink_census_enable(mv_handle* h, int on);
+int mv_sink_census_read(mv_handle* h, uint32_t* items, uint64_t* share_q20, int vocab, uint32_t* by_head, int layers_x_heads, int reset);
 
 /* ---- multi-GPU exchange (the reference is single-process, predict_memory.py:103) --------------------
  * One process per GPU, contiguous corpus shards, no data-path collective; the ONE exchange is an all-gather of the

@@ -88,7 +88,20 @@ def _engine_dims(sd: Dict[str, np.ndarray]) -> Dict[str, int]:
                 proj_dim=512 if "_projector_single._linear_layers.0.weight" in sd else 768)
 
 
-def _score(engine_factory, sd, compute: str, ids, lens, anchor_ids, anchor_lens, batch: int, opts: Dict[str, Any]) -> Dict[str, Any]:
+CENSUS_TOP = 10  # tokens the --census list names per form
+
+
+def _sink_tokens(eng, ids, lens) -> list:
+    """The sink census of the rows just scored, most flagged items first; `sequences_with_token` = the share of those rows that contain the token — the f to put
+    into the guarded form's 1 + 1.34 f if that token is what its heads sit on (include/memvul_hip.h mv_set_form)."""
+    rows = eng.sink_census(top=CENSUS_TOP)["tokens"]
+    valid = np.arange(ids.shape[1])[None, :] < np.asarray(lens)[:, None]
+    for r in rows:
+        r["sequences_with_token"] = float(((ids == r["token_id"]) & valid).any(1).mean()) if len(lens) else 0.0
+    return rows
+
+
+def _score(engine_factory, sd, compute: str, ids, lens, anchor_ids, anchor_lens, batch: int, opts: Dict[str, Any], census: bool = False) -> Dict[str, Any]:
     """One engine of compute dtype `compute`: the anchors appended in order — consecutive anchors of one padded length per call, cut to the longest of them,
     so every anchor runs at the padded length of its own token count — the rows scored through forward_by_length in batches; then closed."""
     eng = engine_factory(0 if "device" not in opts else opts["device"], **{k: v for k, v in opts.items() if k != "device"})
@@ -105,6 +118,9 @@ def _score(engine_factory, sd, compute: str, ids, lens, anchor_ids, anchor_lens,
                 L = max(int(np.max(anchor_lens[g0:g1])), 1)
                 eng.anchor_append(np.ascontiguousarray(anchor_ids[g0:g1, :L]), np.ascontiguousarray(anchor_lens[g0:g1]))
                 g0 = g1
+            census = census and compute in ("precise", "safe", "guarded") and hasattr(eng, "sink_census_enable")  # (MV_F16X8 only; after the anchors: the issue reports alone)
+            if census:
+                eng.sink_census_enable(True)
             logits = np.empty((len(lens), G, 2), np.float32)
             t0 = time.perf_counter()
             for s0 in range(0, len(lens), batch):
@@ -122,20 +138,22 @@ def _score(engine_factory, sd, compute: str, ids, lens, anchor_ids, anchor_lens,
             if compute == "guarded" and hasattr(eng, "form_stats"):
                 seqs, resc = eng.form_stats()
                 mon.update(guarded_sequences=int(seqs), guarded_rescored=int(resc))
-        return {"logits": logits, "monitors": mon, "reports_per_s": float(len(lens) / dt) if dt > 0 else 0.0}
+            sink_tokens = _sink_tokens(eng, ids, lens) if census else None
+        return {"logits": logits, "monitors": mon, "reports_per_s": float(len(lens) / dt) if dt > 0 else 0.0, "sink_tokens": sink_tokens}
     finally:
         eng.close()
 
 
 def audit(state_dict_or_archive, ids, lens, anchor_ids, anchor_lens, forms: Sequence[str] = ("precise",), sample: Optional[int] = None,
           engine_factory=binding.Engine, tol: float = 1e-3, thres: float = 0.5, same_idx: int = 0, batch: int = 512,
-          engine_options: Optional[Dict[str, Any]] = None, keep_logits: bool = False) -> Dict[str, Any]:
+          engine_options: Optional[Dict[str, Any]] = None, keep_logits: bool = False, census: bool = False) -> Dict[str, Any]:
     """The audit on arrays.  `state_dict_or_archive`: the reference's state dict (name -> array) or the path of an archive (model.tar.gz, its directory, or a
     weights file archive.read_state_dict reads).  ids [N, S] zero-padded / lens [N]: the issue reports; anchor_ids / anchor_lens: the golden anchors.
     Scores `sample` rows (sample_rows; None = all) on an "f32" engine — the reference — then on one engine per name in `forms` ("precise", "safe",
     "guarded", "f16"), one engine alive at a time, and returns {"rows", "reference": {reports_per_s}, "forms": {name: compare(...) + monitors +
     reports_per_s}, "meets": every form within tol}.  engine_factory(device, **options) builds the engines (the CPU suite passes an oracle-backed stand-in).
-    keep_logits: also return the logits ("reference"/"forms"[name]["logits"]: arrays, not JSON)."""
+    keep_logits: also return the logits ("reference"/"forms"[name]["logits"]: arrays, not JSON).  census: every MV_F16X8 form also gets "sink_tokens" — the
+    sink census of its scored rows (binding.Engine.sink_census) with, per token, the share of those rows that contain it; nothing else changes."""
     for f in forms:
         if f not in FORMS:
             raise ValueError(f"audit: unknown form {f!r}: expected a subset of {FORMS}")
@@ -156,10 +174,12 @@ def audit(state_dict_or_archive, ids, lens, anchor_ids, anchor_lens, forms: Sequ
     if keep_logits:
         res["reference"]["logits"] = ref["logits"]
     for f in forms:
-        got = _score(engine_factory, sd, f, ids, lens, anchor_ids, anchor_lens, batch, opts)
+        got = _score(engine_factory, sd, f, ids, lens, anchor_ids, anchor_lens, batch, opts, census)
         r = compare(ref["logits"], got["logits"], tol=tol, thres=thres, same_idx=same_idx)
         r["rows_over_idx"] = [int(rows[i]) for i in r["rows_over_idx"]]  # in the caller's numbering
         r["monitors"], r["reports_per_s"] = got["monitors"], got["reports_per_s"]
+        if got["sink_tokens"] is not None:
+            r["sink_tokens"] = got["sink_tokens"]
         if keep_logits:
             r["logits"] = got["logits"]
         res["forms"][f] = r
@@ -227,13 +247,14 @@ def main(argv=None, engine_factory=binding.Engine) -> int:
     ap.add_argument("--thres", type=float, default=0.5, help="threshold on the best P(same) whose crossings are counted")
     ap.add_argument("--tol", type=float, default=1e-3, help="tolerance on the logits")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--census", action="store_true", help="add the sink census of every MV_F16X8 form: which tokens its flagged heads sit on (sink_tokens)")
     args = ap.parse_args(argv)
     sd, config, same_idx = _read_archive(args.archive)
     if config is None:
         ap.error("--archive must be an archive (config.json, vocabulary/, weights): the readers come from its config")
     ids, lens, aids, alens = _read_inputs(config, args.golden, args.input)
     res = audit(sd, ids, lens, aids, alens, forms=tuple(f for f in args.forms.split(",") if f), sample=args.sample, engine_factory=engine_factory,
-                tol=args.tol, thres=args.thres, same_idx=same_idx, engine_options={"device": args.device})
+                tol=args.tol, thres=args.thres, same_idx=same_idx, engine_options={"device": args.device}, census=args.census)
     for r in res["forms"].values():
         r.pop("row_max", None)  # one line a person can read: the per-row maxima stay with audit()
     print(json.dumps(res))

@@ -65,6 +65,14 @@ def on_sink_policy() -> str:
     return v
 
 
+def sink_census_policy() -> bool:
+    """$MEMVUL_SINK_CENSUS = 0 (default) | 1, parsed strictly: whether an MV_F16X8 engine keeps the sink census from construction on (Engine.sink_census)."""
+    v = os.environ.get("MEMVUL_SINK_CENSUS", "0")
+    if v not in ("0", "1"):
+        raise ValueError(f"MEMVUL_SINK_CENSUS={v!r}: expected '0' or '1'")
+    return v == "1"
+
+
 def wants_safe_form(name_or_code) -> bool:
     """True when the compute dtype asked for (None = default_compute()) is the name "safe": MV_F16X8 in the safe form."""
     return wanted_form(name_or_code) == "safe"
@@ -86,7 +94,7 @@ ABI_SYMBOLS = [
     "mv_create", "mv_destroy", "mv_last_error", "mv_sync", "mv_load_tensor", "mv_finalize_weights",
     "mv_anchor_reset", "mv_anchor_append", "mv_anchor_count", "mv_anchor_get", "mv_anchor_set",
     "mv_forward", "mv_forward_ragged", "mv_forward_ragged_begin", "mv_forward_ragged_end", "mv_encode", "mv_match", "mv_topk", "mv_corpus_upload", "mv_corpus_run", "mv_corpus_run_len",
-    "mv_corpus_results", "mv_x8_saturation", "mv_attention_concentration", "mv_set_form", "mv_get_form", "mv_form_stats", "mv_last_row_forms", "mv_corpus_row_forms", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
+    "mv_corpus_results", "mv_x8_saturation", "mv_attention_concentration", "mv_sink_census_enable", "mv_sink_census_read", "mv_set_form", "mv_get_form", "mv_form_stats", "mv_last_row_forms", "mv_corpus_row_forms", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
     "mv_debug_encode", "mv_debug_read", "mv_test_gemm", "mv_test_gemm_pp", "mv_test_gemm_f32", "mv_test_e4m3", "mv_format_records", "mv_comm_prepare", "mv_comm_unique_id", "mv_comm_init", "mv_comm_allgather",
     "mv_comm_destroy", "mv_comm_info", "mv_device_count",
 ]
@@ -148,6 +156,8 @@ def load_library(path: Optional[str] = None, dev: bool = False):
         "mv_corpus_results": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, vp]),
         "mv_x8_saturation": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int]),
         "mv_attention_concentration": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
+        "mv_sink_census_enable": (C.c_int, [vp, C.c_int]),
+        "mv_sink_census_read": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int]),
         "mv_set_streams": (C.c_int, [vp, C.c_int]),
         "mv_set_form": (C.c_int, [vp, C.c_int]),
         "mv_get_form": (C.c_int, [vp]),
@@ -212,6 +222,7 @@ class Engine:
         config) or 768 (use_header=False: the pooler output, no ``_projector_single`` in the state dict).  dev: load the development
         build (tests / A/B scripts: the only one that reads DEV_SWITCHES)."""
         on_sink_policy()  # (a malformed MEMVUL_ON_SINK raises before anything is created)
+        sink_census_policy()
         self._lib = load_library(dev=dev)
         self.P = int(proj_dim)
         self.cfg = MvConfig(vocab_size, 768, layers, 12, 3072, max_pos, type_vocab, self.P, ln_eps, max_tokens,
@@ -235,6 +246,7 @@ class Engine:
         self._corpus_runs = []       # the corpus_run calls since the last corpus_upload: what a switch of form sweeps once more
         self._guard_warned = False   # the guarded form's one warning (more than GUARDED_WARN_SHARE of the sequences rescored)
         self._last_rows = 0          # rows of the last call last_row_forms() speaks of
+        self._census = False         # the sink census is on (sink_census_enable / MEMVUL_SINK_CENSUS=1)
 
     # -- plumbing
     def _check(self, rc: int, what: str):
@@ -279,6 +291,8 @@ class Engine:
         self._check(self._lib.mv_finalize_weights(self._h, compute_dtype_of(compute_dtype)), "mv_finalize_weights")
         self._precise = compute_dtype_of(compute_dtype) == MV_F16X8
         self._sat_warned = False
+        if self._precise and sink_census_policy():  # (the census reads the planes of MV_F16X8: on another compute dtype the switch has nothing to switch on)
+            self.sink_census_enable(True)
         if wanted_form(compute_dtype):
             self.set_form(wanted_form(compute_dtype))
         else:
@@ -341,6 +355,46 @@ class Engine:
         self._check(self._lib.quick.mv_attention_concentration(self._h, C.byref(m), C.byref(n), C.byref(t), int(bool(reset))), "mv_attention_concentration")
         return float(m.value), int(n.value), int(t.value)
 
+    # -- the sink census
+    def sink_census_enable(self, on: bool = True):
+        """Keep (or stop keeping) the sink census for the passes enqueued from now on (mv_sink_census_enable; MV_F16X8 only, raises otherwise)."""
+        self._check(self._lib.mv_sink_census_enable(self._h, int(bool(on))), "mv_sink_census_enable")
+        self._census = bool(on)
+
+    def sink_census_read(self, reset: bool = False):
+        """The raw histograms of mv_sink_census_read (waits for the work in flight): items uint32 [vocab], share_q20 uint64 [vocab], by_head uint32 [layers, 12]."""
+        V, L = int(self.cfg.vocab_size), int(self.cfg.layers)
+        items, share, by_head = np.zeros(V, np.uint32), np.zeros(V, np.uint64), np.zeros((L, 12), np.uint32)
+        self._check(self._lib.mv_sink_census_read(self._h, _ptr(items), _ptr(share), V, _ptr(by_head), L * 12, int(bool(reset))), "mv_sink_census_read")
+        return items, share, by_head
+
+    def sink_census(self, top: int = 10, reset: bool = False, vocab=None):
+        """Which tokens the flagged heads sit on: {"tokens": the `top` token ids by flagged items, most first (ties: the lower id), each {token_id, items,
+        mean_share (of the [CLS] row's attention, over its items), share_of_flagged_items}, "by_head": uint32 [layers, 12], "flagged_items": their total}.
+        vocab: a tokenizer or vocabulary (convert_ids_to_tokens, an id -> string mapping or a sequence of strings): each row also gets "token"."""
+        items, share, by_head = self.sink_census_read(reset)
+        total = int(items.sum())
+        order = np.argsort(-items.astype(np.int64), kind="stable")[:max(int(top), 0)]
+        rows = []
+        for t in order:
+            n = int(items[t])
+            if n == 0:
+                break
+            row = {"token_id": int(t), "items": n, "mean_share": float(share[t]) / n / float(1 << 20), "share_of_flagged_items": n / total}
+            if vocab is not None:
+                row["token"] = _token_string(vocab, int(t))
+            rows.append(row)
+        return {"tokens": rows, "by_head": by_head, "flagged_items": total}
+
+    def _census_note(self) -> str:
+        """What the one-time sink warning appends with the census on: the top three tokens ("" with it off — the text then stays as it always was)."""
+        if not getattr(self, "_census", False):
+            return ""
+        rows = self.sink_census(top=3)["tokens"]
+        if not rows:
+            return ""
+        return "; sink census, token id (share of the flagged items): " + ", ".join(f"{r['token_id']} ({r['share_of_flagged_items']:.0%})" for r in rows)
+
     def _check_saturation(self):
         """Called after the host-synchronous entry points of the precise mode: warn ONCE when the fp8 planes clamped anything, and once when the concentration
         monitor trips.  Returns True when that trip switched the engine to the safe form (MEMVUL_ON_SINK=safe): the caller redoes its call."""
@@ -356,8 +410,8 @@ class Engine:
                 warnings.warn(f"MV_F16X8: in {n} of {t} (sequence, head, layer) items the [CLS] row puts more than half of a head's attention on ONE ordinary token "
                               f"(collision mass up to {m:.2f}): the 1e-3 logit tolerance of the default form is backed by measurement for diffuse attention and "
                               "for attention sinks on [CLS] / [SEP] only (profiles/r06_n_sink_envelope.txt: 0.8 - 2.7e-3 for such a sink); "
-                              "MEMVUL_CLS_ASIDE=0 MEMVUL_QKV_ASIDE=qkv is the most conservative form (include/memvul_hip.h mv_attention_concentration)",
-                              RuntimeWarning, stacklevel=3)
+                              "MEMVUL_CLS_ASIDE=0 MEMVUL_QKV_ASIDE=qkv is the most conservative form (include/memvul_hip.h mv_attention_concentration)"
+                              + self._census_note(), RuntimeWarning, stacklevel=3)
         if getattr(self, "_precise", False) and self._form == "guarded" and not self._guard_warned:
             seqs, resc = self.form_stats()
             if seqs >= 100 and resc > GUARDED_WARN_SHARE * seqs:
@@ -724,6 +778,16 @@ class Engine:
         self._check(self._lib.mv_test_gemm_f32(self._h, self.GEMM_F32_ACTS[act], M, N, K, _ptr(A), _ptr(W), _ptr(bias), _ptr(res), _ptr(out), iters,
                                                C.byref(ms)), "mv_test_gemm_f32")
         return out, float(ms.value)
+
+
+def _token_string(vocab, token_id: int) -> str:
+    """The string of a token id from a tokenizer (convert_ids_to_tokens), a mapping id -> string, or a sequence of strings; "" where it has none."""
+    if hasattr(vocab, "convert_ids_to_tokens"):
+        t = vocab.convert_ids_to_tokens([token_id])
+        return str(t[0]) if t else ""
+    if hasattr(vocab, "get"):
+        return str(vocab.get(token_id, ""))
+    return str(vocab[token_id]) if 0 <= token_id < len(vocab) else ""
 
 
 def device_count() -> int:

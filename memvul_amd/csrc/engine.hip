@@ -26,6 +26,7 @@
 #include "misc_kernels.h"
 #include "match_topk.h"
 #include "ref_f32.h"
+#include "sink_census.h"
 
 namespace {
 
@@ -220,6 +221,11 @@ struct mv_handle {
   float* anchors = nullptr;
   int n_anchors = 0;
   unsigned long long* attn_conc = nullptr;  // MV_F16X8: [0] max collision mass of the [CLS] row on ordinary keys (float bits), [1] items above 0.25 (AttnArgs::conc)
+  // the sink census (mv_sink_census_enable / mv_sink_census_read; sink_census.h): allocated at the first enable, sized by the loaded vocabulary
+  bool census = false;                        // one host-side test per monitored layer of a pass while it is off
+  uint32_t* census_items = nullptr;           // [vocab_size]
+  unsigned long long* census_share = nullptr; // [vocab_size] sum of round(p* 2^20)
+  uint32_t* census_heads = nullptr;           // [layers][12]
   unsigned long long* x8_sat = nullptr;  // MV_F16X8: device counter (64-bit: it cannot wrap within a run) of activation elements beyond the fp8 planes' range (mv_x8_saturation)
 
   // resident corpus
@@ -795,6 +801,13 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
       }
       if (int rc = launch_pp<PP_QK>(h, wk.stream, KC_GEMM_QKV, g)) return rc;
       g.cls_corr = nullptr; g.vlo_sp = nullptr;
+      // the sink census: the layers whose attention launch feeds the concentration monitor, and only where it is attached (a rescoring pass counts nothing twice)
+      if (h->census && x8 && pf.monitor) {
+        ProfScope ps(h, wk.stream, KC_ATTENTION);
+        hipLaunchKernelGGL(sink_census_kernel, dim3((unsigned)((B * MV_HEADS + 3) / 4)), dim3(256), 0, wk.stream, (const half_t*)wk.q, (const half_t*)wk.k, d_lens,
+                           d_ids, pitch, S_in, Sp, B * MV_HEADS, c.vocab_size, h->census_items, h->census_share, h->census_heads + (size_t)l * MV_HEADS);
+        if (int rc = launch_check(h, "sink_census")) return rc;
+      }
       // K3: attention (cls_as: + the context's special rows' low parts for the output projection's row term)
       if (int rc = launch_attention(h, wk, d_lens, B, Sp, x8, cls_as, pf)) return rc;
       // K4: attention output projection + bias + LayerNorm(residual), in place on the raw stream; + vstats of the new rows
@@ -2262,6 +2275,41 @@ int mv_attention_concentration(mv_handle* h, float* max_collision, int64_t* item
   std::memcpy(max_collision, &bits, 4);
   *items_over = v[1] > (unsigned long long)INT64_MAX ? INT64_MAX : (int64_t)v[1];
   *items_total = v[2] > (unsigned long long)INT64_MAX ? INT64_MAX : (int64_t)v[2];
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+int mv_sink_census_enable(mv_handle* h, int on) try {
+  if (!h) return MV_ERR_INVALID;
+  if (!h->finalized) return fail(h, MV_ERR_STATE, "mv_sink_census_enable: weights not finalized (mv_finalize_weights)");
+  if (!h->precise) return fail(h, MV_ERR_STATE, "mv_sink_census_enable: the census reads the planes of compute dtype MV_F16X8; this handle was finalized as MV_F16 or MV_F32");
+  if (on && !h->census_items) {
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s0 = h->work[0].stream;
+    if (int rc = dev_alloc(h, s0, &h->census_items, (int64_t)h->cfg.vocab_size)) return rc;
+    if (int rc = dev_alloc(h, s0, &h->census_share, (int64_t)h->cfg.vocab_size)) return rc;
+    if (int rc = dev_alloc(h, s0, &h->census_heads, (int64_t)h->cfg.layers * MV_HEADS)) return rc;
+    HIPCHK(h, hipStreamSynchronize(s0));  // (zeroed before a pass on another stream can add to them)
+  }
+  h->census = on != 0;  // (read on the host when a pass is enqueued: work in flight keeps what it was enqueued with)
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+int mv_sink_census_read(mv_handle* h, uint32_t* items, uint64_t* share_q20, int vocab, uint32_t* by_head, int layers_x_heads, int reset) try {
+  if (!h) return MV_ERR_INVALID;
+  if (!h->census_items) return fail(h, MV_ERR_STATE, "mv_sink_census_read: the census was never enabled (mv_sink_census_enable)");
+  if (vocab != h->cfg.vocab_size || layers_x_heads != h->cfg.layers * MV_HEADS)
+    return fail(h, MV_ERR_INVALID, "mv_sink_census_read: vocab must be mv_config.vocab_size and layers_x_heads mv_config.layers * 12");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = sync_all(h)) return rc;
+  const size_t V = (size_t)vocab, LH = (size_t)layers_x_heads;
+  if (items) HIPCHK(h, hipMemcpy(items, h->census_items, V * 4, hipMemcpyDeviceToHost));
+  if (share_q20) HIPCHK(h, hipMemcpy(share_q20, h->census_share, V * 8, hipMemcpyDeviceToHost));
+  if (by_head) HIPCHK(h, hipMemcpy(by_head, h->census_heads, LH * 4, hipMemcpyDeviceToHost));
+  if (reset) {
+    HIPCHK(h, hipMemset(h->census_items, 0, V * 4));
+    HIPCHK(h, hipMemset(h->census_share, 0, V * 8));
+    HIPCHK(h, hipMemset(h->census_heads, 0, LH * 4));
+  }
   return MV_OK;
 } catch (...) { return on_exception(h); }
 
