@@ -94,7 +94,7 @@ typedef struct mv_config {
  *                             In the safe form MEMVUL_CLS_ASIDE, MEMVUL_CLS_ASIDE_MIN_LEN and MEMVUL_QKV_ASIDE have no effect (it is their most conservative setting).
  * (The seventh switch of the product, MEMVUL_COMPUTE = precise | f16 | f32 (+ aliases), is read by the Python surface: memvul_amd/binding.py default_compute.)
  * (So are MEMVUL_ON_SINK = warn | safe and MEMVUL_SINK_CENSUS = 0 | 1 — binding.py on_sink_policy / sink_census_policy; the latter calls mv_sink_census_enable
- * after mv_finalize_weights.)
+ * after mv_finalize_weights — and MEMVUL_SINK_TOKENS = ID[,ID...] — binding.py sink_tokens_policy: mv_set_sink_tokens after mv_finalize_weights, guarded form only.)
  * Development A/B knobs (kernel path forced at test sizes, raster, grid share, one-plane short passes) exist only in the -DMEMVUL_DEV_SWITCHES build
  * (libmemvul_hip_dev.so: memvul_amd/build.py, loaded by the GPU tests and A/B scripts that need them); this library does not read them. */
 int mv_create(int device, const mv_config* cfg, mv_handle** out);
@@ -144,6 +144,8 @@ int mv_finalize_weights(mv_handle* h, int compute_dtype);
  *                    and rescores everything swept since, in full batches, before mv_corpus_results copies anything.  The rescoring passes leave the global
  *                    counters of mv_attention_concentration alone (a sequence is counted once).  Costs the default form's rate times (1 + 1.34 f) at a flagged
  *                    share f: above f ~ 0.25 the safe form is the cheaper one.  mv_debug_encode ignores it (taps show the default form).
+ *                    With a sink-token list (mv_set_sink_tokens, below) a sequence that carries a listed token is not encoded twice: it skips the default form
+ *                    and goes straight into the safe-form pass, next to the sequences the monitor flags.
  * mv_set_form: MV_FORM_SAFE / MV_FORM_GUARDED on a handle finalized as MV_F16 or MV_F32 -> MV_ERR_STATE, an unknown value -> MV_ERR_INVALID.  The form of a pass is read on the
  * host when the pass is enqueued: work already in flight keeps the form it was enqueued with.  mv_get_form returns the current form. */
 #define MV_FORM_DEFAULT 0
@@ -160,6 +162,42 @@ int mv_form_stats(mv_handle* h, int64_t* sequences, int64_t* rescored, int reset
 int mv_last_row_forms(mv_handle* h, uint8_t* forms, int n);
 /* The same for rows [first, first + count) of the resident corpus: valid after mv_corpus_results (rows never swept read MV_FORM_DEFAULT). */
 int mv_corpus_row_forms(mv_handle* h, int64_t first, int64_t count, uint8_t* forms);
+
+/* The sink-token list: ordinary-token sinks are driven by the token (mv_sink_census_read names it), so a sequence that is certain to be flagged
+ * can be read off its ids.  THE RULE: a sequence is ROUTED iff one of its tokens at positions 1 .. len - 2 is in the list — positions 0 and len - 1 are [CLS] /
+ * [SEP] (the special rows cover them; the census looks at the same positions), ids at positions >= len are padding and never looked at (a list that holds id 0
+ * does not route by padding), there is no length gate, and a sequence of len <= 2 has no such position.
+ * The list is kept in every form of MV_F16X8 and ACTED ON ONLY IN MV_FORM_GUARDED (the safe form is already safe, the default form stays the default form): there
+ * a routed sequence never runs in the default form.  mv_forward / mv_forward_ragged / mv_forward_ragged_begin / mv_encode / mv_anchor_append plan the batch over
+ * all its rows as without a list (every row keeps the width of its pass), run the unrouted rows of each pass in the default form with the per-sequence monitor
+ * (the pass's shortest-sequence rule, MEMVUL_CLS_ASIDE_MIN_LEN, is taken over the rows that run in it), and encode the routed rows ONCE, in the safe form, in the
+ * rescoring passes, together with the unrouted rows the monitor flagged.  A routed sequence gets the bits a safe-form handle gives it through the same call.  The
+ * list is read where the form is: when the job is made — a ticket of mv_forward_ragged_begin keeps the routing it was begun with.  On the resident corpus the ids
+ * live on the device: one kernel (memvul_amd/csrc/route.h) flags every corpus row under the current list, lazily, at the first mv_corpus_run* or
+ * mv_corpus_route_flags after an upload or a list change (a kernel, one copy back, one wait — not per batch); a guarded sweep leaves the routed rows of its
+ * range out of its batches and marks them, and the rescoring in front of mv_corpus_results encodes them with the flagged ones; rows swept before a list change keep
+ * the routing of their sweep.  mv_debug_encode ignores the list, as it ignores the guarded form.
+ * ROUTED SEQUENCES FEED NEITHER mv_attention_concentration NOR THE CENSUS: their only pass is a rescoring pass, which runs with the monitor detached (a sequence
+ * is counted once — a routed one not at all: the list already says what the monitor would have).  A sink the list does not name is still caught by the monitor.
+ * Empty (the default), the guarded form is what it is without this list, bit for bit, counters included.
+ * mv_set_sink_tokens replaces the list: n == 0 clears it (ids may be NULL then), duplicates are allowed; n < 0, n > MV_MAX_SINK_TOKENS, ids == NULL with n > 0 or
+ * an id outside [0, mv_config.vocab_size) -> MV_ERR_INVALID, the list unchanged; before mv_finalize_weights, or on a handle finalized as MV_F16 or MV_F32 ->
+ * MV_ERR_STATE.  mv_get_sink_tokens returns the list's length (>= 0) and fills up to `capacity` ids.
+ * mv_route_stats: *routed = the sequences sent directly to the safe form since the handle was created (or the last reset; corpus rows count once the rescoring
+ * in front of mv_corpus_results has encoded them).  mv_form_stats keeps its meaning: *rescored counts only sequences encoded twice — the rows mv_last_row_forms /
+ * mv_corpus_row_forms call MV_FORM_SAFE in the guarded form are routed + rescored.
+ * mv_route_scan: the rule itself, host only, no handle, no GPU work, callable from any thread: flags[b] = 1 / 0 for the rows of ids [B][S] with lengths lens [B]
+ * under the list tokens [n] over a vocabulary of `vocab` ids (a length outside [0, S] is read as clamped; an id outside the vocabulary matches nothing).  The
+ * batch entry points run exactly this function.  A NULL array, B < 0, S <= 0, vocab <= 0, n outside 0 .. MV_MAX_SINK_TOKENS or a token outside [0, vocab) ->
+ * MV_ERR_INVALID, flags untouched.
+ * mv_corpus_route_flags: what the device kernel computed for rows [first, first + count) of the resident corpus under the current list (computed first if stale;
+ * all 0 with an empty list); no corpus -> MV_ERR_STATE.  No reference counterpart (the reference computes in fp32). */
+#define MV_MAX_SINK_TOKENS 64
+int mv_set_sink_tokens(mv_handle* h, const int32_t* ids, int n);
+int mv_get_sink_tokens(mv_handle* h, int32_t* ids, int capacity);
+int mv_route_stats(mv_handle* h, int64_t* routed, int reset);
+int mv_route_scan(const int32_t* ids, const int32_t* lens, int B, int S, const int32_t* tokens, int n, int vocab, uint8_t* flags);
+int mv_corpus_route_flags(mv_handle* h, int64_t first, int64_t count, uint8_t* flags);
 
 /* ---- anchor memory (replaces ModelMemory.forward_gold_instances, model_memory.py:105-115, as
  *      driven by predict_memory.py:81-83 and callbacks.py:48-53) ------------------------------ */

@@ -101,14 +101,18 @@ def _sink_tokens(eng, ids, lens) -> list:
     return rows
 
 
-def _score(engine_factory, sd, compute: str, ids, lens, anchor_ids, anchor_lens, batch: int, opts: Dict[str, Any], census: bool = False) -> Dict[str, Any]:
+def _score(engine_factory, sd, compute: str, ids, lens, anchor_ids, anchor_lens, batch: int, opts: Dict[str, Any], census: bool = False,
+           sink_tokens: Optional[Sequence[int]] = None) -> Dict[str, Any]:
     """One engine of compute dtype `compute`: the anchors appended in order — consecutive anchors of one padded length per call, cut to the longest of them,
-    so every anchor runs at the padded length of its own token count — the rows scored through forward_by_length in batches; then closed."""
+    so every anchor runs at the padded length of its own token count — the rows scored through forward_by_length in batches; then closed.  sink_tokens: the
+    sink-token list the engine gets before anything is encoded (the guarded form's: audit() hands it to no other)."""
     eng = engine_factory(0 if "device" not in opts else opts["device"], **{k: v for k, v in opts.items() if k != "device"})
     try:
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")  # the monitors are reported below, as numbers
             eng.load_state_dict(sd, compute)
+            if sink_tokens is not None:
+                eng.set_sink_tokens(list(sink_tokens))
             eng.anchor_reset()
             g0, G = 0, len(anchor_lens)
             while g0 < G:
@@ -138,6 +142,8 @@ def _score(engine_factory, sd, compute: str, ids, lens, anchor_ids, anchor_lens,
             if compute == "guarded" and hasattr(eng, "form_stats"):
                 seqs, resc = eng.form_stats()
                 mon.update(guarded_sequences=int(seqs), guarded_rescored=int(resc))
+                if sink_tokens is not None:
+                    mon["guarded_routed"] = int(eng.route_stats())
             sink_tokens = _sink_tokens(eng, ids, lens) if census else None
         return {"logits": logits, "monitors": mon, "reports_per_s": float(len(lens) / dt) if dt > 0 else 0.0, "sink_tokens": sink_tokens}
     finally:
@@ -146,17 +152,25 @@ def _score(engine_factory, sd, compute: str, ids, lens, anchor_ids, anchor_lens,
 
 def audit(state_dict_or_archive, ids, lens, anchor_ids, anchor_lens, forms: Sequence[str] = ("precise",), sample: Optional[int] = None,
           engine_factory=binding.Engine, tol: float = 1e-3, thres: float = 0.5, same_idx: int = 0, batch: int = 512,
-          engine_options: Optional[Dict[str, Any]] = None, keep_logits: bool = False, census: bool = False) -> Dict[str, Any]:
+          engine_options: Optional[Dict[str, Any]] = None, keep_logits: bool = False, census: bool = False,
+          sink_tokens: Optional[Sequence[int]] = None) -> Dict[str, Any]:
     """The audit on arrays.  `state_dict_or_archive`: the reference's state dict (name -> array) or the path of an archive (model.tar.gz, its directory, or a
     weights file archive.read_state_dict reads).  ids [N, S] zero-padded / lens [N]: the issue reports; anchor_ids / anchor_lens: the golden anchors.
     Scores `sample` rows (sample_rows; None = all) on an "f32" engine — the reference — then on one engine per name in `forms` ("precise", "safe",
     "guarded", "f16"), one engine alive at a time, and returns {"rows", "reference": {reports_per_s}, "forms": {name: compare(...) + monitors +
     reports_per_s}, "meets": every form within tol}.  engine_factory(device, **options) builds the engines (the CPU suite passes an oracle-backed stand-in).
     keep_logits: also return the logits ("reference"/"forms"[name]["logits"]: arrays, not JSON).  census: every MV_F16X8 form also gets "sink_tokens" — the
-    sink census of its scored rows (binding.Engine.sink_census) with, per token, the share of those rows that contain it; nothing else changes."""
+    sink census of its scored rows (binding.Engine.sink_census) with, per token, the share of those rows that contain it; nothing else changes.
+    sink_tokens: the sink-token list (binding.Engine.set_sink_tokens) of the audited "guarded" form — an error without "guarded" among `forms`; that form's object
+    gains "sink_token_list", "rescored_share" and "routed_share" (of the sequences it encoded, anchors included), and with `census` its "sink_tokens" then shows
+    what the list does NOT cover: a routed sequence feeds no census."""
     for f in forms:
         if f not in FORMS:
             raise ValueError(f"audit: unknown form {f!r}: expected a subset of {FORMS}")
+    if sink_tokens is not None:
+        sink_tokens = binding._sink_token_list(sink_tokens)
+        if "guarded" not in forms:
+            raise ValueError("audit: sink_tokens is acted on in the guarded form only: add \"guarded\" to the forms")
     if isinstance(state_dict_or_archive, str):
         sd, _, same_idx = _read_archive(state_dict_or_archive)  # (the archive's own index of "same"; a bare weights file: 0)
     else:
@@ -174,12 +188,17 @@ def audit(state_dict_or_archive, ids, lens, anchor_ids, anchor_lens, forms: Sequ
     if keep_logits:
         res["reference"]["logits"] = ref["logits"]
     for f in forms:
-        got = _score(engine_factory, sd, f, ids, lens, anchor_ids, anchor_lens, batch, opts, census)
+        got = _score(engine_factory, sd, f, ids, lens, anchor_ids, anchor_lens, batch, opts, census, sink_tokens if f == "guarded" else None)
         r = compare(ref["logits"], got["logits"], tol=tol, thres=thres, same_idx=same_idx)
         r["rows_over_idx"] = [int(rows[i]) for i in r["rows_over_idx"]]  # in the caller's numbering
         r["monitors"], r["reports_per_s"] = got["monitors"], got["reports_per_s"]
         if got["sink_tokens"] is not None:
             r["sink_tokens"] = got["sink_tokens"]
+        if f == "guarded" and sink_tokens is not None:
+            seqs = max(int(got["monitors"].get("guarded_sequences", 0)), 1)
+            r["sink_token_list"] = [int(t) for t in sink_tokens]
+            r["rescored_share"] = int(got["monitors"].get("guarded_rescored", 0)) / seqs
+            r["routed_share"] = int(got["monitors"].get("guarded_routed", 0)) / seqs
         if keep_logits:
             r["logits"] = got["logits"]
         res["forms"][f] = r
@@ -248,13 +267,24 @@ def main(argv=None, engine_factory=binding.Engine) -> int:
     ap.add_argument("--tol", type=float, default=1e-3, help="tolerance on the logits")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--census", action="store_true", help="add the sink census of every MV_F16X8 form: which tokens its flagged heads sit on (sink_tokens)")
+    ap.add_argument("--sink-tokens", default=None, metavar="ID[,ID...]", help="the sink-token list of the audited guarded form (needs guarded among --forms): its "
+                    "object gains routed_share; with --census its sink_tokens shows what the list does not cover")
     args = ap.parse_args(argv)
+    forms = tuple(f for f in args.forms.split(",") if f)
+    sink_tokens = None
+    if args.sink_tokens is not None:
+        try:
+            sink_tokens = binding.parse_sink_tokens(args.sink_tokens)
+        except ValueError as e:
+            ap.error(str(e).replace("MEMVUL_SINK_TOKENS=", "--sink-tokens "))
+        if "guarded" not in forms:
+            ap.error("--sink-tokens is acted on in the guarded form only: add guarded to --forms")
     sd, config, same_idx = _read_archive(args.archive)
     if config is None:
         ap.error("--archive must be an archive (config.json, vocabulary/, weights): the readers come from its config")
     ids, lens, aids, alens = _read_inputs(config, args.golden, args.input)
-    res = audit(sd, ids, lens, aids, alens, forms=tuple(f for f in args.forms.split(",") if f), sample=args.sample, engine_factory=engine_factory,
-                tol=args.tol, thres=args.thres, same_idx=same_idx, engine_options={"device": args.device}, census=args.census)
+    res = audit(sd, ids, lens, aids, alens, forms=forms, sample=args.sample, engine_factory=engine_factory,
+                tol=args.tol, thres=args.thres, same_idx=same_idx, engine_options={"device": args.device}, census=args.census, sink_tokens=sink_tokens)
     for r in res["forms"].values():
         r.pop("row_max", None)  # one line a person can read: the per-row maxima stay with audit()
     print(json.dumps(res))

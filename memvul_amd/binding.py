@@ -7,8 +7,9 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import warnings
-from typing import Dict, Iterable, Optional, Tuple
+from typing import Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 
@@ -73,6 +74,38 @@ def sink_census_policy() -> bool:
     return v == "1"
 
 
+MAX_SINK_TOKENS = 64  # include/memvul_hip.h MV_MAX_SINK_TOKENS
+
+
+def parse_sink_tokens(text: str) -> List[int]:
+    """"1012,1010" -> [1012, 1010]: comma-separated decimal token ids and nothing else (no spaces, no signs, no empty field); anything else raises."""
+    if not isinstance(text, str) or not re.fullmatch(r"[0-9]+(,[0-9]+)*", text):
+        raise ValueError(f"MEMVUL_SINK_TOKENS={text!r}: expected comma-separated decimal token ids, e.g. '1012,1010'")
+    ids = [int(t) for t in text.split(",")]
+    if len(ids) > MAX_SINK_TOKENS:
+        raise ValueError(f"MEMVUL_SINK_TOKENS: {len(ids)} ids, the list holds at most {MAX_SINK_TOKENS}")
+    return ids
+
+
+def sink_tokens_policy() -> Optional[List[int]]:
+    """$MEMVUL_SINK_TOKENS = ID[,ID...], parsed strictly (parse_sink_tokens), or None when it is not set: the sink-token list a guarded engine gets after
+    mv_finalize_weights (Engine.set_sink_tokens).  Set while the engine's form is not "guarded" it raises there: a switch that would do nothing is a typo."""
+    v = os.environ.get("MEMVUL_SINK_TOKENS")
+    return None if v is None else parse_sink_tokens(v)
+
+
+def _sink_token_list(ids) -> List[int]:
+    """engine_options["sink_tokens"] / Engine.set_sink_tokens: a sequence of integer token ids (a string is MEMVUL_SINK_TOKENS' syntax), checked as strictly."""
+    if isinstance(ids, str):
+        return parse_sink_tokens(ids)
+    out = []
+    for t in ids:
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)):
+            raise ValueError(f"sink_tokens: expected integer token ids, got {t!r}")
+        out.append(int(t))
+    return out
+
+
 def wants_safe_form(name_or_code) -> bool:
     """True when the compute dtype asked for (None = default_compute()) is the name "safe": MV_F16X8 in the safe form."""
     return wanted_form(name_or_code) == "safe"
@@ -94,7 +127,8 @@ ABI_SYMBOLS = [
     "mv_create", "mv_destroy", "mv_last_error", "mv_sync", "mv_load_tensor", "mv_finalize_weights",
     "mv_anchor_reset", "mv_anchor_append", "mv_anchor_count", "mv_anchor_get", "mv_anchor_set",
     "mv_forward", "mv_forward_ragged", "mv_forward_ragged_begin", "mv_forward_ragged_end", "mv_encode", "mv_match", "mv_topk", "mv_corpus_upload", "mv_corpus_run", "mv_corpus_run_len",
-    "mv_corpus_results", "mv_x8_saturation", "mv_attention_concentration", "mv_sink_census_enable", "mv_sink_census_read", "mv_set_form", "mv_get_form", "mv_form_stats", "mv_last_row_forms", "mv_corpus_row_forms", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
+    "mv_corpus_results", "mv_x8_saturation", "mv_attention_concentration", "mv_sink_census_enable", "mv_sink_census_read", "mv_set_form", "mv_get_form", "mv_form_stats", "mv_last_row_forms", "mv_corpus_row_forms",
+    "mv_set_sink_tokens", "mv_get_sink_tokens", "mv_route_stats", "mv_route_scan", "mv_corpus_route_flags", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
     "mv_debug_encode", "mv_debug_read", "mv_test_gemm", "mv_test_gemm_pp", "mv_test_gemm_f32", "mv_test_e4m3", "mv_format_records", "mv_comm_prepare", "mv_comm_unique_id", "mv_comm_init", "mv_comm_allgather",
     "mv_comm_destroy", "mv_comm_info", "mv_device_count",
 ]
@@ -164,6 +198,11 @@ def load_library(path: Optional[str] = None, dev: bool = False):
         "mv_form_stats": (C.c_int, [vp, P(C.c_int64), P(C.c_int64), C.c_int]),
         "mv_last_row_forms": (C.c_int, [vp, vp, C.c_int]),
         "mv_corpus_row_forms": (C.c_int, [vp, C.c_int64, C.c_int64, vp]),
+        "mv_set_sink_tokens": (C.c_int, [vp, i32p, C.c_int]),
+        "mv_get_sink_tokens": (C.c_int, [vp, i32p, C.c_int]),
+        "mv_route_stats": (C.c_int, [vp, P(C.c_int64), C.c_int]),
+        "mv_route_scan": (C.c_int, [vp, vp, C.c_int, C.c_int, i32p, C.c_int, C.c_int, vp]),
+        "mv_corpus_route_flags": (C.c_int, [vp, C.c_int64, C.c_int64, vp]),
         "mv_profile_enable": (C.c_int, [vp, C.c_int]),
         "mv_profile_select": (C.c_int, [vp, C.c_uint32]),
         "mv_profile_read": (C.c_int, [vp, P(C.c_double), P(C.c_int64), C.c_int]),
@@ -217,12 +256,15 @@ class Engine:
 
     def __init__(self, device: int = 0, *, vocab_size: int = 30522, layers: int = 12, max_pos: int = 512,
                  type_vocab: int = 2, ln_eps: float = 1e-12, max_tokens: int = 65536, max_batch: int = 512,
-                 max_anchors: int = 1024, same_idx: int = 0, proj_dim: int = 512, dev: bool = False):
+                 max_anchors: int = 1024, same_idx: int = 0, proj_dim: int = 512, dev: bool = False, sink_tokens=None):
         """proj_dim: width of the embedding the matcher runs on — 512 (the header output: use_header=True, every reference
         config) or 768 (use_header=False: the pooler output, no ``_projector_single`` in the state dict).  dev: load the development
-        build (tests / A/B scripts: the only one that reads DEV_SWITCHES)."""
+        build (tests / A/B scripts: the only one that reads DEV_SWITCHES).  sink_tokens: the sink-token list of the guarded form (what MEMVUL_SINK_TOKENS sets; it wins
+        over the environment), applied by load_state_dict — it raises there unless the form is "guarded"."""
         on_sink_policy()  # (a malformed MEMVUL_ON_SINK raises before anything is created)
         sink_census_policy()
+        sink_tokens_policy()
+        self._sink_tokens_wanted = None if sink_tokens is None else _sink_token_list(sink_tokens)
         self._lib = load_library(dev=dev)
         self.P = int(proj_dim)
         self.cfg = MvConfig(vocab_size, 768, layers, 12, 3072, max_pos, type_vocab, self.P, ln_eps, max_tokens,
@@ -297,6 +339,15 @@ class Engine:
             self.set_form(wanted_form(compute_dtype))
         else:
             self._form = {v: k for k, v in FORMS.items()}.get(self._get_form(), "default")  # (MEMVUL_FORM, read by mv_create)
+        want = getattr(self, "_sink_tokens_wanted", None)
+        src = "sink_tokens"
+        if want is None:
+            want, src = sink_tokens_policy(), "MEMVUL_SINK_TOKENS"
+        if want is not None:  # (once, after mv_finalize_weights and after the form is known)
+            if self._form != "guarded":
+                raise ValueError(f"{src} is set, but this engine's form is {self._form!r}: the sink-token list is acted on in the guarded form only "
+                                 "(compute dtype \"guarded\" / MEMVUL_FORM=guarded); it would do nothing here")
+            self.set_sink_tokens(want)
 
     # -- the three forms of MV_F16X8
     def _get_form(self) -> int:
@@ -338,6 +389,49 @@ class Engine:
         f = np.empty((count,), np.uint8)
         self._check(self._lib.mv_corpus_row_forms(self._h, first, count, _ptr(f)), "mv_corpus_row_forms")
         return ["safe" if x == MV_FORM_SAFE else "default" for x in f]
+
+    # -- the sink-token list of the guarded form
+    def set_sink_tokens(self, ids):
+        """Replace the sink-token list (mv_set_sink_tokens; [] clears it): in the guarded form a sequence that carries one of these ids at positions 1 .. len - 2
+        goes straight into the safe-form pass instead of being encoded twice.  Typically the top rows of sink_census().  MV_F16X8 only; kept in every form,
+        acted on in the guarded form; at most MAX_SINK_TOKENS ids inside the vocabulary (the library raises otherwise and keeps the list it had)."""
+        ids = _sink_token_list(ids)
+        a = (C.c_int32 * max(len(ids), 1))(*ids)
+        self._check(self._lib.mv_set_sink_tokens(self._h, a if ids else None, len(ids)), "mv_set_sink_tokens")
+
+    def sink_tokens(self) -> List[int]:
+        """The list as the handle holds it (mv_get_sink_tokens)."""
+        a = (C.c_int32 * MAX_SINK_TOKENS)()
+        n = int(self._lib.mv_get_sink_tokens(self._h, a, MAX_SINK_TOKENS))
+        if n < 0:
+            self._check(n, "mv_get_sink_tokens")
+        return [int(a[i]) for i in range(n)]
+
+    def route_stats(self, reset: bool = False) -> int:
+        """Sequences sent directly to the safe form by the list so far (mv_route_stats); form_stats()[1] counts only the sequences encoded twice."""
+        n = C.c_int64(0)
+        self._check(self._lib.mv_route_stats(self._h, C.byref(n), int(bool(reset))), "mv_route_stats")
+        return int(n.value)
+
+    @staticmethod
+    def route_scan(ids, lens, tokens, vocab_size: int = 30522, lib=None) -> np.ndarray:
+        """The routing rule on the host (mv_route_scan, no GPU): bool [B], True where a row of ids [B, S] carries one of `tokens` at positions 1 .. len - 2."""
+        ids, lens = _as(ids, np.int32), _as(lens, np.int32)
+        if ids.ndim != 2 or lens.shape != (ids.shape[0],):
+            raise ValueError("route_scan: ids [B, S] and lens [B]")
+        tokens = _sink_token_list(tokens)
+        t = (C.c_int32 * max(len(tokens), 1))(*tokens)
+        flags = np.zeros((ids.shape[0],), np.uint8)
+        rc = (lib or load_library()).mv_route_scan(_ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1], t if tokens else None, len(tokens), int(vocab_size), _ptr(flags))
+        if rc != 0:
+            raise RuntimeError(f"mv_route_scan failed ({rc}): bad shape, more than {MAX_SINK_TOKENS} tokens or a token outside [0, {int(vocab_size)})")
+        return flags.astype(bool)
+
+    def corpus_route_flags(self, first: int, count: int) -> np.ndarray:
+        """bool [count]: what the device kernel flags for rows [first, first + count) of the resident corpus under the current list (mv_corpus_route_flags)."""
+        f = np.zeros((count,), np.uint8)
+        self._check(self._lib.mv_corpus_route_flags(self._h, first, count, _ptr(f)), "mv_corpus_route_flags")
+        return f.astype(bool)
 
     def x8_saturation(self, reset: bool = False) -> int:
         """MV_F16X8: activation elements (raw stream, attention context, GELU output) that fell outside the +-112 range of the fp8
@@ -418,7 +512,9 @@ class Engine:
                 self._guard_warned = True
                 warnings.warn(f"MV_F16X8, guarded form: {resc} of {seqs} sequences were encoded again in the safe form — above a share of {GUARDED_WARN_SHARE} the safe "
                               "form (compute dtype \"safe\" / set_form(\"safe\") / MEMVUL_FORM=safe) scores the same corpus faster: a guarded sequence costs "
-                              "1 + 1.34 x that share of a default-form one, a safe-form one 1.34 (include/memvul_hip.h mv_set_form)", RuntimeWarning, stacklevel=3)
+                              "1 + 1.34 x that share of a default-form one, a safe-form one 1.34 (include/memvul_hip.h mv_set_form).  If the sinks sit on a few tokens "
+                              "(sink_census() names them), set_sink_tokens / MEMVUL_SINK_TOKENS sends the sequences that carry them straight to the safe form "
+                              "instead of encoding them twice", RuntimeWarning, stacklevel=3)
         if getattr(self, "_precise", False) and not self._sat_warned:
             n = self.x8_saturation()
             if n:

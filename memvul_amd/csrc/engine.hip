@@ -27,6 +27,7 @@
 #include "match_topk.h"
 #include "ref_f32.h"
 #include "sink_census.h"
+#include "route.h"
 
 namespace {
 
@@ -177,6 +178,7 @@ struct Work {
   // count and staging `st`: `pin` (PINNED, allocated at the set's first ticket) without the outputs it was not asked for
   bool sweep = false, ticket = false;
   bool guard = false, safe = false;  // the form the ticket was started in: mv_forward_ragged_end rescores the flagged rows of a guarded one
+  std::vector<uint8_t> routed;       // ... and the rows of its plan that the sink-token list of that moment routed (Job::routed; empty: none)
   Plan plan;
   int G = 0;
   Stage pin, st;
@@ -216,6 +218,13 @@ struct mv_handle {
     std::vector<uint32_t> over;
   } stage, stage2;         // stage2 / plan2: the guarded form's rescoring batch (the flagged rows of the batch just run, in plan order)
   Plan plan2;
+  // the sink-token list (mv_set_sink_tokens; route.h): acted on in the guarded form only — a sequence that carries a listed token at positions 1 .. len - 2 never
+  // runs in the default form, it seeds the rescoring plan directly
+  std::vector<int32_t> sink_tokens;     // as given (duplicates kept)
+  std::vector<uint32_t> sink_bitmap;    // route_bitmap of it over mv_config.vocab_size
+  std::vector<uint8_t> route_flags, routed;  // of the host batch being made: caller's row order / plan order (Job::routed)
+  Plan plan1;                           // ... and its plan without the routed rows (split_plan)
+  int64_t routed_seqs = 0;              // mv_route_stats
   std::vector<uint8_t> last_forms;             // mv_last_row_forms: the form that produced each row of the last host-buffer call, caller's row order
   int64_t guard_seqs = 0, guard_rescored = 0;  // mv_form_stats
   float* anchors = nullptr;
@@ -246,6 +255,14 @@ struct mv_handle {
   std::vector<uint8_t> c_pend_keep;     // ... and whether that run kept P(same)
   std::vector<uint8_t> c_forms;         // mv_corpus_row_forms
   bool c_pending = false;
+  // ... and the sink-token list there: the flags of every corpus row under the current list (route_flags_kernel), recomputed lazily after an upload or a list
+  // change; a guarded sweep leaves the routed rows of its range out and marks them forced (rescore_corpus encodes them without looking at c_over)
+  uint32_t* route_bm_dev = nullptr;     // the bitmap on the device [ceil(vocab / 32)]
+  uint8_t* c_route_dev = nullptr;       // [c_n]
+  std::vector<uint8_t> c_route;         // [c_n] on the host
+  bool c_route_stale = true;
+  std::vector<uint8_t> c_pend_force;    // [c_n] the row's pending run (c_pend_w) left it out: routed
+  std::vector<std::vector<int32_t>> c_idx_live;  // index lists of the split batches of sweeps in flight (alive until rescore_corpus has waited for them)
 
   // last-layer pruning ([CLS] rows only after the last layer's K / V projection) and its compact buffers
   bool cls_prune = true;   // env MEMVUL_CLS_PRUNE=0 disables
@@ -1103,6 +1120,7 @@ struct Job {
   bool safe = false;                              // the form of its passes (job_form: from the handle, when the job is made)
   bool guard = false;                             // the guarded form: default-form passes with the per-sequence monitor counts kept (out.over / the corpus' c_over)
   bool monitor = true;                            // false: a rescoring job (PassForm::monitor)
+  const uint8_t* routed = nullptr;                // the guarded form, plan order: rows the sink-token list routed — they ran in no pass yet, rescore_rows encodes them
 };
 
 // The form in force when a job is made (MV_F16 has none)
@@ -1195,6 +1213,7 @@ int rescore_rows(mv_handle* h, Work& wk, const Plan& pl, const Job& j, int B) {
   p2.order.clear(), p2.passes.clear(), p2.tokens = 0;
   v.ids.clear(), v.lens.clear();
   std::vector<int> widths;
+  int64_t n_routed = 0;
   for (const Pass& p : pl.passes)
     if (std::find(widths.begin(), widths.end(), p.width) == widths.end()) widths.push_back(p.width);
   for (const int w : widths) {
@@ -1203,7 +1222,9 @@ int rescore_rows(mv_handle* h, Work& wk, const Plan& pl, const Job& j, int B) {
       if (p.width != w) continue;
       for (int i = 0; i < p.rows; ++i) {
         const int r = p.first + i;
-        if (!guard_flagged(h, j.out.over[r], j.lens[r])) continue;
+        const bool forced = j.routed && j.routed[r];  // (its count was never written)
+        if (!forced && !guard_flagged(h, j.out.over[r], j.lens[r])) continue;
+        n_routed += forced;
         p2.order.push_back(r);
         v.lens.push_back(j.lens[r]);
         const int32_t* src = j.ids + p.tok + (int64_t)i * w;
@@ -1243,7 +1264,8 @@ int rescore_rows(mv_handle* h, Work& wk, const Plan& pl, const Job& j, int B) {
     h->last_forms[pl.order.empty() ? o : (size_t)pl.order[o]] = MV_FORM_SAFE;
   }
   if (j.u_dev) HIPCHK(h, hipStreamSynchronize(wk.stream));
-  h->guard_rescored += (int64_t)n2;
+  h->guard_rescored += (int64_t)n2 - n_routed;
+  h->routed_seqs += n_routed;
   return MV_OK;
 }
 
@@ -1254,6 +1276,7 @@ int rescore_corpus(mv_handle* h) {
   if (!h->c_pending) return MV_OK;
   if (int rc = sync_all(h)) return rc;
   h->c_pending = false;
+  h->c_idx_live.clear();
   Work& wk = h->work[0];
   std::vector<uint32_t> over((size_t)h->c_n);
   HIPCHK(h, hipMemcpyAsync(over.data(), h->c_over, (size_t)h->c_n * 4, hipMemcpyDeviceToHost, wk.stream));
@@ -1263,7 +1286,8 @@ int rescore_corpus(mv_handle* h) {
     const int w = h->c_pend_w[(size_t)r];
     if (!w) continue;
     h->c_pend_w[(size_t)r] = 0;
-    if (guard_flagged(h, over[(size_t)r], h->c_lens_host[(size_t)r])) groups[2 * w + h->c_pend_keep[(size_t)r]].push_back((int32_t)r);
+    const int forced = h->c_pend_force[(size_t)r];  // routed by the sink-token list of its sweep: it has run in no pass yet
+    if (forced || guard_flagged(h, over[(size_t)r], h->c_lens_host[(size_t)r])) groups[2 * w + h->c_pend_keep[(size_t)r]].push_back((int32_t)r);
   }
   const int G = h->n_anchors;
   PassForm pf;
@@ -1287,13 +1311,152 @@ int rescore_corpus(mv_handle* h) {
       if (int rc = match_dev(h, wk, wk.u, n, nullptr, nullptr, keep ? wk.psame : nullptr, 1, wk.best, wk.best_idx)) return rc;
       const int64_t ns = (int64_t)n * (keep ? G : 1);
       hipLaunchKernelGGL(corpus_scatter_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, wk.stream, (const float*)wk.best, (const int32_t*)wk.best_idx,
-                         keep ? (const float*)wk.psame : (const float*)nullptr, (const int32_t*)wk.d_idx, n, G, h->c_best, h->c_idx, h->c_psame);
+                         keep ? (const float*)wk.psame : (const float*)nullptr, (const int32_t*)wk.d_idx, n, G, h->c_best, h->c_idx, h->c_psame,
+                         (const uint32_t*)nullptr, (uint32_t*)nullptr);
       if (int rc = launch_check(h, "corpus_scatter")) return rc;
-      for (int i = 0; i < n; ++i) h->c_forms[(size_t)idx[first + i]] = MV_FORM_SAFE;
-      h->guard_rescored += n;
+      for (int i = 0; i < n; ++i) {
+        h->c_forms[(size_t)idx[first + i]] = MV_FORM_SAFE;
+        (h->c_pend_force[(size_t)idx[first + i]] ? h->routed_seqs : h->guard_rescored) += 1;
+      }
     }
   }
   HIPCHK(h, hipStreamSynchronize(wk.stream));
+  return MV_OK;
+}
+
+// ---- the sink-token list (mv_set_sink_tokens; route.h) ----------------------------------------------------------------------------------------------------------
+// A host batch of a guarded job: the rows of [B][S] the list routes (h->route_flags, caller's row order); returns how many.  0 without a list.
+int scan_routed(mv_handle* h, const Job& j, const int32_t* ids, const int32_t* lens, int B, int S) {
+  if (!j.guard || j.full || h->sink_tokens.empty()) return 0;
+  h->route_flags.resize((size_t)B);
+  return route_scan(ids, lens, B, S, h->sink_bitmap.data(), h->cfg.vocab_size, h->route_flags.data());
+}
+
+// A planned batch with routed rows (flags: caller's row order): every pass of pl keeps its rows and its width, with its unrouted rows first — pl.order is made
+// explicit for that — `routed` marks the others in plan order, and p1 gets one pass per pass of pl that has unrouted rows: those rows alone, min_len over them
+// (the ids of a pass are staged in plan order, so they are the head of the pass's ids: same Pass::tok).
+void split_plan(Plan& pl, int B, const int32_t* lens, const uint8_t* flags, std::vector<uint8_t>& routed, Plan& p1) {
+  if (pl.order.empty()) {
+    pl.order.resize((size_t)B);
+    for (int i = 0; i < B; ++i) pl.order[(size_t)i] = i;
+  }
+  routed.assign((size_t)B, 0);
+  p1.order.clear(), p1.passes.clear(), p1.tokens = pl.tokens;
+  for (const Pass& p : pl.passes) {
+    const auto b = pl.order.begin() + p.first, e = b + p.rows;
+    const auto mid = std::stable_partition(b, e, [&](int r) { return !flags[r]; });
+    const int nu = (int)(mid - b);
+    for (int i = nu; i < p.rows; ++i) routed[(size_t)(p.first + i)] = 1;
+    if (!nu) continue;
+    int m = INT32_MAX;
+    for (auto it = b; it != mid; ++it) m = std::min(m, lens[*it]);
+    p1.passes.push_back({p.first, nu, p.width, m, p.tok});
+  }
+}
+
+void gather(const Plan& pl, const int32_t* ids, const int32_t* lens, int S, int32_t* ids_out, int32_t* lens_out);
+
+// The resident corpus: h->c_route = the flag of every row under the current list, recomputed when an upload or a list change made it stale — one kernel over
+// the whole corpus, one copy back, one wait (workspace set 0's stream; nothing on the device reads what it writes).  An empty list flags nothing, without a launch.
+int ensure_route_flags(mv_handle* h) {
+  if (!h->c_route_stale) return MV_OK;
+  h->c_route.assign((size_t)h->c_n, 0);
+  if (!h->sink_tokens.empty() && h->c_n > 0) {
+    const hipStream_t s0 = h->work[0].stream;
+    if (!h->route_bm_dev)
+      if (int rc = dev_alloc(h, s0, &h->route_bm_dev, (int64_t)h->sink_bitmap.size(), false)) return rc;
+    if (!h->c_route_dev)
+      if (int rc = dev_alloc(h, s0, &h->c_route_dev, h->c_n, false)) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->route_bm_dev, h->sink_bitmap.data(), h->sink_bitmap.size() * 4, hipMemcpyHostToDevice, s0));
+    hipLaunchKernelGGL(route_flags_kernel, dim3((unsigned)((h->c_n + 3) / 4)), dim3(256), 0, s0, (const int32_t*)h->c_ids, (const int32_t*)h->c_lens, h->c_n, h->c_S,
+                       (const uint32_t*)h->route_bm_dev, h->cfg.vocab_size, h->c_route_dev);
+    if (int rc = launch_check(h, "route_flags")) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->c_route.data(), h->c_route_dev, (size_t)h->c_n, hipMemcpyDeviceToHost, s0));
+    HIPCHK(h, hipStreamSynchronize(s0));
+  }
+  h->c_route_stale = false;
+  return MV_OK;
+}
+
+// One batch of a guarded sweep that has routed rows (pass p of the sweep's plan, whose row 0 is corpus row j.c_row): its unrouted rows gathered by index list
+// into wk's pass buffer at the sweep's width — the path of rescore_corpus, in the default form with the per-row monitor attached — and their results, P(same)
+// rows and monitor counts scattered back to their corpus slots.  Asynchronous, like the in-place batches next to it.
+int run_split_batch(mv_handle* h, Work& wk, const Pass& p, const Job& j) {
+  std::vector<int32_t> idx;
+  int m = INT32_MAX;
+  for (int i = 0; i < p.rows; ++i) {
+    const int64_t r = j.c_row + p.first + i;
+    if (h->c_route[(size_t)r]) continue;
+    idx.push_back((int32_t)r);
+    m = std::min(m, h->c_lens_host[(size_t)r]);
+  }
+  if (idx.empty()) return MV_OK;  // every row routed: nothing runs in the default form
+  h->c_idx_live.push_back(std::move(idx));
+  const std::vector<int32_t>& ix = h->c_idx_live.back();
+  const int n = (int)ix.size(), w = p.width, G = h->n_anchors;
+  const bool keep = j.keep_psame;
+  auto run = [&]() -> int {
+    HIPCHK(h, hipMemcpyAsync(wk.d_idx, ix.data(), (size_t)n * 4, hipMemcpyHostToDevice, wk.stream));
+    const int64_t nt = (int64_t)n * w;
+    hipLaunchKernelGGL(corpus_gather_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, wk.stream, (const int32_t*)h->c_ids, (const int32_t*)h->c_lens,
+                       h->c_S, (const int32_t*)wk.d_idx, n, w, wk.d_ids, wk.d_lens);
+    if (int rc = launch_check(h, "corpus_gather")) return rc;
+    PassForm pf;
+    pf.safe = false; pf.monitor = true; pf.seq_over = wk.seq_over;
+    HIPCHK(h, hipMemsetAsync(pf.seq_over, 0, (size_t)n * 4, wk.stream));
+    if (int rc = encode_dev(h, wk, wk.d_ids, wk.d_lens, m, n, w, -1, wk.u, pf, false, w)) return rc;
+    if (int rc = match_dev(h, wk, wk.u, n, nullptr, nullptr, keep ? wk.psame : nullptr, 1, wk.best, wk.best_idx)) return rc;
+    const int64_t ns = (int64_t)n * (keep ? G : 1);
+    hipLaunchKernelGGL(corpus_scatter_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, wk.stream, (const float*)wk.best, (const int32_t*)wk.best_idx,
+                       keep ? (const float*)wk.psame : (const float*)nullptr, (const int32_t*)wk.d_idx, n, G, h->c_best, h->c_idx, h->c_psame,
+                       (const uint32_t*)wk.seq_over, h->c_over);
+    return launch_check(h, "corpus_scatter");
+  };
+  const int rc = run();
+  if (rc != MV_OK) hipStreamSynchronize(wk.stream);
+  return rc;
+}
+
+// run_in_order with routed rows among them: the batch staged in the split plan's order (as the by-length entry points stage theirs), the unrouted rows of every
+// pass in the default form, the routed rows through rescore_rows, the results back in the caller's order (and, mv_anchor_append, into the bank in one copy).
+int run_in_order_routed(mv_handle* h, const int32_t* lens, int B, int S, const Job& j) {
+  Plan& pl = h->plan;
+  Work& wk = h->work[0];
+  split_plan(pl, B, lens, h->route_flags.data(), h->routed, h->plan1);
+  auto& v = h->stage;
+  const size_t g2 = (size_t)h->n_anchors * 2, P = (size_t)h->P;
+  v.ids.resize((size_t)pl.tokens);
+  v.lens.resize((size_t)B);
+  v.over.resize((size_t)B);
+  gather(pl, j.ids, lens, S, v.ids.data(), v.lens.data());
+  Job s = j;
+  s.ids = v.ids.data(); s.lens = v.lens.data(); s.u_dev = nullptr; s.routed = h->routed.data();
+  s.out = Stage{};
+  s.out.over = v.over.data();
+  if (j.out.logits) { v.logits.resize((size_t)B * g2); s.out.logits = v.logits.data(); }
+  if (j.out.probs) { v.probs.resize((size_t)B * g2); s.out.probs = v.probs.data(); }
+  if (j.out.best) { v.best.resize((size_t)B * 2); s.out.best = v.best.data(); }
+  if (j.out.idx) { v.idx.resize((size_t)B); s.out.idx = v.idx.data(); }
+  if (j.out.embed || j.u_dev) { v.embed.resize((size_t)B * P); s.out.embed = v.embed.data(); }
+  if (!h->plan1.passes.empty())
+    if (int rc = run_passes(h, wk, h->plan1, 0, h->plan1.passes.size(), s)) return rc;
+  HIPCHK(h, hipStreamSynchronize(wk.stream));
+  if (int rc = rescore_rows(h, wk, pl, s, B)) return rc;
+  std::vector<float>& bank = h->stage2.embed;  // (rescore_rows is done with it)
+  if (j.u_dev) bank.resize((size_t)B * P);
+  for (size_t i = 0; i < (size_t)B; ++i) {
+    const size_t o = (size_t)pl.order[i];
+    if (j.out.logits) std::memcpy(j.out.logits + o * g2, s.out.logits + i * g2, g2 * 4);
+    if (j.out.probs) std::memcpy(j.out.probs + o * g2, s.out.probs + i * g2, g2 * 4);
+    if (j.out.best) { j.out.best[o * 2] = s.out.best[i * 2]; j.out.best[o * 2 + 1] = s.out.best[i * 2 + 1]; }
+    if (j.out.idx) j.out.idx[o] = s.out.idx[i];
+    if (j.out.embed) std::memcpy(j.out.embed + o * P, s.out.embed + i * P, P * 4);
+    if (j.u_dev) std::memcpy(bank.data() + o * P, s.out.embed + i * P, P * 4);
+  }
+  if (j.u_dev) {
+    HIPCHK(h, hipMemcpyAsync(j.u_dev, bank.data(), (size_t)B * P * 4, hipMemcpyHostToDevice, wk.stream));
+    HIPCHK(h, hipStreamSynchronize(wk.stream));
+  }
   return MV_OK;
 }
 
@@ -1302,6 +1465,7 @@ int rescore_corpus(mv_handle* h) {
 int run_in_order(mv_handle* h, const int32_t* lens, int B, int S, Job& j) {
   if (j.guard) { h->stage.over.resize((size_t)B); j.out.over = h->stage.over.data(); }
   if (int rc = plan_batch(h, lens, B, S, 0, false, 0, h->plan)) return rc;
+  if (scan_routed(h, j, j.ids, lens, B, S)) return run_in_order_routed(h, lens, B, S, j);
   if (int rc = run_passes(h, h->work[0], h->plan, 0, h->plan.passes.size(), j)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->work[0].stream));
   return j.full ? MV_OK : rescore_rows(h, h->work[0], h->plan, j, B);
@@ -1865,13 +2029,20 @@ int mv_forward_ragged(mv_handle* h, const int32_t* ids, const int32_t* lens, int
   v.best.resize((size_t)B * 2);
   v.idx.resize(B);
   if (embed) v.embed.resize((size_t)B * h->P);
-  gather(pl, ids, lens, S, v.ids.data(), v.lens.data());
   Job j;
+  job_form(h, j);
+  const Plan* p1 = &pl;  // the passes of the first run: without the rows the sink-token list routes
+  if (scan_routed(h, j, ids, lens, B, S)) {
+    split_plan(pl, B, lens, h->route_flags.data(), h->routed, h->plan1);
+    j.routed = h->routed.data();
+    p1 = &h->plan1;
+  }
+  gather(pl, ids, lens, S, v.ids.data(), v.lens.data());
   j.ids = v.ids.data(); j.lens = v.lens.data(); j.match = true;
   j.out = Stage{nullptr, nullptr, v.idx.data(), logits ? v.logits.data() : nullptr, probs ? v.probs.data() : nullptr, v.best.data(), embed ? v.embed.data() : nullptr};
-  job_form(h, j);
   if (j.guard) { v.over.resize(B); j.out.over = v.over.data(); }
-  if (int rc = run_passes(h, h->work[0], pl, 0, pl.passes.size(), j)) return rc;
+  if (!p1->passes.empty())
+    if (int rc = run_passes(h, h->work[0], *p1, 0, p1->passes.size(), j)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->work[0].stream));
   if (int rc = rescore_rows(h, h->work[0], pl, j, B)) return rc;
   scatter(h, pl.order, G, j.out, logits, probs, best, best_idx, embed);
@@ -1918,12 +2089,19 @@ int mv_forward_ragged_begin(mv_handle* h, const int32_t* ids, const int32_t* len
   if (!want_logits) st.logits = nullptr;
   if (!want_probs) st.probs = nullptr;
   if (!want_embed) st.embed = nullptr;
-  gather(wk.plan, ids, lens, S, st.ids, st.lens);
   Job j;
-  job_form(h, j);  // (the form in force HERE is the ticket's: mv_forward_ragged_end rescores a guarded one)
+  job_form(h, j);  // (the form in force HERE is the ticket's: mv_forward_ragged_end rescores a guarded one — and the sink-token list in force here its routing)
+  const Plan* p1 = &wk.plan;
+  wk.routed.clear();
+  if (scan_routed(h, j, ids, lens, B, S)) {
+    split_plan(wk.plan, B, lens, h->route_flags.data(), wk.routed, h->plan1);
+    p1 = &h->plan1;
+  }
+  gather(wk.plan, ids, lens, S, st.ids, st.lens);
   if (!j.guard) st.over = nullptr;
   j.ids = st.ids; j.lens = st.lens; j.match = true; j.out = st;
-  if (int rc = run_passes(h, wk, wk.plan, 0, wk.plan.passes.size(), j)) return rc;
+  if (!p1->passes.empty())
+    if (int rc = run_passes(h, wk, *p1, 0, p1->passes.size(), j)) return rc;
   wk.ticket = true; wk.G = h->n_anchors; wk.st = st; wk.guard = j.guard; wk.safe = j.safe;
   *ticket = set;
   return MV_OK;
@@ -1942,6 +2120,7 @@ int mv_forward_ragged_end(mv_handle* h, int ticket, float* logits, float* probs,
     // the batch's ids are still in the pinned staging; the bank rows the batch was matched against are the first wk.G of whatever the bank holds now
     Job j;
     j.ids = wk.st.ids; j.lens = wk.st.lens; j.match = true; j.out = wk.st; j.guard = wk.guard; j.safe = wk.safe;
+    j.routed = wk.routed.empty() ? nullptr : wk.routed.data();
     const int G_now = h->n_anchors;
     h->n_anchors = wk.G;
     const int rc = rescore_rows(h, wk, wk.plan, j, (int)wk.plan.order.size());
@@ -1997,6 +2176,10 @@ int mv_corpus_upload(mv_handle* h, const int32_t* ids, const int32_t* lens, int6
   HIPCHK(h, hipStreamSynchronize(s0));
   dev_free(h, h->c_ids); dev_free(h, h->c_lens); dev_free(h, h->c_best); dev_free(h, h->c_idx); dev_free(h, h->c_psame); dev_free(h, h->c_over);
   h->c_ids = nullptr; h->c_lens = nullptr; h->c_best = nullptr; h->c_idx = nullptr; h->c_psame = nullptr; h->c_over = nullptr;
+  dev_free(h, h->c_route_dev);
+  h->c_route_dev = nullptr;
+  h->c_route_stale = true;
+  h->c_idx_live.clear();
   h->c_pending = false;
   h->c_psame_rows = 0;
   if (int rc = dev_alloc(h, s0, &h->c_ids, n * S, false)) return rc;
@@ -2006,6 +2189,7 @@ int mv_corpus_upload(mv_handle* h, const int32_t* ids, const int32_t* lens, int6
   if (int rc = dev_alloc(h, s0, &h->c_over, n)) return rc;
   h->c_pend_w.assign((size_t)n, 0);
   h->c_pend_keep.assign((size_t)n, 0);
+  h->c_pend_force.assign((size_t)n, 0);
   h->c_forms.assign((size_t)n, MV_FORM_DEFAULT);
   HIPCHK(h, hipMemcpyAsync(h->c_ids, ids, (size_t)n * S * 4, hipMemcpyHostToDevice, s0));
   HIPCHK(h, hipMemcpyAsync(h->c_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, s0));
@@ -2047,8 +2231,13 @@ int mv_corpus_run_len(mv_handle* h, int64_t first, int64_t count, int batch, int
   Job j;
   j.c_row = first; j.keep_psame = keep_probs != 0;
   job_form(h, j);
+  // ... with a sink-token list: the rows it routes run in no batch here, they are marked pending and forced (rescore_corpus encodes them in the safe form)
+  const bool route = j.guard && !h->sink_tokens.empty();
+  if (route)
+    if (int rc = ensure_route_flags(h)) return rc;
   // the guarded form: the sweep stays asynchronous and only records the per-row counts (c_over) and what it ran (c_pend_w): rescore_corpus, from mv_corpus_results
   for (int64_t r = first; r < first + count; ++r) {
+    h->c_pend_force[(size_t)r] = (uint8_t)(route && h->c_route[(size_t)r]);
     h->c_pend_w[(size_t)r] = (int16_t)(j.guard ? S_use : 0);
     h->c_pend_keep[(size_t)r] = (uint8_t)(keep_probs != 0);
     h->c_forms[(size_t)r] = (uint8_t)(j.safe ? MV_FORM_SAFE : MV_FORM_DEFAULT);
@@ -2058,6 +2247,12 @@ int mv_corpus_run_len(mv_handle* h, int64_t first, int64_t count, int batch, int
     Work& wk = h->work[h->rr];
     wk.sweep = true;
     if (h->n_streams == 2) h->rr ^= 1;
+    const Pass& p = pl.passes[i];
+    const uint8_t* f = route ? h->c_route.data() + first + p.first : nullptr;
+    if (f && std::find(f, f + p.rows, (uint8_t)1) != f + p.rows) {  // (a batch with no routed row takes the in-place path)
+      if (int rc = run_split_batch(h, wk, p, j)) return rc;
+      continue;
+    }
     if (int rc = run_passes(h, wk, pl, i, i + 1, j)) return rc;
   }
   return MV_OK;
@@ -2235,6 +2430,55 @@ int mv_form_stats(mv_handle* h, int64_t* sequences, int64_t* rescored, int reset
   *sequences = h->guard_seqs;
   *rescored = h->guard_rescored;
   if (reset) h->guard_seqs = h->guard_rescored = 0;
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+int mv_set_sink_tokens(mv_handle* h, const int32_t* ids, int n) try {
+  if (!h) return MV_ERR_INVALID;
+  if (!h->finalized) return fail(h, MV_ERR_STATE, "mv_set_sink_tokens: weights not finalized (mv_finalize_weights)");
+  if (!h->precise) return fail(h, MV_ERR_STATE, "mv_set_sink_tokens: the list routes between forms of compute dtype MV_F16X8; this handle was finalized as MV_F16 or MV_F32");
+  if (n < 0 || n > MV_MAX_SINK_TOKENS || (n > 0 && !ids)) return fail(h, MV_ERR_INVALID, "mv_set_sink_tokens: 0 .. 64 token ids");
+  for (int i = 0; i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= h->cfg.vocab_size) return fail(h, MV_ERR_INVALID, "mv_set_sink_tokens: token id outside [0, vocab_size)");
+  std::vector<int32_t> list(ids, ids + n);
+  std::vector<uint32_t> bm = route_bitmap(ids, n, h->cfg.vocab_size);
+  h->sink_tokens.swap(list);  // (nothing below throws: the list is replaced whole or not at all)
+  h->sink_bitmap.swap(bm);
+  h->c_route_stale = true;
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+int mv_get_sink_tokens(mv_handle* h, int32_t* ids, int capacity) try {
+  if (!h) return MV_ERR_INVALID;
+  if (capacity < 0 || (capacity > 0 && !ids)) return fail(h, MV_ERR_INVALID, "mv_get_sink_tokens: bad argument");
+  const int n = (int)h->sink_tokens.size();
+  for (int i = 0; i < n && i < capacity; ++i) ids[i] = h->sink_tokens[(size_t)i];
+  return n;
+} catch (...) { return on_exception(h); }
+
+int mv_route_stats(mv_handle* h, int64_t* routed, int reset) try {
+  if (!h || !routed) return fail(h, MV_ERR_INVALID, "mv_route_stats: bad argument");
+  *routed = h->routed_seqs;
+  if (reset) h->routed_seqs = 0;
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+int mv_route_scan(const int32_t* ids, const int32_t* lens, int B, int S, const int32_t* tokens, int n, int vocab, uint8_t* flags) try {
+  if (!ids || !lens || !flags || B < 0 || S <= 0 || vocab <= 0 || n < 0 || n > MV_MAX_SINK_TOKENS || (n > 0 && !tokens)) return MV_ERR_INVALID;
+  for (int i = 0; i < n; ++i)
+    if (tokens[i] < 0 || tokens[i] >= vocab) return MV_ERR_INVALID;
+  const std::vector<uint32_t> bm = route_bitmap(tokens, n, vocab);
+  route_scan(ids, lens, B, S, bm.data(), vocab, flags);
+  return MV_OK;
+} catch (...) { return on_exception(nullptr); }
+
+int mv_corpus_route_flags(mv_handle* h, int64_t first, int64_t count, uint8_t* flags) try {
+  if (!h || !flags) return fail(h, MV_ERR_INVALID, "mv_corpus_route_flags: bad argument");
+  if (!h->c_ids) return fail(h, MV_ERR_STATE, "no resident corpus (mv_corpus_upload)");
+  if (first < 0 || count <= 0 || first + count > h->c_n) return fail(h, MV_ERR_INVALID, "mv_corpus_route_flags: bad range");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = ensure_route_flags(h)) return rc;
+  std::memcpy(flags, h->c_route.data() + first, (size_t)count);
   return MV_OK;
 } catch (...) { return on_exception(h); }
 

@@ -365,10 +365,12 @@ __global__ __launch_bounds__(256) void corpus_gather_kernel(const int32_t* __res
   ids_out[t] = ids[r * S + c];
   if (c == 0) lens_out[i] = lens[r];
 }
-// ... and the rescored rows' best P(same), best anchor and (psame != NULL) P(same) rows [n][G] back to their corpus slots
+// ... and the rescored rows' best P(same), best anchor and (psame != NULL) P(same) rows [n][G] back to their corpus slots (over != NULL: a sweep batch that
+// left its routed rows out, mv_set_sink_tokens — the per-row monitor counts of the rows it ran go back too)
 __global__ __launch_bounds__(256) void corpus_scatter_kernel(const float* __restrict__ best, const int32_t* __restrict__ best_idx, const float* __restrict__ psame,
                                                              const int32_t* __restrict__ idx, int n, int G, float* __restrict__ c_best,
-                                                             int32_t* __restrict__ c_idx, float* __restrict__ c_psame) {
+                                                             int32_t* __restrict__ c_idx, float* __restrict__ c_psame, const uint32_t* __restrict__ over,
+                                                             uint32_t* __restrict__ c_over) {
   const int cols = psame ? G : 1;
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= (int64_t)n * cols) return;
@@ -379,5 +381,6 @@ __global__ __launch_bounds__(256) void corpus_scatter_kernel(const float* __rest
     c_best[2 * r] = best[2 * i];
     c_best[2 * r + 1] = best[2 * i + 1];
     c_idx[r] = best_idx[i];
+    if (over) c_over[r] = over[i];
   }
 }

@@ -188,6 +188,8 @@ class ModelMemory(Model):
         # engine_options["compute_dtype"] or $MEMVUL_COMPUTE = precise | f16x8 | f16 | fast | safe | guarded.  An unknown name raises here
         # (ValueError), not inside ctypes.
         # "safe" / "guarded" = MV_F16X8 in that form (include/memvul_hip.h mv_set_form): the name itself goes to Engine.load_state_dict, which sets the form.
+        # engine_options["sink_tokens"] = [id, ...] (or $MEMVUL_SINK_TOKENS): the sink-token list of the guarded form — Engine.load_state_dict applies it after
+        # finalize and raises unless the form is "guarded" (binding.sink_tokens_policy).
         cd = opts.pop("compute_dtype", None)
         cd = wanted_form(cd) or compute_dtype_of(cd)
         if self._engine is not None:

@@ -65,6 +65,7 @@ class ModelSingle(Model):
         opts = dict(max_tokens=128 * 512, max_batch=512, max_anchors=1)
         opts.update(self._engine_options)
         opts_compute = opts.pop("compute_dtype", None)  # None: binding.default_compute() — precise unless $MEMVUL_COMPUTE says otherwise
+        # (engine_options["sink_tokens"] = [id, ...] / $MEMVUL_SINK_TOKENS: the guarded form's sink-token list, applied by Engine.load_state_dict — guarded only)
         if self._engine is not None:
             self._engine.close()
         self._engine = Engine(self._device_index, vocab_size=sd[PFX_BERT + "embeddings.word_embeddings.weight"].shape[0], layers=layers,
