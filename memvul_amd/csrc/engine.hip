@@ -129,6 +129,40 @@ struct Stage {
   uint32_t* over = nullptr;  // the guarded form: per row, the monitor items over MV_SINK_COLLISION (AttnArgs::seq_over)
 };
 
+// Which results a staging holds, and a view of one without the others
+struct Want {
+  bool logits = false, probs = false, best = false, idx = false, embed = false, over = false;
+};
+inline Want wanted(const Stage& o, bool embed) { return {o.logits != nullptr, o.probs != nullptr, o.best != nullptr, o.idx != nullptr, embed, false}; }
+inline Stage only(Stage s, const Want& w) {
+  if (!w.logits) s.logits = nullptr;
+  if (!w.probs) s.probs = nullptr;
+  if (!w.best) s.best = nullptr;
+  if (!w.idx) s.idx = nullptr;
+  if (!w.embed) s.embed = nullptr;
+  if (!w.over) s.over = nullptr;
+  return s;
+}
+
+// Pageable host staging of the synchronous entry points
+struct HostStage {
+  std::vector<int32_t> ids, lens, idx;
+  std::vector<float> logits, probs, best, embed;
+  std::vector<uint32_t> over;
+  // sized for `rows` rows of `tokens` ids in all against G anchors (ids and lengths always, of the results those wanted): the view of it
+  Stage view(size_t rows, size_t tokens, size_t G, size_t P, const Want& w) {
+    ids.resize(tokens);
+    lens.resize(rows);
+    if (w.logits) logits.resize(rows * G * 2);
+    if (w.probs) probs.resize(rows * G * 2);
+    if (w.best) best.resize(rows * 2);
+    if (w.idx) idx.resize(rows);
+    if (w.embed) embed.resize(rows * P);
+    if (w.over) over.resize(rows);
+    return only(Stage{ids.data(), lens.data(), idx.data(), logits.data(), probs.data(), best.data(), embed.data(), over.data()}, w);
+  }
+};
+
 // How a batch runs: its row order (plan row i = caller row order[i]; empty = the identity) and its passes, each rows [first, first + rows) of that order
 // at `width` tokens per row, its ids at token `tok` of the staging
 struct Pass {
@@ -139,6 +173,21 @@ struct Plan {
   std::vector<int> order;
   std::vector<Pass> passes;
   int64_t tokens = 0;  // ids of every pass
+};
+
+// What run_passes does with a planned batch besides encoding it, and where the results go
+struct Job {
+  const int32_t *ids = nullptr, *lens = nullptr;  // host, plan order: the ids of every pass at its own width, back to back (Pass::tok); NULL: the resident corpus
+  int64_t c_row = 0; bool keep_psame = false;    // ... whose row c_row is plan row 0: ids read in place at pitch c_S, results (and P(same)) to its arrays
+  Stage out;                                      // host results, plan order (NULL: not asked for; out.ids / out.lens unused)
+  bool match = false;                             // + the matcher: the best anchor always, logits / probs where `out` asks for them
+  float* u_dev = nullptr;                         // the encoder's output to the device here (mv_anchor_append: the bank) instead of wk.u
+  int n_layers = -1; bool full = false;           // mv_debug_encode: the layers to run, and the full last layer (encode_dev)
+  int G = 0;                                      // the anchors it is matched against: the bank's first G rows (job_form: the count when the job is made)
+  bool safe = false;                              // the form of its passes (job_form: from the handle, when the job is made)
+  bool guard = false;                             // the guarded form: default-form passes with the per-sequence monitor counts kept (out.over / the corpus' c_over)
+  bool monitor = true;                            // false: a rescoring job (PassForm::monitor)
+  const uint8_t* routed = nullptr;                // the guarded form, plan order: rows the sink-token list routed — they ran in no pass yet, rescore_rows encodes them
 };
 
 // Activation buffers of ONE in-flight batch and the stream its kernels run on, and what is in flight there
@@ -174,14 +223,13 @@ struct Work {
   half_t* vlo_sp = nullptr;   // 2^11 x the low parts of V of the special rows [B 12][64][2] (GemmArgs::vlo_sp -> AttnArgs::vlo_sp)
   float *qkv32 = nullptr, *ctx32 = nullptr, *h32 = nullptr;  // MV_F32: Q | K | V [T][2304], attention context [T][768], GELU output [T][3072], allocated by mv_finalize_weights
   int32_t* tile_both = nullptr;  // cls_aside: per 256-row tile of the pass, non-zero = its sequence is shorter than cls_min_len (GemmArgs::tile_both)
-  // in flight on this stream: batches of a resident sweep (check_ready waits for them) and / or a ticket of mv_forward_ragged_begin — its plan, anchor
-  // count and staging `st`: `pin` (PINNED, allocated at the set's first ticket) without the outputs it was not asked for
+  // in flight on this stream: batches of a resident sweep (check_ready waits for them) and / or a ticket of mv_forward_ragged_begin — its plan and the job it
+  // was begun with (form, anchor count, and as ids / out the view of `pin` it is staged in: PINNED, allocated at the set's first ticket)
   bool sweep = false, ticket = false;
-  bool guard = false, safe = false;  // the form the ticket was started in: mv_forward_ragged_end rescores the flagged rows of a guarded one
-  std::vector<uint8_t> routed;       // ... and the rows of its plan that the sink-token list of that moment routed (Job::routed; empty: none)
   Plan plan;
-  int G = 0;
-  Stage pin, st;
+  Job job;
+  std::vector<uint8_t> routed;  // the rows of the plan that the sink-token list of that moment routed (job.routed points here)
+  Stage pin;
 };
 
 struct mv_handle {
@@ -212,11 +260,7 @@ struct mv_handle {
   int n_alloc = 2;         // sets created
   int rr = 0;              // workspace set of the next resident-sweep batch
   Plan plan;               // the synchronous entry points' plan and by-length staging (they run on set 0, behind whatever ticket is in flight there)
-  struct {
-    std::vector<int32_t> ids, lens, idx;
-    std::vector<float> logits, probs, best, embed;
-    std::vector<uint32_t> over;
-  } stage, stage2;         // stage2 / plan2: the guarded form's rescoring batch (the flagged rows of the batch just run, in plan order)
+  HostStage stage, stage2;  // stage2 / plan2: the guarded form's rescoring batch (the flagged rows of the batch just run, in plan order)
   Plan plan2;
   // the sink-token list (mv_set_sink_tokens; route.h): acted on in the guarded form only — a sequence that carries a listed token at positions 1 .. len - 2 never
   // runs in the default form, it seeds the rescoring plan directly
@@ -897,9 +941,8 @@ int max_rows_for(mv_handle* h, int S_in) {
 // K9 + K10 fused (match_topk.h): logits / probs / psame_out are optional full outputs; k >= 1 selects the best anchor
 // (and, with topk_p / topk_idx, the k best).  4 issue reports per workgroup when that already fills the chip, else 1
 // (the same bits either way).
-int match_dev(mv_handle* h, Work& wk, const float* u_dev, int B, float* logits, float* probs, float* psame_out, int k, float* best_out,
+int match_dev(mv_handle* h, Work& wk, const float* u_dev, int B, int G, float* logits, float* probs, float* psame_out, int k, float* best_out,
               int32_t* idx_out, float* topk_p = nullptr, int32_t* topk_idx = nullptr) {
-  const int G = h->n_anchors;
   if (G <= 0) return fail(h, MV_ERR_STATE, "anchor bank is empty (call mv_anchor_append / mv_anchor_set first)");
   MatchArgs a{};
   a.B = B; a.G = G; a.same_idx = h->cfg.same_idx; a.k = k;
@@ -1070,27 +1113,32 @@ int upload_f16(mv_handle* h, hipStream_t stream, half_t** dst, const float* src,
   return MV_OK;
 }
 
-// ---- the one planner and the one pass loop -------------------------------------------------------------------------------------------------------------------
+// ---- the one planner, the one pass cutter, the one pass loop, the one row scatter ---------------------------------------------------------------------------------
+// cut_passes: appends to pl the passes of its rows [start, end) at `width` tokens per row: max_rows_for(width) rows each (cap > 0: at most cap), min_len over
+// len_of(plan row).
+template <typename LenOf>
+int cut_passes(mv_handle* h, Plan& pl, int start, int end, int width, int cap, LenOf len_of) {
+  int rows = max_rows_for(h, width);
+  if (cap > 0 && cap < rows) rows = cap;
+  if (rows <= 0) return fail(h, MV_ERR_CAPACITY, "mv_config.max_tokens too small for one row of this length");
+  for (int first = start; first < end; first += rows) {
+    const int n = end - first < rows ? end - first : rows;
+    int m = INT32_MAX;
+    for (int i = first; i < first + n; ++i) m = std::min(m, (int)len_of(i));
+    pl.passes.push_back({first, n, width, m, pl.tokens});
+    pl.tokens += (int64_t)n * width;
+  }
+  return MV_OK;
+}
+
 // plan_batch: rows [0, B) of lengths `lens` into pl.  by_length false: the identity order in passes of max_rows_for(S) rows at width S.  by_length true
 // (mv_forward_ragged*: a pad-to-longest batch of UNSORTED rows): the rows ordered (stably) by the padded length of their own token count, a run of one padded
 // length merged into the next longer one while it holds fewer than min_tokens padded tokens, each group then cut into passes of max_rows_for(its width) rows.
 // max_rows > 0 caps the rows of a pass further (the resident sweep's batch).
 int plan_batch(mv_handle* h, const int32_t* lens, int B, int S, int min_tokens, bool by_length, int max_rows, Plan& pl) {
   pl.order.clear(), pl.passes.clear(), pl.tokens = 0;
-  auto cut = [&](int start, int end, int width) -> int {  // rows [start, end) of the order, at `width` tokens per row
-    int rows = max_rows_for(h, width);
-    if (max_rows > 0 && max_rows < rows) rows = max_rows;
-    if (rows <= 0) return fail(h, MV_ERR_CAPACITY, "mv_config.max_tokens too small for one row of this length");
-    for (int first = start; first < end; first += rows) {
-      const int n = end - first < rows ? end - first : rows;
-      int m = INT32_MAX;
-      for (int i = first; i < first + n; ++i) m = std::min(m, lens[pl.order.empty() ? i : pl.order[i]]);
-      pl.passes.push_back({first, n, width, m, pl.tokens});
-      pl.tokens += (int64_t)n * width;
-    }
-    return MV_OK;
-  };
-  if (!by_length) return cut(0, B, S);
+  auto len_of = [&](int i) { return lens[pl.order.empty() ? i : pl.order[i]]; };  // of plan row i
+  if (!by_length) return cut_passes(h, pl, 0, B, S, max_rows, len_of);
   auto pad = [&](int r) { return padded_len(lens[r] < 1 ? 1 : lens[r]); };  // of caller row r
   pl.order.resize(B);
   for (int i = 0; i < B; ++i) {
@@ -1103,28 +1151,15 @@ int plan_batch(mv_handle* h, const int32_t* lens, int B, int S, int min_tokens, 
     const int width = pad(pl.order[end - 1]);
     if (end < B && pad(pl.order[end]) == width) continue;                   // inside a run of one padded length
     if (end < B && (int64_t)(end - start) * width < min_tokens) continue;  // too small a pass: these rows travel with the next longer group
-    if (int rc = cut(start, end, width < S ? width : S)) return rc;
+    if (int rc = cut_passes(h, pl, start, end, width < S ? width : S, max_rows, len_of)) return rc;
     start = end;
   }
   return MV_OK;
 }
 
-// What run_passes does with a planned batch besides encoding it, and where the results go
-struct Job {
-  const int32_t *ids = nullptr, *lens = nullptr;  // host, plan order: the ids of every pass at its own width, back to back (Pass::tok); NULL: the resident corpus
-  int64_t c_row = 0; bool keep_psame = false;    // ... whose row c_row is plan row 0: ids read in place at pitch c_S, results (and P(same)) to its arrays
-  Stage out;                                      // host results, plan order (NULL: not asked for; out.ids / out.lens unused)
-  bool match = false;                             // + the matcher: the best anchor always, logits / probs where `out` asks for them
-  float* u_dev = nullptr;                         // the encoder's output to the device here (mv_anchor_append: the bank) instead of wk.u
-  int n_layers = -1; bool full = false;           // mv_debug_encode: the layers to run, and the full last layer (encode_dev)
-  bool safe = false;                              // the form of its passes (job_form: from the handle, when the job is made)
-  bool guard = false;                             // the guarded form: default-form passes with the per-sequence monitor counts kept (out.over / the corpus' c_over)
-  bool monitor = true;                            // false: a rescoring job (PassForm::monitor)
-  const uint8_t* routed = nullptr;                // the guarded form, plan order: rows the sink-token list routed — they ran in no pass yet, rescore_rows encodes them
-};
-
-// The form in force when a job is made (MV_F16 has none)
+// The form and the anchor count in force when a job is made (MV_F16 has no forms)
 void job_form(const mv_handle* h, Job& j) {
+  j.G = h->n_anchors;
   j.safe = h->precise && h->form == MV_FORM_SAFE;
   j.guard = h->precise && h->form == MV_FORM_GUARDED;
 }
@@ -1133,7 +1168,7 @@ void job_form(const mv_handle* h, Job& j) {
 // lengths: one upload when they fit wk's buffers, else one per pass at its own width.  Host results: one download each when the rows fit wk's max_batch
 // rows (every pass writes at its own rows there), else one per pass.
 int run_passes(mv_handle* h, Work& wk, const Plan& pl, size_t p0, size_t p1, const Job& j) {
-  const int G = h->n_anchors;
+  const int G = j.G;
   const size_t P = (size_t)h->P;
   const Pass &a = pl.passes[p0], &z = pl.passes[p1 - 1];
   const int rows = z.first + z.rows - a.first;
@@ -1175,9 +1210,9 @@ int run_passes(mv_handle* h, Work& wk, const Plan& pl, size_t p0, size_t p1, con
       if (int rc = encode_dev(h, wk, ids, lens, p.min_len, p.rows, p.width, j.n_layers, u, pf, j.full, j.ids ? p.width : h->c_S)) return rc;
       if (!j.ids) {
         const size_t c = (size_t)(j.c_row + p.first);
-        if (int rc = match_dev(h, wk, u, p.rows, nullptr, nullptr, j.keep_psame ? h->c_psame + c * G : nullptr, 1, h->c_best + c * 2, h->c_idx + c)) return rc;
+        if (int rc = match_dev(h, wk, u, p.rows, G, nullptr, nullptr, j.keep_psame ? h->c_psame + c * G : nullptr, 1, h->c_best + c * 2, h->c_idx + c)) return rc;
       } else if (j.match) {  // only the outputs the caller asked for leave the kernel (the best anchor always does)
-        if (int rc = match_dev(h, wk, u, p.rows, j.out.logits ? wk.logits + r * G * 2 : nullptr, j.out.probs ? wk.probs + r * G * 2 : nullptr, nullptr, 1,
+        if (int rc = match_dev(h, wk, u, p.rows, G, j.out.logits ? wk.logits + r * G * 2 : nullptr, j.out.probs ? wk.probs + r * G * 2 : nullptr, nullptr, 1,
                                wk.best + r * 2, wk.best_idx + r)) return rc;
       }
       if (!one_down)
@@ -1188,6 +1223,19 @@ int run_passes(mv_handle* h, Work& wk, const Plan& pl, size_t p0, size_t p1, con
   const int rc = run();
   if (rc != MV_OK) hipStreamSynchronize(wk.stream);
   return rc;
+}
+
+// The one row scatter: row i of src to row map[i] of dst (an empty map: to row i), n rows — the results both hold.
+void scatter_rows(const Stage& src, const Stage& dst, const std::vector<int>& map, size_t n, size_t G, size_t P) {
+  const size_t g2 = G * 2;
+  for (size_t i = 0; i < n; ++i) {
+    const size_t o = map.empty() ? i : (size_t)map[i];
+    if (src.logits && dst.logits) std::memcpy(dst.logits + o * g2, src.logits + i * g2, g2 * 4);
+    if (src.probs && dst.probs) std::memcpy(dst.probs + o * g2, src.probs + i * g2, g2 * 4);
+    if (src.best && dst.best) { dst.best[o * 2] = src.best[i * 2]; dst.best[o * 2 + 1] = src.best[i * 2 + 1]; }
+    if (src.idx && dst.idx) dst.idx[o] = src.idx[i];
+    if (src.embed && dst.embed) std::memcpy(dst.embed + o * P, src.embed + i * P, P * 4);
+  }
 }
 
 // ---- the guarded form -------------------------------------------------------------------------------------------------------------------------------------
@@ -1202,14 +1250,15 @@ bool guard_flagged(const mv_handle* h, uint32_t over, int len) {
 }
 
 // After the default-form passes of a guarded job (j.out.over holds the counts, the stream is idle): a second plan over the flagged rows — each at the width of
-// the pass it first ran in, the flagged rows of every pass of one width sharing passes — run in the safe form with the monitor detached; those rows' results in
-// j.out (and in the bank, j.u_dev) are overwritten.  Records the form of each of the B rows in the caller's order (mv_last_row_forms).
+// the pass it first ran in, the flagged rows of every pass of one width sharing passes — run in the safe form with the monitor detached, against the job's own
+// anchor count; those rows' results in j.out (and in the bank, j.u_dev: one copy per row) are overwritten.  Records the form of each of the B rows in the
+// caller's order (mv_last_row_forms).
 int rescore_rows(mv_handle* h, Work& wk, const Plan& pl, const Job& j, int B) {
   h->last_forms.assign((size_t)B, (uint8_t)(j.safe ? MV_FORM_SAFE : MV_FORM_DEFAULT));
   if (!j.guard) return MV_OK;
   h->guard_seqs += B;
   Plan& p2 = h->plan2;
-  auto& v = h->stage2;
+  HostStage& v = h->stage2;
   p2.order.clear(), p2.passes.clear(), p2.tokens = 0;
   v.ids.clear(), v.lens.clear();
   std::vector<int> widths;
@@ -1231,35 +1280,19 @@ int rescore_rows(mv_handle* h, Work& wk, const Plan& pl, const Job& j, int B) {
         v.ids.insert(v.ids.end(), src, src + w);
       }
     }
-    const int end = (int)p2.order.size(), rows = max_rows_for(h, w);
-    for (int first = start; first < end; first += rows) {
-      const int n = end - first < rows ? end - first : rows;
-      int m = INT32_MAX;
-      for (int i = first; i < first + n; ++i) m = std::min(m, v.lens[i]);
-      p2.passes.push_back({first, n, w, m, p2.tokens});
-      p2.tokens += (int64_t)n * w;
-    }
+    if (int rc = cut_passes(h, p2, start, (int)p2.order.size(), w, 0, [&](int i) { return v.lens[(size_t)i]; })) return rc;
   }
-  const size_t n2 = p2.order.size();
+  const size_t n2 = p2.order.size(), P = (size_t)h->P;
   if (!n2) return MV_OK;
-  const size_t g2 = (size_t)h->n_anchors * 2, P = (size_t)h->P;
-  const bool want_embed = j.out.embed || j.u_dev;
   Job r;
-  r.ids = v.ids.data(); r.lens = v.lens.data(); r.match = j.match; r.safe = true; r.monitor = false;
-  if (j.out.logits) { v.logits.resize(n2 * g2); r.out.logits = v.logits.data(); }
-  if (j.out.probs) { v.probs.resize(n2 * g2); r.out.probs = v.probs.data(); }
-  if (j.out.best) { v.best.resize(n2 * 2); r.out.best = v.best.data(); }
-  if (j.out.idx) { v.idx.resize(n2); r.out.idx = v.idx.data(); }
-  if (want_embed) { v.embed.resize(n2 * P); r.out.embed = v.embed.data(); }
+  r.match = j.match; r.G = j.G; r.safe = true; r.monitor = false;
+  r.out = v.view(n2, (size_t)p2.tokens, (size_t)j.G, P, wanted(j.out, j.out.embed || j.u_dev));  // (the ids and the lengths are in it already)
+  r.ids = r.out.ids; r.lens = r.out.lens;
   if (int rc = run_passes(h, wk, p2, 0, p2.passes.size(), r)) return rc;
   HIPCHK(h, hipStreamSynchronize(wk.stream));
+  scatter_rows(r.out, j.out, p2.order, n2, (size_t)j.G, P);
   for (size_t i = 0; i < n2; ++i) {
     const size_t o = (size_t)p2.order[i];
-    if (j.out.logits) std::memcpy(j.out.logits + o * g2, r.out.logits + i * g2, g2 * 4);
-    if (j.out.probs) std::memcpy(j.out.probs + o * g2, r.out.probs + i * g2, g2 * 4);
-    if (j.out.best) { j.out.best[o * 2] = r.out.best[i * 2]; j.out.best[o * 2 + 1] = r.out.best[i * 2 + 1]; }
-    if (j.out.idx) j.out.idx[o] = r.out.idx[i];
-    if (j.out.embed) std::memcpy(j.out.embed + o * P, r.out.embed + i * P, P * 4);
     if (j.u_dev) HIPCHK(h, hipMemcpyAsync(j.u_dev + o * P, r.out.embed + i * P, P * 4, hipMemcpyHostToDevice, wk.stream));
     h->last_forms[pl.order.empty() ? o : (size_t)pl.order[o]] = MV_FORM_SAFE;
   }
@@ -1269,9 +1302,37 @@ int rescore_rows(mv_handle* h, Work& wk, const Plan& pl, const Job& j, int B) {
   return MV_OK;
 }
 
-// The resident corpus: every row a guarded sweep ran since the last rescoring (c_pend_w) whose count (c_over) flags it — gathered by index list into a pass
-// buffer at the s_eff width of its run, in full batches, encoded in the safe form with the monitor detached, matched, and scattered back to its corpus slots
-// (P(same) rows too where the run kept them).  On workspace set 0, after every batch of the sweep has finished; waits.
+// The one indexed pass over the resident corpus: rows idx[0, n) gathered into wk's pass buffer at width w, encoded in the form pf (counts: with the per-row
+// monitor counts kept), matched, and scattered back to their corpus slots — keep: their P(same) rows too, counts: the counts to c_over.  Asynchronous on wk:
+// idx stays alive until that stream has been waited for; after a failure it waits for what it enqueued.
+int run_corpus_rows(mv_handle* h, Work& wk, const int32_t* idx, int n, int w, int min_len, PassForm pf, bool keep, bool counts) {
+  const int G = h->n_anchors;
+  auto run = [&]() -> int {
+    HIPCHK(h, hipMemcpyAsync(wk.d_idx, idx, (size_t)n * 4, hipMemcpyHostToDevice, wk.stream));
+    const int64_t nt = (int64_t)n * w;
+    hipLaunchKernelGGL(corpus_gather_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, wk.stream, (const int32_t*)h->c_ids, (const int32_t*)h->c_lens,
+                       h->c_S, (const int32_t*)wk.d_idx, n, w, wk.d_ids, wk.d_lens);
+    if (int rc = launch_check(h, "corpus_gather")) return rc;
+    if (counts) {
+      pf.seq_over = wk.seq_over;
+      HIPCHK(h, hipMemsetAsync(pf.seq_over, 0, (size_t)n * 4, wk.stream));
+    }
+    if (int rc = encode_dev(h, wk, wk.d_ids, wk.d_lens, min_len, n, w, -1, wk.u, pf, false, w)) return rc;
+    if (int rc = match_dev(h, wk, wk.u, n, G, nullptr, nullptr, keep ? wk.psame : nullptr, 1, wk.best, wk.best_idx)) return rc;
+    const int64_t ns = (int64_t)n * (keep ? G : 1);
+    hipLaunchKernelGGL(corpus_scatter_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, wk.stream, (const float*)wk.best, (const int32_t*)wk.best_idx,
+                       keep ? (const float*)wk.psame : (const float*)nullptr, (const int32_t*)wk.d_idx, n, G, h->c_best, h->c_idx, h->c_psame,
+                       counts ? (const uint32_t*)wk.seq_over : (const uint32_t*)nullptr, counts ? h->c_over : (uint32_t*)nullptr);
+    return launch_check(h, "corpus_scatter");
+  };
+  const int rc = run();
+  if (rc != MV_OK) hipStreamSynchronize(wk.stream);
+  return rc;
+}
+
+// The resident corpus: every row a guarded sweep ran since the last rescoring (c_pend_w) whose count (c_over) flags it, and every row it left out as routed —
+// grouped by the s_eff width of the run (and whether it kept P(same)), each group cut into full passes and run through run_corpus_rows in the safe form with the
+// monitor detached.  On workspace set 0, after every batch of the sweep has finished; waits once, at the end.
 int rescore_corpus(mv_handle* h) {
   if (!h->c_pending) return MV_OK;
   if (int rc = sync_all(h)) return rc;
@@ -1289,34 +1350,19 @@ int rescore_corpus(mv_handle* h) {
     const int forced = h->c_pend_force[(size_t)r];  // routed by the sink-token list of its sweep: it has run in no pass yet
     if (forced || guard_flagged(h, over[(size_t)r], h->c_lens_host[(size_t)r])) groups[2 * w + h->c_pend_keep[(size_t)r]].push_back((int32_t)r);
   }
-  const int G = h->n_anchors;
   PassForm pf;
   pf.safe = true; pf.monitor = false;
   for (auto& kv : groups) {
     const int w = kv.first >> 1;
-    const bool keep = (kv.first & 1) && h->c_psame && h->c_G == G;
+    const bool keep = (kv.first & 1) && h->c_psame && h->c_G == h->n_anchors;
     const std::vector<int32_t>& idx = kv.second;
-    const int rows = max_rows_for(h, w);
-    if (rows <= 0) return fail(h, MV_ERR_CAPACITY, "mv_config.max_tokens too small for one row of this length");
-    for (size_t first = 0; first < idx.size(); first += (size_t)rows) {
-      const int n = (int)std::min((size_t)rows, idx.size() - first);
-      int m = INT32_MAX;
-      for (int i = 0; i < n; ++i) m = std::min(m, h->c_lens_host[(size_t)idx[first + i]]);
-      HIPCHK(h, hipMemcpyAsync(wk.d_idx, idx.data() + first, (size_t)n * 4, hipMemcpyHostToDevice, wk.stream));
-      const int64_t nt = (int64_t)n * w;
-      hipLaunchKernelGGL(corpus_gather_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, wk.stream, (const int32_t*)h->c_ids, (const int32_t*)h->c_lens,
-                         h->c_S, (const int32_t*)wk.d_idx, n, w, wk.d_ids, wk.d_lens);
-      if (int rc = launch_check(h, "corpus_gather")) return rc;
-      if (int rc = encode_dev(h, wk, wk.d_ids, wk.d_lens, m, n, w, -1, wk.u, pf, false, w)) return rc;
-      if (int rc = match_dev(h, wk, wk.u, n, nullptr, nullptr, keep ? wk.psame : nullptr, 1, wk.best, wk.best_idx)) return rc;
-      const int64_t ns = (int64_t)n * (keep ? G : 1);
-      hipLaunchKernelGGL(corpus_scatter_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, wk.stream, (const float*)wk.best, (const int32_t*)wk.best_idx,
-                         keep ? (const float*)wk.psame : (const float*)nullptr, (const int32_t*)wk.d_idx, n, G, h->c_best, h->c_idx, h->c_psame,
-                         (const uint32_t*)nullptr, (uint32_t*)nullptr);
-      if (int rc = launch_check(h, "corpus_scatter")) return rc;
-      for (int i = 0; i < n; ++i) {
-        h->c_forms[(size_t)idx[first + i]] = MV_FORM_SAFE;
-        (h->c_pend_force[(size_t)idx[first + i]] ? h->routed_seqs : h->guard_rescored) += 1;
+    Plan g;  // the group's rows in passes
+    if (int rc = cut_passes(h, g, 0, (int)idx.size(), w, 0, [&](int i) { return h->c_lens_host[(size_t)idx[(size_t)i]]; })) return rc;
+    for (const Pass& p : g.passes) {
+      if (int rc = run_corpus_rows(h, wk, idx.data() + p.first, p.rows, w, p.min_len, pf, keep, false)) return rc;
+      for (int i = p.first; i < p.first + p.rows; ++i) {
+        h->c_forms[(size_t)idx[(size_t)i]] = MV_FORM_SAFE;
+        (h->c_pend_force[(size_t)idx[(size_t)i]] ? h->routed_seqs : h->guard_rescored) += 1;
       }
     }
   }
@@ -1354,8 +1400,6 @@ void split_plan(Plan& pl, int B, const int32_t* lens, const uint8_t* flags, std:
   }
 }
 
-void gather(const Plan& pl, const int32_t* ids, const int32_t* lens, int S, int32_t* ids_out, int32_t* lens_out);
-
 // The resident corpus: h->c_route = the flag of every row under the current list, recomputed when an upload or a list change made it stale — one kernel over
 // the whole corpus, one copy back, one wait (workspace set 0's stream; nothing on the device reads what it writes).  An empty list flags nothing, without a launch.
 int ensure_route_flags(mv_handle* h) {
@@ -1378,9 +1422,9 @@ int ensure_route_flags(mv_handle* h) {
   return MV_OK;
 }
 
-// One batch of a guarded sweep that has routed rows (pass p of the sweep's plan, whose row 0 is corpus row j.c_row): its unrouted rows gathered by index list
-// into wk's pass buffer at the sweep's width — the path of rescore_corpus, in the default form with the per-row monitor attached — and their results, P(same)
-// rows and monitor counts scattered back to their corpus slots.  Asynchronous, like the in-place batches next to it.
+// One batch of a guarded sweep that has routed rows (pass p of the sweep's plan, whose row 0 is corpus row j.c_row): its unrouted rows through run_corpus_rows
+// at the sweep's width, in the default form with the per-row monitor counts kept.  Asynchronous, like the in-place batches next to it: the index list lives in
+// c_idx_live until rescore_corpus has waited for the sweep.
 int run_split_batch(mv_handle* h, Work& wk, const Pass& p, const Job& j) {
   std::vector<int32_t> idx;
   int m = INT32_MAX;
@@ -1393,85 +1437,11 @@ int run_split_batch(mv_handle* h, Work& wk, const Pass& p, const Job& j) {
   if (idx.empty()) return MV_OK;  // every row routed: nothing runs in the default form
   h->c_idx_live.push_back(std::move(idx));
   const std::vector<int32_t>& ix = h->c_idx_live.back();
-  const int n = (int)ix.size(), w = p.width, G = h->n_anchors;
-  const bool keep = j.keep_psame;
-  auto run = [&]() -> int {
-    HIPCHK(h, hipMemcpyAsync(wk.d_idx, ix.data(), (size_t)n * 4, hipMemcpyHostToDevice, wk.stream));
-    const int64_t nt = (int64_t)n * w;
-    hipLaunchKernelGGL(corpus_gather_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, wk.stream, (const int32_t*)h->c_ids, (const int32_t*)h->c_lens,
-                       h->c_S, (const int32_t*)wk.d_idx, n, w, wk.d_ids, wk.d_lens);
-    if (int rc = launch_check(h, "corpus_gather")) return rc;
-    PassForm pf;
-    pf.safe = false; pf.monitor = true; pf.seq_over = wk.seq_over;
-    HIPCHK(h, hipMemsetAsync(pf.seq_over, 0, (size_t)n * 4, wk.stream));
-    if (int rc = encode_dev(h, wk, wk.d_ids, wk.d_lens, m, n, w, -1, wk.u, pf, false, w)) return rc;
-    if (int rc = match_dev(h, wk, wk.u, n, nullptr, nullptr, keep ? wk.psame : nullptr, 1, wk.best, wk.best_idx)) return rc;
-    const int64_t ns = (int64_t)n * (keep ? G : 1);
-    hipLaunchKernelGGL(corpus_scatter_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, wk.stream, (const float*)wk.best, (const int32_t*)wk.best_idx,
-                       keep ? (const float*)wk.psame : (const float*)nullptr, (const int32_t*)wk.d_idx, n, G, h->c_best, h->c_idx, h->c_psame,
-                       (const uint32_t*)wk.seq_over, h->c_over);
-    return launch_check(h, "corpus_scatter");
-  };
-  const int rc = run();
-  if (rc != MV_OK) hipStreamSynchronize(wk.stream);
-  return rc;
+  return run_corpus_rows(h, wk, ix.data(), (int)ix.size(), p.width, m, PassForm(), j.keep_psame, true);
 }
 
-// run_in_order with routed rows among them: the batch staged in the split plan's order (as the by-length entry points stage theirs), the unrouted rows of every
-// pass in the default form, the routed rows through rescore_rows, the results back in the caller's order (and, mv_anchor_append, into the bank in one copy).
-int run_in_order_routed(mv_handle* h, const int32_t* lens, int B, int S, const Job& j) {
-  Plan& pl = h->plan;
-  Work& wk = h->work[0];
-  split_plan(pl, B, lens, h->route_flags.data(), h->routed, h->plan1);
-  auto& v = h->stage;
-  const size_t g2 = (size_t)h->n_anchors * 2, P = (size_t)h->P;
-  v.ids.resize((size_t)pl.tokens);
-  v.lens.resize((size_t)B);
-  v.over.resize((size_t)B);
-  gather(pl, j.ids, lens, S, v.ids.data(), v.lens.data());
-  Job s = j;
-  s.ids = v.ids.data(); s.lens = v.lens.data(); s.u_dev = nullptr; s.routed = h->routed.data();
-  s.out = Stage{};
-  s.out.over = v.over.data();
-  if (j.out.logits) { v.logits.resize((size_t)B * g2); s.out.logits = v.logits.data(); }
-  if (j.out.probs) { v.probs.resize((size_t)B * g2); s.out.probs = v.probs.data(); }
-  if (j.out.best) { v.best.resize((size_t)B * 2); s.out.best = v.best.data(); }
-  if (j.out.idx) { v.idx.resize((size_t)B); s.out.idx = v.idx.data(); }
-  if (j.out.embed || j.u_dev) { v.embed.resize((size_t)B * P); s.out.embed = v.embed.data(); }
-  if (!h->plan1.passes.empty())
-    if (int rc = run_passes(h, wk, h->plan1, 0, h->plan1.passes.size(), s)) return rc;
-  HIPCHK(h, hipStreamSynchronize(wk.stream));
-  if (int rc = rescore_rows(h, wk, pl, s, B)) return rc;
-  std::vector<float>& bank = h->stage2.embed;  // (rescore_rows is done with it)
-  if (j.u_dev) bank.resize((size_t)B * P);
-  for (size_t i = 0; i < (size_t)B; ++i) {
-    const size_t o = (size_t)pl.order[i];
-    if (j.out.logits) std::memcpy(j.out.logits + o * g2, s.out.logits + i * g2, g2 * 4);
-    if (j.out.probs) std::memcpy(j.out.probs + o * g2, s.out.probs + i * g2, g2 * 4);
-    if (j.out.best) { j.out.best[o * 2] = s.out.best[i * 2]; j.out.best[o * 2 + 1] = s.out.best[i * 2 + 1]; }
-    if (j.out.idx) j.out.idx[o] = s.out.idx[i];
-    if (j.out.embed) std::memcpy(j.out.embed + o * P, s.out.embed + i * P, P * 4);
-    if (j.u_dev) std::memcpy(bank.data() + o * P, s.out.embed + i * P, P * 4);
-  }
-  if (j.u_dev) {
-    HIPCHK(h, hipMemcpyAsync(j.u_dev, bank.data(), (size_t)B * P * 4, hipMemcpyHostToDevice, wk.stream));
-    HIPCHK(h, hipStreamSynchronize(wk.stream));
-  }
-  return MV_OK;
-}
-
-// mv_forward / mv_encode / mv_anchor_append / mv_debug_encode: the rows in their own order, the pass loop on workspace set 0, then wait (and, in the guarded
-// form, rescore the flagged rows).
-int run_in_order(mv_handle* h, const int32_t* lens, int B, int S, Job& j) {
-  if (j.guard) { h->stage.over.resize((size_t)B); j.out.over = h->stage.over.data(); }
-  if (int rc = plan_batch(h, lens, B, S, 0, false, 0, h->plan)) return rc;
-  if (scan_routed(h, j, j.ids, lens, B, S)) return run_in_order_routed(h, lens, B, S, j);
-  if (int rc = run_passes(h, h->work[0], h->plan, 0, h->plan.passes.size(), j)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->work[0].stream));
-  return j.full ? MV_OK : rescore_rows(h, h->work[0], h->plan, j, B);
-}
-
-// The rows of a by-length batch gathered into plan order: each pass's ids at its own width (ids [B][S]).
+// ---- the one host batch flow --------------------------------------------------------------------------------------------------------------------------------------
+// The rows of a batch gathered into plan order: each pass's ids at its own width (ids [B][S]).
 void gather(const Plan& pl, const int32_t* ids, const int32_t* lens, int S, int32_t* ids_out, int32_t* lens_out) {
   for (const Pass& p : pl.passes)
     for (int i = 0; i < p.rows; ++i) {
@@ -1481,17 +1451,60 @@ void gather(const Plan& pl, const int32_t* ids, const int32_t* lens, int S, int3
     }
 }
 
-// Row i of the plan order (st) to row order[i] of the caller's arrays: the outputs st holds.
-void scatter(const mv_handle* h, const std::vector<int>& order, int G, const Stage& st, float* logits, float* probs, float* best, int32_t* best_idx, float* embed) {
-  const size_t g2 = (size_t)G * 2, P = (size_t)h->P;
-  for (size_t i = 0; i < order.size(); ++i) {
-    const size_t o = (size_t)order[i];
-    if (st.logits) std::memcpy(logits + o * g2, st.logits + i * g2, g2 * 4);
-    if (st.probs) std::memcpy(probs + o * g2, st.probs + i * g2, g2 * 4);
-    best[o * 2] = st.best[i * 2]; best[o * 2 + 1] = st.best[i * 2 + 1];
-    best_idx[o] = st.idx[i];
-    if (st.embed) std::memcpy(embed + o * P, st.embed + i * P, P * 4);
+// Make and enqueue: rows [0, B) of ids [B][S] planned into pl (plan_batch), the rows the sink-token list routes split off (scan_routed, split_plan: `routed`,
+// which j then points into), the batch gathered in plan order into a view of the staging — hs, or wk's pinned one — that holds the results `want` names, and the
+// passes of the unrouted rows enqueued on wk.  Does not wait.  j comes in made (match, form, anchor count) and leaves with the staging as its ids, lens and out.
+// A batch in its own order with no routed row is not staged: its ids are read in place and j.out stays the caller's arrays (the plan's order is empty).
+int enqueue_batch(mv_handle* h, Work& wk, Plan& pl, std::vector<uint8_t>& routed, HostStage* hs, const int32_t* ids, const int32_t* lens, int B, int S,
+                  int min_tokens, bool by_length, Want want, Job& j) {
+  if (int rc = plan_batch(h, lens, B, S, min_tokens, by_length, 0, pl)) return rc;
+  const Plan* p1 = &pl;  // the passes of the first run: without the routed rows
+  routed.clear();
+  j.routed = nullptr;
+  if (scan_routed(h, j, ids, lens, B, S)) {
+    split_plan(pl, B, lens, h->route_flags.data(), routed, h->plan1);
+    j.routed = routed.data();
+    p1 = &h->plan1;
   }
+  const bool in_place = pl.order.empty();
+  if (in_place) want = Want();  // (only the monitor counts go through the staging)
+  want.over = j.guard;
+  const Stage st = hs ? hs->view((size_t)B, in_place ? 0 : (size_t)pl.tokens, (size_t)j.G, (size_t)h->P, want) : only(wk.pin, want);
+  if (in_place) {
+    j.ids = ids; j.lens = lens; j.out.over = st.over;
+  } else {
+    gather(pl, ids, lens, S, st.ids, st.lens);
+    j.ids = st.ids; j.lens = st.lens; j.out = st; j.u_dev = nullptr;
+  }
+  return p1->passes.empty() ? MV_OK : run_passes(h, wk, *p1, 0, p1->passes.size(), j);
+}
+
+// Collect: wait for wk, rescore the flagged and the routed rows of a guarded job (rescore_rows), and bring a staged batch's results to the caller's rows (dst).
+int collect_batch(mv_handle* h, Work& wk, const Plan& pl, const Job& j, int B, const Stage& dst) {
+  HIPCHK(h, hipStreamSynchronize(wk.stream));
+  if (!j.full)  // (mv_debug_encode: the taps show the passes as they ran)
+    if (int rc = rescore_rows(h, wk, pl, j, B)) return rc;
+  if (!pl.order.empty()) scatter_rows(j.out, dst, pl.order, (size_t)B, (size_t)j.G, (size_t)h->P);
+  return MV_OK;
+}
+
+// mv_forward / mv_encode / mv_anchor_append / mv_debug_encode: the rows in their own order on workspace set 0, both halves back to back.  mv_anchor_append with
+// routed rows (the batch was staged): the bank's rows in the caller's order, in one copy.
+int run_in_order(mv_handle* h, const int32_t* lens, int B, int S, const Job& j) {
+  Work& wk = h->work[0];
+  const size_t P = (size_t)h->P;
+  Job s = j;
+  if (int rc = enqueue_batch(h, wk, h->plan, h->routed, &h->stage, j.ids, lens, B, S, 0, false, wanted(j.out, j.out.embed || j.u_dev), s)) return rc;
+  if (int rc = collect_batch(h, wk, h->plan, s, B, j.out)) return rc;
+  if (j.u_dev && !h->plan.order.empty()) {
+    Want e;
+    e.embed = true;
+    const Stage bank = h->stage2.view((size_t)B, 0, 0, P, e);  // (rescore_rows is done with it)
+    scatter_rows(s.out, bank, h->plan.order, (size_t)B, 0, P);
+    HIPCHK(h, hipMemcpyAsync(j.u_dev, bank.embed, (size_t)B * P * 4, hipMemcpyHostToDevice, wk.stream));
+    HIPCHK(h, hipStreamSynchronize(wk.stream));
+  }
+  return MV_OK;
 }
 
 }  // namespace
@@ -2007,52 +2020,30 @@ int mv_forward(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int
 } catch (...) { return on_exception(h); }
 
 // ---- by length: mv_forward on a pad-to-longest batch of UNSORTED rows (binding.Engine.forward_by_length) ----------------------------------------------------------
-// plan_batch orders and groups the rows, gather stages them in that order (each pass at its own width), run_passes runs the passes back to back on one stream,
-// scatter puts the results back in the caller's row order.
-// The whole flow in ONE call on workspace set 0: one release of the caller's interpreter lock per batch (next to two other Python threads every release cost the
-// scoring thread ~10 ms of waiting: profiles/r06_*_e2e_dropin.txt).
+// enqueue_batch plans the rows by length, stages them in that order (each pass at its own width) and runs the passes back to back on one stream; collect_batch
+// waits, rescores and puts the results back in the caller's row order.
+// The whole flow in ONE call on workspace set 0 with the pageable staging: one release of the caller's interpreter lock per batch (next to two other Python
+// threads every release cost the scoring thread ~10 ms of waiting: profiles/r06_*_e2e_dropin.txt).
 int mv_forward_ragged(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int min_tokens, float* logits, float* probs, float* best,
                       int32_t* best_idx, float* embed) try {
   if (int rc = check_ready(h)) return rc;
   if (!ids || !lens || B <= 0 || S <= 0 || S > h->cfg.max_pos || !best || !best_idx) return fail(h, MV_ERR_INVALID, "mv_forward_ragged: bad argument");
   if (h->n_anchors <= 0) return fail(h, MV_ERR_STATE, "anchor bank is empty (call mv_anchor_append / mv_anchor_set first)");
-  Plan& pl = h->plan;
-  if (int rc = plan_batch(h, lens, B, S, min_tokens, true, 0, pl)) return rc;
   if (int rc = check_ids(h, ids, (int64_t)B * S, "mv_forward_ragged")) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const int G = h->n_anchors;
-  auto& v = h->stage;
-  v.ids.resize((size_t)pl.tokens);
-  v.lens.resize(B);
-  if (logits) v.logits.resize((size_t)B * G * 2);
-  if (probs) v.probs.resize((size_t)B * G * 2);
-  v.best.resize((size_t)B * 2);
-  v.idx.resize(B);
-  if (embed) v.embed.resize((size_t)B * h->P);
+  Work& wk = h->work[0];
+  const Stage dst{nullptr, nullptr, best_idx, logits, probs, best, embed};
   Job j;
+  j.match = true;
   job_form(h, j);
-  const Plan* p1 = &pl;  // the passes of the first run: without the rows the sink-token list routes
-  if (scan_routed(h, j, ids, lens, B, S)) {
-    split_plan(pl, B, lens, h->route_flags.data(), h->routed, h->plan1);
-    j.routed = h->routed.data();
-    p1 = &h->plan1;
-  }
-  gather(pl, ids, lens, S, v.ids.data(), v.lens.data());
-  j.ids = v.ids.data(); j.lens = v.lens.data(); j.match = true;
-  j.out = Stage{nullptr, nullptr, v.idx.data(), logits ? v.logits.data() : nullptr, probs ? v.probs.data() : nullptr, v.best.data(), embed ? v.embed.data() : nullptr};
-  if (j.guard) { v.over.resize(B); j.out.over = v.over.data(); }
-  if (!p1->passes.empty())
-    if (int rc = run_passes(h, h->work[0], *p1, 0, p1->passes.size(), j)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->work[0].stream));
-  if (int rc = rescore_rows(h, h->work[0], pl, j, B)) return rc;
-  scatter(h, pl.order, G, j.out, logits, probs, best, best_idx, embed);
-  return MV_OK;
+  if (int rc = enqueue_batch(h, wk, h->plan, h->routed, &h->stage, ids, lens, B, S, min_tokens, true, wanted(dst, embed != nullptr), j)) return rc;
+  return collect_batch(h, wk, h->plan, j, B, dst);
 } catch (...) { return on_exception(h); }
 
-// mv_forward_ragged in two halves, so that the caller can hand over batch k + 1 BEFORE it collects batch k: `begin` enqueues the batch on a workspace set without
-// a ticket, into that set's pinned staging, and returns a ticket (the set) without waiting; `end` waits for that set's stream and scatters the results.  At most
-// one batch per workspace set (MEMVUL_STREAMS: 2) is in flight; tickets are collected in the order they were issued.  The GPU then never waits for the caller's
-// Python between two batches (predict_memory.evaluate).
+// mv_forward_ragged in two halves, so that the caller can hand over batch k + 1 BEFORE it collects batch k: `begin` is enqueue_batch on a workspace set without
+// a ticket, into that set's pinned staging, and returns a ticket (the set) without waiting; `end` is collect_batch on that set with the job the ticket was begun
+// with — its form, its routing and its anchor count.  At most one batch per workspace set (MEMVUL_STREAMS: 2) is in flight; tickets are collected in the order
+// they were issued.  The GPU then never waits for the caller's Python between two batches (predict_memory.evaluate).
 int mv_forward_ragged_begin(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int min_tokens, int want_logits, int want_probs, int want_embed,
                             int* ticket) try {
   if (int rc = check_ready(h)) return rc;
@@ -2063,7 +2054,6 @@ int mv_forward_ragged_begin(mv_handle* h, const int32_t* ids, const int32_t* len
   while (set < h->n_alloc && h->work[set].ticket) ++set;
   if (set == h->n_alloc) return fail(h, MV_ERR_CAPACITY, "mv_forward_ragged_begin: every workspace set has a batch in flight (score this one with mv_forward_ragged)");
   Work& wk = h->work[set];
-  if (int rc = plan_batch(h, lens, B, S, min_tokens, true, 0, wk.plan)) return rc;
   if (int rc = check_ids(h, ids, (int64_t)B * S, "mv_forward_ragged_begin")) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   if (!wk.pin.best) {  // pinned staging of this set, once: [max_batch][max_pos], [max_batch] x 2, [max_batch][max_anchors][2] x 2, [max_batch][2], [max_batch][P]
@@ -2085,24 +2075,12 @@ int mv_forward_ragged_begin(mv_handle* h, const int32_t* ids, const int32_t* len
     if (rc) return rc;
     wk.pin = s;
   }
-  Stage st = wk.pin;
-  if (!want_logits) st.logits = nullptr;
-  if (!want_probs) st.probs = nullptr;
-  if (!want_embed) st.embed = nullptr;
-  Job j;
-  job_form(h, j);  // (the form in force HERE is the ticket's: mv_forward_ragged_end rescores a guarded one — and the sink-token list in force here its routing)
-  const Plan* p1 = &wk.plan;
-  wk.routed.clear();
-  if (scan_routed(h, j, ids, lens, B, S)) {
-    split_plan(wk.plan, B, lens, h->route_flags.data(), wk.routed, h->plan1);
-    p1 = &h->plan1;
-  }
-  gather(wk.plan, ids, lens, S, st.ids, st.lens);
-  if (!j.guard) st.over = nullptr;
-  j.ids = st.ids; j.lens = st.lens; j.match = true; j.out = st;
-  if (!p1->passes.empty())
-    if (int rc = run_passes(h, wk, *p1, 0, p1->passes.size(), j)) return rc;
-  wk.ticket = true; wk.G = h->n_anchors; wk.st = st; wk.guard = j.guard; wk.safe = j.safe;
+  wk.job = Job();
+  wk.job.match = true;
+  job_form(h, wk.job);  // (the form, the sink-token list and the bank in force HERE are the ticket's)
+  if (int rc = enqueue_batch(h, wk, wk.plan, wk.routed, nullptr, ids, lens, B, S, min_tokens, true, Want{want_logits != 0, want_probs != 0, true, true, want_embed != 0},
+                             wk.job)) return rc;
+  wk.ticket = true;
   *ticket = set;
   return MV_OK;
 } catch (...) { return on_exception(h); }
@@ -2111,24 +2089,13 @@ int mv_forward_ragged_end(mv_handle* h, int ticket, float* logits, float* probs,
   if (!h || ticket < 0 || ticket > 1 || !h->work[ticket].ticket) return fail(h, MV_ERR_STATE, "mv_forward_ragged_end: no batch in flight under this ticket");
   Work& wk = h->work[ticket];
   HIPCHK(h, hipSetDevice(h->device));
-  const hipError_t e = hipStreamSynchronize(wk.stream);
   wk.ticket = false;
-  if (e != hipSuccess) return fail(h, MV_ERR_HIP, std::string("mv_forward_ragged_end: ") + hipGetErrorString(e));
-  if (!best || !best_idx || (wk.st.logits && !logits) || (wk.st.probs && !probs) || (wk.st.embed && !embed))
+  const Stage& st = wk.job.out;  // (the batch's ids are still in the pinned staging; the bank rows it was matched against are the first wk.job.G of what the bank holds now)
+  if (!best || !best_idx || (st.logits && !logits) || (st.probs && !probs) || (st.embed && !embed)) {
+    hipStreamSynchronize(wk.stream);  // (the set is free again only once its batch has left the pinned staging alone)
     return fail(h, MV_ERR_INVALID, "mv_forward_ragged_end: an output the batch was started with is missing");
-  {
-    // the batch's ids are still in the pinned staging; the bank rows the batch was matched against are the first wk.G of whatever the bank holds now
-    Job j;
-    j.ids = wk.st.ids; j.lens = wk.st.lens; j.match = true; j.out = wk.st; j.guard = wk.guard; j.safe = wk.safe;
-    j.routed = wk.routed.empty() ? nullptr : wk.routed.data();
-    const int G_now = h->n_anchors;
-    h->n_anchors = wk.G;
-    const int rc = rescore_rows(h, wk, wk.plan, j, (int)wk.plan.order.size());
-    h->n_anchors = G_now;
-    if (rc) return rc;
   }
-  scatter(h, wk.plan.order, wk.G, wk.st, logits, probs, best, best_idx, embed);
-  return MV_OK;
+  return collect_batch(h, wk, wk.plan, wk.job, (int)wk.plan.order.size(), Stage{nullptr, nullptr, best_idx, logits, probs, best, embed});
 } catch (...) { return on_exception(h); }
 
 int mv_match(mv_handle* h, const float* u, int B, float* logits, float* probs, float* best, int32_t* best_idx) try {
@@ -2139,7 +2106,7 @@ int mv_match(mv_handle* h, const float* u, int B, float* logits, float* probs, f
   Work& wk = h->work[0];
   const int G = h->n_anchors;
   HIPCHK(h, hipMemcpyAsync(wk.u_in, u, (size_t)B * h->P * 4, hipMemcpyHostToDevice, wk.stream));
-  if (int rc = match_dev(h, wk, wk.u_in, B, logits ? wk.logits : nullptr, probs ? wk.probs : nullptr, nullptr, 1, wk.best,
+  if (int rc = match_dev(h, wk, wk.u_in, B, G, logits ? wk.logits : nullptr, probs ? wk.probs : nullptr, nullptr, 1, wk.best,
                          wk.best_idx)) return rc;
   const size_t bg = (size_t)B * G;
   if (logits) HIPCHK(h, hipMemcpyAsync(logits, wk.logits, bg * 8, hipMemcpyDeviceToHost, wk.stream));
@@ -2159,7 +2126,7 @@ int mv_topk(mv_handle* h, const float* u, int B, int k, float* topk_p, int32_t* 
   Work& wk = h->work[0];
   HIPCHK(h, hipMemcpyAsync(wk.u_in, u, (size_t)B * h->P * 4, hipMemcpyHostToDevice, wk.stream));
   // one fused pass: P(same) [B, G] never reaches HBM, only 8 B k bytes of results do
-  if (int rc = match_dev(h, wk, wk.u_in, B, nullptr, nullptr, nullptr, k, nullptr, nullptr, wk.topk_p, wk.topk_idx)) return rc;
+  if (int rc = match_dev(h, wk, wk.u_in, B, h->n_anchors, nullptr, nullptr, nullptr, k, nullptr, nullptr, wk.topk_p, wk.topk_idx)) return rc;
   HIPCHK(h, hipMemcpyAsync(topk_p, wk.topk_p, (size_t)B * k * 4, hipMemcpyDeviceToHost, wk.stream));
   HIPCHK(h, hipMemcpyAsync(topk_idx, wk.topk_idx, (size_t)B * k * 4, hipMemcpyDeviceToHost, wk.stream));
   HIPCHK(h, hipStreamSynchronize(wk.stream));
