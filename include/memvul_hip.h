@@ -270,6 +270,36 @@ int mv_corpus_run_len(mv_handle* h, int64_t first, int64_t count, int batch, int
 int mv_set_streams(mv_handle* h, int n);
 /* best fp32 [count,2], best_idx int32 [count], p_same fp32 [count,G] (NULL unless kept). Synchronises. */
 int mv_corpus_results(mv_handle* h, int64_t first, int64_t count, float* best, int32_t* best_idx, float* p_same);
+/* ---- the editable memory on a resident corpus.  The CWE anchor bank is the part of the reference model that changes without retraining
+ *      (forward_gold_instances, model_memory.py:105-115, rebuilds it from the golden instances; the matcher of l.135-147 is all that reads it), and the
+ *      encoder — all but tens of microseconds of a batch — does not depend on it.  A corpus that keeps its embeddings is matched again against a changed
+ *      bank without the encoder; one that keeps top-k lists serves BASELINE.json configs[4] ("1000-anchor bank + top-k match") without the
+ *      [N][G] P(same) array ever leaving the device.
+ * mv_corpus_keep: what the sweeps of the CURRENT upload keep besides best / best_idx: keep_embed (0 | 1) the embedding of every row, fp32 [N][proj_dim] —
+ * the encoder writes it there, no copy; topk (0 .. 64) the k anchors with the largest P(same) of every row, order and ties as mv_topk.  Call it after
+ * mv_corpus_upload and before the first mv_corpus_run* of that upload (later: MV_ERR_STATE; no corpus: MV_ERR_STATE; a value out of range: MV_ERR_INVALID);
+ * an upload resets it to (0, 0) and frees the arrays.  With (0, 0), the default, nothing is allocated and every other entry point is what it is without this
+ * one: same results, same launches, same allocations.  The arrays are allocated at the first run (MV_ERR_NOMEM with the size in the message when that fails);
+ * a run with topk larger than the bank, or anchors / 256 * topk > 1024, returns MV_ERR_INVALID.  In the guarded form a row that was encoded again in the
+ * safe form, or routed there, keeps the safe form's embedding and top-k list, like its best anchor.  The library remembers which rows a keeping run covered.
+ * mv_corpus_rematch: the matcher alone (model_memory.py:135-147) over the kept embeddings of rows [first, first + count) against the bank AS IT IS NOW: it
+ * first collects what mv_corpus_results would (the sweeps in flight, the guarded form's rescoring), launches no encoder kernel, and waits before it returns.
+ *   g_first == 0 (full): best, best_idx and the top-k lists of the rows are rewritten; with keep_probs also their P(same) rows (the array is reallocated at
+ *     the present anchor count exactly as mv_corpus_run_len does, and only then does the pitch mv_corpus_results copies with change).  Byte-equal to
+ *     running the same mv_corpus_run* calls again.
+ *   0 < g_first < anchors (appended): THE CALLER STATES that the stored results of the rows were computed against a bank whose first g_first rows are the
+ *     present ones (anchors were appended since, nothing else changed).  Only anchors [g_first, G) are matched and a merge kernel folds them into the stored
+ *     best anchor and top-k lists, in the matcher's order — largest P(same) first, a tie to the lower anchor index, NaN above everything: byte-equal to the
+ *     full mode.  keep_probs != 0 here: MV_ERR_INVALID.
+ *   g_first == anchors: nothing was appended, MV_OK.  g_first outside [0, anchors]: MV_ERR_INVALID.
+ * No embeddings kept, a row of the range that no keeping run covered, or an empty bank: MV_ERR_STATE; a kept top-k larger than the bank: MV_ERR_INVALID.
+ * mv_corpus_embeddings: embed fp32 [count][proj_dim], what mv_encode returns for the rows at the width they were swept at (model_memory.py:90-103).
+ * mv_corpus_topk: topk_p fp32 [count][k], topk_idx int32 [count][k] with the k of mv_corpus_keep (BASELINE.json configs[4]).  Both collect like
+ * mv_corpus_results and return MV_ERR_STATE for a range with a row no keeping run covered, or when the corpus does not keep what they read. */
+int mv_corpus_keep(mv_handle* h, int keep_embed, int topk);
+int mv_corpus_rematch(mv_handle* h, int64_t first, int64_t count, int g_first, int keep_probs);
+int mv_corpus_embeddings(mv_handle* h, int64_t first, int64_t count, float* embed);                 /* [count][proj_dim] fp32 */
+int mv_corpus_topk(mv_handle* h, int64_t first, int64_t count, float* topk_p, int32_t* topk_idx);   /* [count][k] */
 /* MV_F16X8 only (always 0 in MV_F16).  The fp8 planes of the activations (raw residual stream, attention context, GELU output) use ONE
  * static scale: |x| <= 112 is representable; an element beyond it keeps its fp16 accuracy but loses its correction term (the precision of
  * MV_F16 for that element) — the computation never fails over it.  *clamped = the number of such elements since the handle was created

@@ -127,7 +127,7 @@ ABI_SYMBOLS = [
     "mv_create", "mv_destroy", "mv_last_error", "mv_sync", "mv_load_tensor", "mv_finalize_weights",
     "mv_anchor_reset", "mv_anchor_append", "mv_anchor_count", "mv_anchor_get", "mv_anchor_set",
     "mv_forward", "mv_forward_ragged", "mv_forward_ragged_begin", "mv_forward_ragged_end", "mv_encode", "mv_match", "mv_topk", "mv_corpus_upload", "mv_corpus_run", "mv_corpus_run_len",
-    "mv_corpus_results", "mv_x8_saturation", "mv_attention_concentration", "mv_sink_census_enable", "mv_sink_census_read", "mv_set_form", "mv_get_form", "mv_form_stats", "mv_last_row_forms", "mv_corpus_row_forms",
+    "mv_corpus_results", "mv_corpus_keep", "mv_corpus_rematch", "mv_corpus_embeddings", "mv_corpus_topk", "mv_x8_saturation", "mv_attention_concentration", "mv_sink_census_enable", "mv_sink_census_read", "mv_set_form", "mv_get_form", "mv_form_stats", "mv_last_row_forms", "mv_corpus_row_forms",
     "mv_set_sink_tokens", "mv_get_sink_tokens", "mv_route_stats", "mv_route_scan", "mv_corpus_route_flags", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
     "mv_debug_encode", "mv_debug_read", "mv_test_gemm", "mv_test_gemm_pp", "mv_test_gemm_f32", "mv_test_e4m3", "mv_format_records", "mv_comm_prepare", "mv_comm_unique_id", "mv_comm_init", "mv_comm_allgather",
     "mv_comm_destroy", "mv_comm_info", "mv_device_count",
@@ -188,6 +188,10 @@ def load_library(path: Optional[str] = None, dev: bool = False):
         "mv_corpus_run": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int]),
         "mv_corpus_run_len": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int]),
         "mv_corpus_results": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, vp]),
+        "mv_corpus_keep": (C.c_int, [vp, C.c_int, C.c_int]),
+        "mv_corpus_rematch": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int]),
+        "mv_corpus_embeddings": (C.c_int, [vp, C.c_int64, C.c_int64, vp]),
+        "mv_corpus_topk": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp]),
         "mv_x8_saturation": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int]),
         "mv_attention_concentration": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
         "mv_sink_census_enable": (C.c_int, [vp, C.c_int]),
@@ -289,6 +293,8 @@ class Engine:
         self._guard_warned = False   # the guarded form's one warning (more than GUARDED_WARN_SHARE of the sequences rescored)
         self._last_rows = 0          # rows of the last call last_row_forms() speaks of
         self._census = False         # the sink census is on (sink_census_enable / MEMVUL_SINK_CENSUS=1)
+        self._bank_epoch = 0         # bumped by whatever rewrites anchors the bank already holds (anchor_reset, anchor_set, the MEMVUL_ON_SINK=safe switch), not by anchor_append
+        self._sweep_kept = None      # the last bucketed_sweep(keep= / topk=): its row order, and the bank (epoch, anchor count) its stored results cover
 
     # -- plumbing
     def _check(self, rc: int, what: str):
@@ -529,6 +535,7 @@ class Engine:
         that form from the ids anchor_append was given (a bank installed with anchor_set is kept: there is nothing to encode it from), one warning."""
         self.set_form("safe")
         self.attention_concentration(reset=True)
+        self._bump_epoch()  # (the bank is encoded again below: results stored against it are stale row for row)
         n_bank = self.n_anchors
         if self._bank_replayable:
             log = self._anchor_log
@@ -551,9 +558,13 @@ class Engine:
     def _anchor_append(self, ids: np.ndarray, lens: np.ndarray):
         self._check(self._lib.mv_anchor_append(self._h, _ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1]), "mv_anchor_append")
 
+    def _bump_epoch(self):
+        self._bank_epoch = getattr(self, "_bank_epoch", 0) + 1
+
     def anchor_reset(self):
         self._anchor_reset()
         self._anchor_log, self._bank_replayable = [], True
+        self._bump_epoch()
 
     def anchor_append(self, ids: np.ndarray, lens: np.ndarray):
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
@@ -581,6 +592,7 @@ class Engine:
         self._check_width(v, "anchor_set")
         self._check(self._lib.mv_anchor_set(self._h, _ptr(v), v.shape[0]), "mv_anchor_set")
         self._anchor_log, self._bank_replayable = [], False
+        self._bump_epoch()
 
     # -- hot loop
     def forward(self, ids: np.ndarray, lens: np.ndarray, want_logits=True, want_probs=True, want_embed=False):
@@ -697,6 +709,8 @@ class Engine:
         self._check(self._lib.mv_corpus_upload(self._h, _ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1]), "mv_corpus_upload")
         self._corpus_n = ids.shape[0]
         self._corpus_runs = []
+        self._corpus_k = 0        # (an upload resets mv_corpus_keep)
+        self._sweep_kept = None
 
     def corpus_run(self, first: int, count: int, batch: int, keep_probs: bool = False, s_eff: int = 0):
         """Enqueue IRs [first, first+count) of the resident corpus in batches of `batch` (asynchronous).  s_eff > 0:
@@ -705,15 +719,45 @@ class Engine:
         if self._on_sink == "safe" and self._form == "default":
             self._corpus_runs.append((first, count, batch, keep_probs, s_eff))
 
-    def bucketed_sweep(self, ids: np.ndarray, lens: np.ndarray, batch: int, with_probs: bool = False):
+    def corpus_keep(self, embed: bool = True, topk: int = 0):
+        """What the sweeps of the corpus just uploaded keep besides best / best_idx (mv_corpus_keep; after corpus_upload, before its first corpus_run): the rows'
+        embeddings — what corpus_rematch matches again against a changed anchor bank, without the encoder — and / or their ``topk`` best anchors."""
+        self._check(self._lib.mv_corpus_keep(self._h, int(bool(embed)), int(topk)), "mv_corpus_keep")
+        self._corpus_k = int(topk)
+
+    def corpus_rematch(self, first: int, count: int, g_first: int = 0, keep_probs: bool = False):
+        """The matcher alone over the kept embeddings of rows [first, first + count) against the bank as it is now (mv_corpus_rematch; it waits).  g_first = 0
+        rewrites the stored results; 0 < g_first < n_anchors: the caller states that they were computed against a bank whose first g_first anchors are the
+        present ones, and only the anchors from g_first on are matched and merged in (same bytes).  rematch_sweep chooses g_first by itself."""
+        self._check(self._lib.mv_corpus_rematch(self._h, first, count, int(g_first), int(bool(keep_probs))), "mv_corpus_rematch")
+
+    def corpus_embeddings(self, first: int, count: int) -> np.ndarray:
+        """fp32 [count, P]: the kept embeddings of rows [first, first + count) (mv_corpus_embeddings)."""
+        out = np.empty((count, self.P), np.float32)
+        self._check(self._lib.mv_corpus_embeddings(self._h, first, count, _ptr(out)), "mv_corpus_embeddings")
+        return out
+
+    def corpus_topk(self, first: int, count: int):
+        """(P(same) fp32 [count, k], anchor index int32 [count, k]) of rows [first, first + count), k as given to corpus_keep (mv_corpus_topk)."""
+        k = getattr(self, "_corpus_k", 0)
+        p = np.empty((count, k), np.float32)
+        i = np.empty((count, k), np.int32)
+        self._check(self._lib.mv_corpus_topk(self._h, first, count, _ptr(p), _ptr(i)), "mv_corpus_topk")
+        return p, i
+
+    def bucketed_sweep(self, ids: np.ndarray, lens: np.ndarray, batch: int, with_probs: bool = False, keep: bool = False, topk: int = 0):
         """Score a ragged corpus with each batch padded to ITS longest member (the reference's pad-to-longest collation,
         predict_memory.py:97-101) instead of the corpus-wide S: rows are sorted by length, uploaded once, swept batch by
-        batch at that batch's length (rounded up to 64 tokens), and the results are returned in the ORIGINAL order."""
+        batch at that batch's length (rounded up to 64 tokens), and the results are returned in the ORIGINAL order.
+        keep / topk: the corpus keeps its embeddings / the k best anchors of every row (corpus_keep), and the engine remembers the order of the upload:
+        rematch_sweep() then scores the same rows against a changed bank without encoding them again, sweep_topk() returns the top-k lists."""
         ids = np.ascontiguousarray(ids, np.int32)
         lens = np.ascontiguousarray(lens, np.int32)
         n = ids.shape[0]
         order = np.argsort(lens, kind="stable")
         self.corpus_upload(ids[order], lens[order])
+        if keep or topk:
+            self.corpus_keep(embed=bool(keep), topk=topk)
         sl = lens[order]
         for s0 in range(0, n, batch):
             nb = min(batch, n - s0)
@@ -721,7 +765,32 @@ class Engine:
         best, idx, ps = self.corpus_results(0, n, with_probs=with_probs)
         inv = np.empty(n, np.int64)
         inv[order] = np.arange(n)
+        if keep or topk:  # (after corpus_results: a MEMVUL_ON_SINK=safe trip in there swept again, against the bank it encoded again)
+            self._sweep_kept = {"n": n, "inv": inv, "embed": bool(keep), "epoch": getattr(self, "_bank_epoch", 0), "covered": self.n_anchors}
         return best[inv], idx[inv], (ps[inv] if ps is not None else None)
+
+    def rematch_sweep(self, with_probs: bool = False):
+        """The rows of the last ``bucketed_sweep(..., keep=True)`` against the anchor bank as it is NOW, by the matcher alone: ``(best, idx, p_same | None)`` in
+        the ORIGINAL row order, the bytes sweeping again would give.  When the bank has only been appended to since the stored results were computed (no
+        anchor_reset, anchor_set or switch of form in between) and P(same) is not asked for, only the new anchors are matched and merged in."""
+        st = getattr(self, "_sweep_kept", None)
+        if st is None or not st["embed"]:
+            raise RuntimeError("rematch_sweep: the resident corpus keeps no embeddings — sweep it with bucketed_sweep(..., keep=True) first")
+        G = self.n_anchors
+        appended = st["epoch"] == getattr(self, "_bank_epoch", 0) and G >= st["covered"] and not with_probs
+        self.corpus_rematch(0, st["n"], st["covered"] if appended else 0, keep_probs=with_probs)
+        best, idx, ps = self.corpus_results(0, st["n"], with_probs=with_probs)
+        st["epoch"], st["covered"] = getattr(self, "_bank_epoch", 0), self.n_anchors
+        inv = st["inv"]
+        return best[inv], idx[inv], (ps[inv] if ps is not None else None)
+
+    def sweep_topk(self):
+        """(P(same) [n, k], anchor index [n, k]) of the last ``bucketed_sweep(..., topk=k)``, in the ORIGINAL row order."""
+        st = getattr(self, "_sweep_kept", None)
+        if st is None or not getattr(self, "_corpus_k", 0):
+            raise RuntimeError("sweep_topk: the resident corpus keeps no top-k lists — sweep it with bucketed_sweep(..., topk=k) first")
+        p, i = self.corpus_topk(0, st["n"])
+        return p[st["inv"]], i[st["inv"]]
 
     def corpus_results(self, first: int, count: int, with_probs: bool = False):
         best = np.empty((count, 2), np.float32)

@@ -181,7 +181,8 @@ struct Job {
   int64_t c_row = 0; bool keep_psame = false;    // ... whose row c_row is plan row 0: ids read in place at pitch c_S, results (and P(same)) to its arrays
   Stage out;                                      // host results, plan order (NULL: not asked for; out.ids / out.lens unused)
   bool match = false;                             // + the matcher: the best anchor always, logits / probs where `out` asks for them
-  float* u_dev = nullptr;                         // the encoder's output to the device here (mv_anchor_append: the bank) instead of wk.u
+  float* u_dev = nullptr;                         // the encoder's output to the device here (mv_anchor_append: the bank; a keeping sweep: c_embed) instead of wk.u
+  int topk = 0;                                   // the resident corpus, mv_corpus_keep: the rows' k best anchors to c_topk_p / c_topk_idx as well (0: none)
   int n_layers = -1; bool full = false;           // mv_debug_encode: the layers to run, and the full last layer (encode_dev)
   int G = 0;                                      // the anchors it is matched against: the bank's first G rows (job_form: the count when the job is made)
   bool safe = false;                              // the form of its passes (job_form: from the handle, when the job is made)
@@ -292,6 +293,14 @@ struct mv_handle {
   float* c_psame = nullptr;
   int64_t c_psame_rows = 0;
   int c_G = 0;
+  // what the corpus keeps of a sweep besides the best anchor (mv_corpus_keep: after an upload, before its first run; allocated at that run): the embeddings, so
+  // that mv_corpus_rematch can match them again against a changed bank without the encoder, and the k best anchors of every row
+  int c_keep_embed = 0, c_k = 0;
+  bool c_ran = false;                   // a run since the upload: mv_corpus_keep comes too late
+  float* c_embed = nullptr;             // [c_n][P]
+  float* c_topk_p = nullptr;            // [c_n][c_k]
+  int32_t* c_topk_idx = nullptr;
+  std::vector<uint8_t> c_has;           // [c_n] a keeping run covered the row (empty while nothing is kept)
   // the guarded form on the resident corpus: the sweep records the per-row monitor counts and which rows it ran at which width; rescore_corpus (mv_corpus_results)
   // encodes the flagged ones again
   uint32_t* c_over = nullptr;           // [c_n] AttnArgs::seq_over of the row's last guarded run
@@ -939,10 +948,11 @@ int max_rows_for(mv_handle* h, int S_in) {
 }
 
 // K9 + K10 fused (match_topk.h): logits / probs / psame_out are optional full outputs; k >= 1 selects the best anchor
-// (and, with topk_p / topk_idx, the k best).  4 issue reports per workgroup when that already fills the chip, else 1
+// (and, with topk_p / topk_idx, the k best).  g_first: against anchors [g_first, g_first + G) of the bank instead of its first G.  4 issue reports per workgroup when that already fills the chip, else 1
 // (the same bits either way).
 int match_dev(mv_handle* h, Work& wk, const float* u_dev, int B, int G, float* logits, float* probs, float* psame_out, int k, float* best_out,
-              int32_t* idx_out, float* topk_p = nullptr, int32_t* topk_idx = nullptr) {
+              int32_t* idx_out, float* topk_p = nullptr, int32_t* topk_idx = nullptr, int g_first = 0) {
+  const float* anchors = h->anchors + (size_t)g_first * h->P;  // mv_corpus_rematch, appended mode: the G anchors from g_first on (indices relative to it)
   if (G <= 0) return fail(h, MV_ERR_STATE, "anchor bank is empty (call mv_anchor_append / mv_anchor_set first)");
   MatchArgs a{};
   a.B = B; a.G = G; a.same_idx = h->cfg.same_idx; a.k = k;
@@ -957,10 +967,10 @@ int match_dev(mv_handle* h, Work& wk, const float* u_dev, int B, int G, float* l
     ProfScope ps(h, wk.stream, KC_MATCH);
     const dim3 grid(small ? 1 : a.nchunk, (B + 3) / 4);
 #define MV_MATCH(PD)                                                                                                                          \
-    if (small && a.logits) hipLaunchKernelGGL((match_topk_kernel<2, 128, 64, 1, 2, PD>), grid, dim3(256), 0, wk.stream, u_dev, h->anchors, h->Wm, a); \
-    else if (small) hipLaunchKernelGGL((match_topk_kernel<2, 128, 64, 0, 2, PD>), grid, dim3(256), 0, wk.stream, u_dev, h->anchors, h->Wm, a);        \
-    else if (a.logits) hipLaunchKernelGGL((match_topk_kernel<2, 256, 32, 1, 2, PD>), grid, dim3(512), 0, wk.stream, u_dev, h->anchors, h->Wm, a);     \
-    else hipLaunchKernelGGL((match_topk_kernel<2, 256, 32, 0, 2, PD>), grid, dim3(512), 0, wk.stream, u_dev, h->anchors, h->Wm, a)
+    if (small && a.logits) hipLaunchKernelGGL((match_topk_kernel<2, 128, 64, 1, 2, PD>), grid, dim3(256), 0, wk.stream, u_dev, anchors, h->Wm, a); \
+    else if (small) hipLaunchKernelGGL((match_topk_kernel<2, 128, 64, 0, 2, PD>), grid, dim3(256), 0, wk.stream, u_dev, anchors, h->Wm, a);        \
+    else if (a.logits) hipLaunchKernelGGL((match_topk_kernel<2, 256, 32, 1, 2, PD>), grid, dim3(512), 0, wk.stream, u_dev, anchors, h->Wm, a);     \
+    else hipLaunchKernelGGL((match_topk_kernel<2, 256, 32, 0, 2, PD>), grid, dim3(512), 0, wk.stream, u_dev, anchors, h->Wm, a)
     if (h->P == MV_PROJ) { MV_MATCH(MV_PROJ); } else { MV_MATCH(MV_HIDDEN); }
 #undef MV_MATCH
     if (int rc = launch_check(h, "match_topk")) return rc;
@@ -1210,7 +1220,8 @@ int run_passes(mv_handle* h, Work& wk, const Plan& pl, size_t p0, size_t p1, con
       if (int rc = encode_dev(h, wk, ids, lens, p.min_len, p.rows, p.width, j.n_layers, u, pf, j.full, j.ids ? p.width : h->c_S)) return rc;
       if (!j.ids) {
         const size_t c = (size_t)(j.c_row + p.first);
-        if (int rc = match_dev(h, wk, u, p.rows, G, nullptr, nullptr, j.keep_psame ? h->c_psame + c * G : nullptr, 1, h->c_best + c * 2, h->c_idx + c)) return rc;
+        if (int rc = match_dev(h, wk, u, p.rows, G, nullptr, nullptr, j.keep_psame ? h->c_psame + c * G : nullptr, j.topk ? j.topk : 1, h->c_best + c * 2, h->c_idx + c,
+                               j.topk ? h->c_topk_p + c * j.topk : nullptr, j.topk ? h->c_topk_idx + c * j.topk : nullptr)) return rc;
       } else if (j.match) {  // only the outputs the caller asked for leave the kernel (the best anchor always does)
         if (int rc = match_dev(h, wk, u, p.rows, G, j.out.logits ? wk.logits + r * G * 2 : nullptr, j.out.probs ? wk.probs + r * G * 2 : nullptr, nullptr, 1,
                                wk.best + r * 2, wk.best_idx + r)) return rc;
@@ -1303,7 +1314,8 @@ int rescore_rows(mv_handle* h, Work& wk, const Plan& pl, const Job& j, int B) {
 }
 
 // The one indexed pass over the resident corpus: rows idx[0, n) gathered into wk's pass buffer at width w, encoded in the form pf (counts: with the per-row
-// monitor counts kept), matched, and scattered back to their corpus slots — keep: their P(same) rows too, counts: the counts to c_over.  Asynchronous on wk:
+// monitor counts kept), matched, and scattered back to their corpus slots — keep: their P(same) rows too, counts: the counts to c_over; on a keeping corpus
+// (mv_corpus_keep) their embeddings and top-k lists as well: a flagged or routed row holds the safe form's, like its best anchor.  Asynchronous on wk:
 // idx stays alive until that stream has been waited for; after a failure it waits for what it enqueued.
 int run_corpus_rows(mv_handle* h, Work& wk, const int32_t* idx, int n, int w, int min_len, PassForm pf, bool keep, bool counts) {
   const int G = h->n_anchors;
@@ -1318,12 +1330,20 @@ int run_corpus_rows(mv_handle* h, Work& wk, const int32_t* idx, int n, int w, in
       HIPCHK(h, hipMemsetAsync(pf.seq_over, 0, (size_t)n * 4, wk.stream));
     }
     if (int rc = encode_dev(h, wk, wk.d_ids, wk.d_lens, min_len, n, w, -1, wk.u, pf, false, w)) return rc;
-    if (int rc = match_dev(h, wk, wk.u, n, G, nullptr, nullptr, keep ? wk.psame : nullptr, 1, wk.best, wk.best_idx)) return rc;
+    const int k = h->c_k;  // mv_corpus_keep: the rows' top-k lists (and their embeddings, wk.u) go back to their corpus slots too
+    if (int rc = match_dev(h, wk, wk.u, n, G, nullptr, nullptr, keep ? wk.psame : nullptr, k ? k : 1, wk.best, wk.best_idx, k ? wk.topk_p : nullptr,
+                           k ? wk.topk_idx : nullptr)) return rc;
     const int64_t ns = (int64_t)n * (keep ? G : 1);
     hipLaunchKernelGGL(corpus_scatter_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, wk.stream, (const float*)wk.best, (const int32_t*)wk.best_idx,
                        keep ? (const float*)wk.psame : (const float*)nullptr, (const int32_t*)wk.d_idx, n, G, h->c_best, h->c_idx, h->c_psame,
                        counts ? (const uint32_t*)wk.seq_over : (const uint32_t*)nullptr, counts ? h->c_over : (uint32_t*)nullptr);
-    return launch_check(h, "corpus_scatter");
+    if (int rc = launch_check(h, "corpus_scatter")) return rc;
+    if (!h->c_embed && !k) return MV_OK;
+    const int64_t nk = (int64_t)n * ((h->c_embed ? h->P / 4 : 0) + 2 * ((k & 3) ? k : k / 4));  // one thread per 16 bytes (corpus_scatter_keep_kernel)
+    hipLaunchKernelGGL(corpus_scatter_keep_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, wk.stream, h->c_embed ? (const float*)wk.u : (const float*)nullptr,
+                       (const uint32_t*)wk.topk_p, (const uint32_t*)wk.topk_idx, (const int32_t*)wk.d_idx, n, h->P, k, h->c_embed, (uint32_t*)h->c_topk_p,
+                       (uint32_t*)h->c_topk_idx);
+    return launch_check(h, "corpus_scatter_keep");
   };
   const int rc = run();
   if (rc != MV_OK) hipStreamSynchronize(wk.stream);
@@ -2134,6 +2154,32 @@ int mv_topk(mv_handle* h, const float* u, int B, int k, float* topk_p, int32_t* 
 } catch (...) { return on_exception(h); }
 
 // ---- resident corpus ---------------------------------------------------------------------------
+// mv_corpus_keep in force at a run against G anchors: k checked against the bank, and the arrays allocated at the first such run (like c_psame).  The zeroing
+// runs on set 0's stream and the batches may start on the other one: it is waited for here, once.
+static int keep_prepare(mv_handle* h, int G) {
+  const int k = h->c_k;
+  if (!h->c_keep_embed && !k) return MV_OK;
+  if (k > G) return fail(h, MV_ERR_INVALID, "mv_corpus_run: the kept top-k (mv_corpus_keep) exceeds the number of anchors");
+  if ((int64_t)(G <= 128 ? 1 : (G + 255) / 256) * k > 1024) return fail(h, MV_ERR_INVALID, "top-k: anchors / 256 * k must not exceed 1024");
+  const hipStream_t s0 = h->work[0].stream;
+  bool fresh = false;
+  auto alloc = [&](auto** p, int64_t count, const char* what) -> int {
+    if (*p) return MV_OK;
+    fresh = true;
+    const int rc = dev_alloc(h, s0, p, count);
+    if (rc != MV_ERR_NOMEM) return rc;
+    return fail(h, MV_ERR_NOMEM, "mv_corpus_run: cannot allocate " + std::to_string((long long)count * 4) + " bytes for the kept " + what + " (mv_corpus_keep): " + h->err);
+  };
+  if (h->c_keep_embed)
+    if (int rc = alloc(&h->c_embed, h->c_n * h->P, "embeddings")) return rc;
+  if (k) {
+    if (int rc = alloc(&h->c_topk_p, h->c_n * k, "top-k probabilities")) return rc;
+    if (int rc = alloc(&h->c_topk_idx, h->c_n * k, "top-k indices")) return rc;
+  }
+  if (fresh) HIPCHK(h, hipStreamSynchronize(s0));
+  return MV_OK;
+}
+
 int mv_corpus_upload(mv_handle* h, const int32_t* ids, const int32_t* lens, int64_t n, int S) try {
   if (int rc = check_ready(h)) return rc;
   if (!ids || !lens || n <= 0 || S <= 0 || S > h->cfg.max_pos) return fail(h, MV_ERR_INVALID, "mv_corpus_upload: bad argument");
@@ -2149,6 +2195,10 @@ int mv_corpus_upload(mv_handle* h, const int32_t* ids, const int32_t* lens, int6
   h->c_idx_live.clear();
   h->c_pending = false;
   h->c_psame_rows = 0;
+  dev_free(h, h->c_embed); dev_free(h, h->c_topk_p); dev_free(h, h->c_topk_idx);  // mv_corpus_keep: back to (0, 0)
+  h->c_embed = nullptr; h->c_topk_p = nullptr; h->c_topk_idx = nullptr;
+  h->c_keep_embed = 0; h->c_k = 0; h->c_ran = false;
+  h->c_has.clear();
   if (int rc = dev_alloc(h, s0, &h->c_ids, n * S, false)) return rc;
   if (int rc = dev_alloc(h, s0, &h->c_lens, n, false)) return rc;
   if (int rc = dev_alloc(h, s0, &h->c_best, n * 2)) return rc;
@@ -2193,11 +2243,16 @@ int mv_corpus_run_len(mv_handle* h, int64_t first, int64_t count, int batch, int
     h->c_psame_rows = h->c_n;
     h->c_G = G;
   }
+  if (int rc = keep_prepare(h, G)) return rc;
+  h->c_ran = true;
   // consecutive batches (also across calls) alternate between the two workspace sets / streams: two batches are in
   // flight at once; their results go to disjoint slices of the resident arrays
   Job j;
   j.c_row = first; j.keep_psame = keep_probs != 0;
   job_form(h, j);
+  if (h->c_embed) j.u_dev = h->c_embed + (size_t)first * h->P;  // a keeping sweep: the encoder writes the rows' slots, the matcher reads them there
+  j.topk = h->c_k;
+  if (!h->c_has.empty()) std::fill(h->c_has.begin() + first, h->c_has.begin() + first + count, (uint8_t)1);
   // ... with a sink-token list: the rows it routes run in no batch here, they are marked pending and forced (rescore_corpus encodes them in the safe form)
   const bool route = j.guard && !h->sink_tokens.empty();
   if (route)
@@ -2239,6 +2294,101 @@ int mv_corpus_results(mv_handle* h, int64_t first, int64_t count, float* best, i
     if (!h->c_psame) return fail(h, MV_ERR_STATE, "P(same) was not kept (mv_corpus_run keep_probs=0)");
     HIPCHK(h, hipMemcpyAsync(p_same, h->c_psame + (size_t)first * h->c_G, (size_t)count * h->c_G * 4, hipMemcpyDeviceToHost, s0));
   }
+  HIPCHK(h, hipStreamSynchronize(s0));
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+int mv_corpus_keep(mv_handle* h, int keep_embed, int topk) try {
+  if (int rc = check_ready(h)) return rc;
+  if (!h->c_ids) return fail(h, MV_ERR_STATE, "no resident corpus (mv_corpus_upload)");
+  if ((keep_embed != 0 && keep_embed != 1) || topk < 0 || topk > MK_KMAX) return fail(h, MV_ERR_INVALID, "mv_corpus_keep: keep_embed must be 0 or 1, topk in [0, 64]");
+  if (h->c_ran) return fail(h, MV_ERR_STATE, "mv_corpus_keep: the corpus has been swept already (call it after mv_corpus_upload, before the first mv_corpus_run)");
+  h->c_keep_embed = keep_embed;
+  h->c_k = topk;
+  if (keep_embed || topk) h->c_has.assign((size_t)h->c_n, 0); else h->c_has.clear();
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+// The checks the three readers of the kept arrays share: a corpus, a range inside it, every row of it covered by a keeping run — then what mv_corpus_results
+// collects first (the sweeps in flight, the guarded form's rescoring).
+static int kept_rows_ready(mv_handle* h, const char* who, int64_t first, int64_t count, bool kept) {
+  if (!h->c_ids) return fail(h, MV_ERR_STATE, "no resident corpus (mv_corpus_upload)");
+  if (!kept) return fail(h, MV_ERR_STATE, std::string(who) + ": the corpus does not keep that (mv_corpus_keep)");
+  if (first < 0 || count <= 0 || first + count > h->c_n || count > INT32_MAX) return fail(h, MV_ERR_INVALID, std::string(who) + ": bad range");
+  for (int64_t r = first; r < first + count; ++r)
+    if (!h->c_has[(size_t)r]) return fail(h, MV_ERR_STATE, std::string(who) + ": row " + std::to_string((long long)r) + " has not been swept by a keeping run");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = sync_all(h)) return rc;
+  return rescore_corpus(h);
+}
+
+int mv_corpus_rematch(mv_handle* h, int64_t first, int64_t count, int g_first, int keep_probs) try {
+  if (int rc = check_ready(h)) return rc;
+  if (!h->c_ids) return fail(h, MV_ERR_STATE, "no resident corpus (mv_corpus_upload)");
+  if (!h->c_embed) return fail(h, MV_ERR_STATE, "mv_corpus_rematch: no embeddings kept (mv_corpus_keep before the sweep)");
+  const int G = h->n_anchors, k = h->c_k;
+  if (G <= 0) return fail(h, MV_ERR_STATE, "anchor bank is empty");
+  if (g_first < 0 || g_first > G) return fail(h, MV_ERR_INVALID, "mv_corpus_rematch: g_first must be in [0, number of anchors]");
+  if (keep_probs != 0 && keep_probs != 1) return fail(h, MV_ERR_INVALID, "mv_corpus_rematch: keep_probs must be 0 or 1");
+  if (keep_probs && g_first > 0) return fail(h, MV_ERR_INVALID, "mv_corpus_rematch: keep_probs needs g_first == 0 (the pitch of the P(same) rows changes with the bank)");
+  if (k > G) return fail(h, MV_ERR_INVALID, "mv_corpus_rematch: the kept top-k exceeds the number of anchors");
+  if (int rc = kept_rows_ready(h, "mv_corpus_rematch", first, count, true)) return rc;
+  if (g_first == G) return MV_OK;  // nothing was appended
+  Work& wk = h->work[0];
+  const size_t P = (size_t)h->P;
+  if (keep_probs && (h->c_psame_rows != h->c_n || h->c_G != G)) {  // as mv_corpus_run_len
+    dev_free(h, h->c_psame);
+    h->c_psame = nullptr;
+    if (int rc = dev_alloc(h, wk.stream, &h->c_psame, h->c_n * G)) return rc;
+    h->c_psame_rows = h->c_n;
+    h->c_G = G;
+  }
+  auto run = [&]() -> int {
+    for (int64_t r = first; r < first + count; r += h->cfg.max_batch) {
+      const int nb = (int)std::min<int64_t>(h->cfg.max_batch, first + count - r);
+      const float* u = h->c_embed + (size_t)r * P;  // read in place
+      if (g_first == 0) {  // full: the stored results rewritten
+        if (int rc = match_dev(h, wk, u, nb, G, nullptr, nullptr, keep_probs ? h->c_psame + (size_t)r * G : nullptr, k ? k : 1, h->c_best + r * 2, h->c_idx + r,
+                               k ? h->c_topk_p + r * k : nullptr, k ? h->c_topk_idx + r * k : nullptr)) return rc;
+        continue;
+      }
+      // appended: the new anchors alone into the workspace, then folded into the stored results
+      const int ks = k ? std::min(k, G - g_first) : 0;
+      if (int rc = match_dev(h, wk, u, nb, G - g_first, nullptr, nullptr, nullptr, ks ? ks : 1, wk.best, wk.best_idx, ks ? wk.topk_p : nullptr, ks ? wk.topk_idx : nullptr,
+                             g_first)) return rc;
+      RematchMergeArgs a{nb, k, ks, g_first, h->cfg.same_idx, wk.best, wk.best_idx, wk.topk_p, wk.topk_idx, h->c_best + r * 2, h->c_idx + r,
+                         k ? h->c_topk_p + r * k : nullptr, k ? h->c_topk_idx + r * k : nullptr};
+      ProfScope ps(h, wk.stream, KC_TOPK);
+      hipLaunchKernelGGL(rematch_merge_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, wk.stream, a);
+      if (int rc = launch_check(h, "rematch_merge")) return rc;
+    }
+    return MV_OK;
+  };
+  const int rc = run();
+  const hipError_t e = hipStreamSynchronize(wk.stream);
+  if (rc != MV_OK) return rc;
+  HIPCHK(h, e);
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+int mv_corpus_embeddings(mv_handle* h, int64_t first, int64_t count, float* embed) try {
+  if (int rc = check_ready(h)) return rc;
+  if (int rc = kept_rows_ready(h, "mv_corpus_embeddings", first, count, h->c_keep_embed != 0)) return rc;
+  if (!embed) return fail(h, MV_ERR_INVALID, "mv_corpus_embeddings: bad argument");
+  const hipStream_t s0 = h->work[0].stream;
+  HIPCHK(h, hipMemcpyAsync(embed, h->c_embed + (size_t)first * h->P, (size_t)count * h->P * 4, hipMemcpyDeviceToHost, s0));
+  HIPCHK(h, hipStreamSynchronize(s0));
+  return MV_OK;
+} catch (...) { return on_exception(h); }
+
+int mv_corpus_topk(mv_handle* h, int64_t first, int64_t count, float* topk_p, int32_t* topk_idx) try {
+  if (int rc = check_ready(h)) return rc;
+  if (int rc = kept_rows_ready(h, "mv_corpus_topk", first, count, h->c_k > 0)) return rc;
+  if (!topk_p || !topk_idx) return fail(h, MV_ERR_INVALID, "mv_corpus_topk: bad argument");
+  const hipStream_t s0 = h->work[0].stream;
+  const size_t k = (size_t)h->c_k;
+  HIPCHK(h, hipMemcpyAsync(topk_p, h->c_topk_p + (size_t)first * k, (size_t)count * k * 4, hipMemcpyDeviceToHost, s0));
+  HIPCHK(h, hipMemcpyAsync(topk_idx, h->c_topk_idx + (size_t)first * k, (size_t)count * k * 4, hipMemcpyDeviceToHost, s0));
   HIPCHK(h, hipStreamSynchronize(s0));
   return MV_OK;
 } catch (...) { return on_exception(h); }

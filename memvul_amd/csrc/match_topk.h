@@ -421,3 +421,59 @@ inline void launch_topk_merge(const MatchArgs& a, hipStream_t stream) {
   else if (n <= 256) hipLaunchKernelGGL(topk_merge_kernel<4>, grid, block, 0, stream, a);
   else hipLaunchKernelGGL(topk_merge_kernel<16>, grid, block, 0, stream, a);
 }
+
+// ---- mv_corpus_rematch, appended mode: the bank grew from g_first to G anchors and only the new ones were matched (as anchors 0 .. G - g_first - 1 of the
+// slice): fold the slice's best anchor and top-ks list of each row into the stored ones.  The order is the matcher's: (mk_key(P(same)) descending, global
+// anchor index ascending), candidates compared as the 64-bit words of mk_select, so the merged lists are the bytes a match against all G anchors writes.
+struct RematchMergeArgs {
+  int n, k, ks, g_first, same_idx;  // rows; entries of a stored list (0: none kept) and of a slice list (min(k, G - g_first)); global index of slice anchor 0
+  const float* s_best;              // the slice: [n][2]
+  const int32_t* s_idx;             // [n]
+  const float* s_topk_p;            // [n][ks]
+  const int32_t* s_topk_idx;
+  float* c_best;                    // the stored results of the same rows, updated in place: [n][2]
+  int32_t* c_idx;                   // [n]
+  float* c_topk_p;                  // [n][k]
+  int32_t* c_topk_idx;
+};
+
+__device__ __forceinline__ unsigned long long mk_word(float p, int gidx) {  // (an exhausted slot, index 0x7fffffff, ranks below everything)
+  return gidx == 0x7fffffff ? 0ull : ((unsigned long long)__float_as_uint(fmaxf(mk_key(p), 0.0f)) << 32) | (unsigned)(~gidx);
+}
+__device__ __forceinline__ unsigned long long mk_readlane64(unsigned long long x, int l) {  // l wave-uniform
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, l);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), l);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// One wave per row, lane = list slot (k <= 64).  Both lists are already in order, so the rank of an entry in the merge is its own position plus the number of
+// entries of the OTHER list that beat it (a stored entry wins a tie of words: only two exhausted slots can tie); an entry whose rank is below k is written at
+// its rank.  Every lane holds its entries in registers before the first store: the stored list is rewritten in place.  No LDS, no atomics.
+__global__ __launch_bounds__(256) void rematch_merge_kernel(RematchMergeArgs a) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= a.n) return;
+  if (lane == 0) {  // the best anchor: replaced only by a strictly greater key (the stored one has the lower index); both class probabilities travel
+    const float pn = a.s_best[2 * b + a.same_idx], po = a.c_best[2 * b + a.same_idx];
+    if (mk_key(pn) > mk_key(po)) {
+      a.c_best[2 * b] = a.s_best[2 * b];
+      a.c_best[2 * b + 1] = a.s_best[2 * b + 1];
+      a.c_idx[b] = a.g_first + a.s_idx[b];
+    }
+  }
+  if (a.k <= 0) return;
+  const size_t o = (size_t)b * a.k, os = (size_t)b * a.ks;
+  float po = -1.0f, pn = -1.0f;
+  int io = 0x7fffffff, in = 0x7fffffff;
+  if (lane < a.k) { po = a.c_topk_p[o + lane]; io = a.c_topk_idx[o + lane]; }
+  if (lane < a.ks) {
+    pn = a.s_topk_p[os + lane];
+    const int si = a.s_topk_idx[os + lane];
+    in = si == 0x7fffffff ? si : a.g_first + si;
+  }
+  const unsigned long long wo = mk_word(po, io), wn = mk_word(pn, in);
+  int ro = lane, rn = lane;
+  for (int j = 0; j < a.ks; ++j) ro += mk_readlane64(wn, j) > wo ? 1 : 0;
+  for (int j = 0; j < a.k; ++j) rn += mk_readlane64(wo, j) >= wn ? 1 : 0;
+  if (lane < a.k && ro < a.k) { a.c_topk_p[o + ro] = po; a.c_topk_idx[o + ro] = io; }
+  if (lane < a.ks && rn < a.k) { a.c_topk_p[o + rn] = pn; a.c_topk_idx[o + rn] = in; }
+}

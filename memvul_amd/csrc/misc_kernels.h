@@ -384,3 +384,29 @@ __global__ __launch_bounds__(256) void corpus_scatter_kernel(const float* __rest
     if (over) c_over[r] = over[i];
   }
 }
+// ... and, on a corpus that keeps them (mv_corpus_keep), the rows' embeddings u [n][P] (NULL: not kept) and top-k lists [n][k] (k == 0: not kept) to their corpus
+// slots: one thread per 16 bytes of a row — P / 4 of the embedding, then k / 4 of each list (a k that is no multiple of 4 leaves the list rows of the corpus
+// unaligned: one thread per entry then).  Launched only when something is kept.
+__global__ __launch_bounds__(256) void corpus_scatter_keep_kernel(const float* __restrict__ u, const uint32_t* __restrict__ topk_p, const uint32_t* __restrict__ topk_idx,
+                                                                  const int32_t* __restrict__ idx, int n, int P, int k, float* __restrict__ c_embed,
+                                                                  uint32_t* __restrict__ c_topk_p, uint32_t* __restrict__ c_topk_idx) {
+  const int pu = u ? P / 4 : 0;
+  const bool vec = (k & 3) == 0;
+  const int ku = vec ? k / 4 : k;  // units of one list row
+  const int per = pu + 2 * ku;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (int64_t)n * per) return;
+  const int i = (int)(t / per);
+  int c = (int)(t - (int64_t)i * per);
+  const int64_t r = idx[i];
+  if (c < pu) {
+    *(float4*)(c_embed + r * P + 4 * c) = *(const float4*)(u + (int64_t)i * P + 4 * c);
+    return;
+  }
+  c -= pu;
+  const uint32_t* src = c < ku ? topk_p : topk_idx;
+  uint32_t* dst = c < ku ? c_topk_p : c_topk_idx;
+  if (c >= ku) c -= ku;
+  if (vec) *(uint4*)(dst + r * k + 4 * c) = *(const uint4*)(src + (int64_t)i * k + 4 * c);
+  else dst[r * k + c] = src[(int64_t)i * k + c];
+}

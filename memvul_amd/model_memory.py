@@ -347,22 +347,44 @@ class ModelMemory(Model):
         return metadata, p_same
 
     def sweep_arrays(self, arrays: Dict[str, Any], first: int = 0, last: Optional[int] = None, batch_size: int = 512,
-                     with_probs: bool = False):
+                     with_probs: bool = False, keep: bool = False, topk: int = 0):
         """``sweep`` on the array form of the evaluation set (ReaderMemory.read_arrays): rows ``first:last`` in one resident
         length-bucketed sweep, metric accumulators updated exactly as ``forward`` / ``sweep`` do (model_memory.py:133-147,
-        162-167).  Returns ``(best [n, 2], best_idx [n], p_same [n, G] or None)``; no Instances, no per-IR Python objects."""
+        162-167).  Returns ``(best [n, 2], best_idx [n], p_same [n, G] or None)``; no Instances, no per-IR Python objects.
+        keep: the corpus keeps its embeddings, so that ``rematch_arrays`` can score the same rows against a changed anchor bank without encoding them again;
+        topk: it keeps the k best anchors of every row (``engine.sweep_topk()``)."""
         if arrays["type"] not in ["test", "unlabel"]:
             raise NotImplementedError("sweep_arrays() serves the test / unlabel branch (model_memory.py:133-147)")
         last = len(arrays["lens"]) if last is None else last
         lens = np.ascontiguousarray(arrays["lens"][first:last], np.int32)
+        self._kept_rows = None
         if len(lens) == 0:
             return np.zeros((0, 2), np.float32), np.zeros((0,), np.int32), None
         ids = arrays["ids"][first:last, :int(lens.max())]
-        best, best_idx, p_same = self.engine.bucketed_sweep(ids, lens, batch_size, with_probs=with_probs)
+        if keep or topk:  # (an engine that is never asked to keep anything is called exactly as before)
+            best, best_idx, p_same = self.engine.bucketed_sweep(ids, lens, batch_size, with_probs=with_probs, keep=keep, topk=topk)
+            self._kept_rows = (first, last) if keep else None
+        else:
+            best, best_idx, p_same = self.engine.bucketed_sweep(ids, lens, batch_size, with_probs=with_probs)
+        self._score_arrays(arrays, first, last, best)
+        return best, best_idx, p_same
+
+    def _score_arrays(self, arrays: Dict[str, Any], first: int, last: int, best: np.ndarray):
         same = np.asarray(arrays["same"][first:last], bool)
         diff_idx = self.vocab.get_token_index("diff", namespace=self._label_namespace)
         self._counts(best, np.where(same, self._same_idx, diff_idx).astype(np.int64))
         self._siamese_metric.add_arrays(same.astype(np.uint8), best[:, self._same_idx])
+
+    def rematch_arrays(self, arrays: Dict[str, Any], first: int = 0, last: Optional[int] = None, with_probs: bool = False):
+        """The rows of the last ``sweep_arrays(..., keep=True)`` scored against the anchor bank as it is NOW (forward_gold_instances, model_memory.py:105-115,
+        appended to or rebuilt it since) by the matcher alone (l.135-147) — the encoder does not run.  Returns what ``sweep_arrays`` returns and updates the
+        metric accumulators the same way."""
+        last = len(arrays["lens"]) if last is None else last
+        if getattr(self, "_kept_rows", None) != (first, last):
+            raise RuntimeError("rematch_arrays(): no kept sweep of these rows — call sweep_arrays(arrays, first, last, keep=True) first (the resident corpus keeps "
+                               "its embeddings only when asked to)")
+        best, best_idx, p_same = self.engine.rematch_sweep(with_probs=with_probs)
+        self._score_arrays(arrays, first, last, best)
         return best, best_idx, p_same
 
     def format_records_json(self, labels: List[str], urls: List[str], p_same: np.ndarray) -> str:
