@@ -411,6 +411,42 @@ int mv_test_e4m3(const float* in, uint8_t* out, int64_t n);
 int mv_format_records(const char* prefixes, const int64_t* prefix_off, int64_t rows, const char* pieces, const int64_t* piece_off, int64_t cols,
                       const char* row_suffix, const double* p, char* out, int64_t cap, int64_t* written);
 
+/* ---- the device WordPiece tokenizer (memvul_amd/csrc/wordpiece.h states the rule) ---------------------------------------------------------------------------
+ * Replaces, for ASCII text, the tokenisation the reference's reader runs per issue report (PretrainedTransformerTokenizer over bert-base-uncased,
+ * reader_memory.py:88, test_config_memory.json:5-16): BertNormalizer(clean_text) -> BertPreTokenizer -> WordPiece("##") -> [CLS] A [SEP] -> truncation on the
+ * right, byte-equal to the Rust backend of BertTokenizerFast for every text whose bytes are all below 0x80.  A row that holds a byte >= 0x80, or one of the
+ * tokenizer's added tokens as a literal, case-sensitive substring of its raw bytes, is NOT tokenised: status[i] = 1, lens[i] = 0, its id row zero — the
+ * caller sends it through the tokenizer it has (memvul_amd/tokenizer.py does).
+ * An object of its own, not part of mv_handle: it needs no weights, owns its stream and its device buffers and shares no mutable state with any handle, so
+ * one thread may be inside mv_tok_encode while another is inside mv_corpus_run* / mv_forward_ragged_* on a handle of the same device.  The object itself is
+ * not re-entrant: one call at a time.
+ * mv_tok_create: the vocabulary as n_vocab strings back to back (string k = bytes vocab_off[k] .. vocab_off[k + 1] of vocab_bytes, its id is k; "##x" is
+ * the continuation piece x; an empty string stands for an id the vocabulary does not use), the added-token literals likewise, the ids of [UNK] / [CLS] /
+ * [SEP], WordPiece's max_input_chars_per_word (1 .. 190) and the normalizer's lowercase flag.  The hash table is built here, on the host (open addressing,
+ * load <= 0.5, every hit confirmed on the bytes).  device >= 0 uploads it and creates the stream; device < 0 builds the table only: such an object serves
+ * mv_tok_encode_host and needs no GPU.  A bad argument -> MV_ERR_INVALID, *out = NULL, the message from mv_tok_last_error(NULL).
+ * mv_tok_encode: n texts (text i = bytes off[i] .. off[i + 1] of `text`, off int64 [n + 1] ascending) -> ids int32 [n][max_length] zero-padded, lens
+ * int32 [n], status uint8 [n].  add_special != 0 writes [CLS] first and [SEP] last; truncation to max_length counts them.  The kernel (one wave per text),
+ * synchronous: the results are in host memory on return.  Device buffers grow to the largest call; the text goes to the device in chunks of at most 64 MiB
+ * (a chunk ends at a row boundary; a single larger row is a chunk of its own).  On an object created with device < 0 -> MV_ERR_STATE.
+ * mv_tok_encode_host: the same arguments, the same rule, single-threaded on the CPU: the rule's reference and the tests' second opinion, not a product path.
+ * Both: n < 0, max_length outside 2 .. 512, offsets not ascending or negative, or NULL where data is needed -> MV_ERR_INVALID with ids, lens and status
+ * untouched; n == 0 -> MV_OK, nothing read or written (also on an object without a device).  A HIP failure in the middle of a call waits for whatever the
+ * call had queued before it returns: the caller's arrays are not written after a failed call.
+ * mv_tok_kernel_ms: *ms = the kernel's own time, from HIP events around each chunk's launch, summed over the chunks of the last mv_tok_encode (0 before the
+ * first): what of a call is tokenising and what is copying. */
+typedef struct mv_tokenizer mv_tokenizer;
+int mv_tok_create(int device, const char* vocab_bytes, const int64_t* vocab_off, int n_vocab, const char* literal_bytes, const int64_t* literal_off,
+                  int n_literals, int unk_id, int cls_id, int sep_id, int max_chars_per_word, int lowercase, mv_tokenizer** out);
+int mv_tok_encode(mv_tokenizer* tok, const char* text, const int64_t* off, int n, int max_length, int add_special, int32_t* ids, int32_t* lens,
+                  uint8_t* status);
+int mv_tok_encode_host(mv_tokenizer* tok, const char* text, const int64_t* off, int n, int max_length, int add_special, int32_t* ids, int32_t* lens,
+                       uint8_t* status);
+int mv_tok_kernel_ms(mv_tokenizer* tok, float* ms);
+void mv_tok_destroy(mv_tokenizer* tok);
+/* Last error message of this object (or of a failed mv_tok_create when tok == NULL). */
+const char* mv_tok_last_error(mv_tokenizer* tok);
+
 #ifdef __cplusplus
 }
 #endif

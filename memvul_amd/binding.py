@@ -94,6 +94,19 @@ def sink_tokens_policy() -> Optional[List[int]]:
     return None if v is None else parse_sink_tokens(v)
 
 
+TOKENIZE_MODES = ("host", "gpu")
+
+
+def tokenize_policy(option=None) -> str:
+    """engine_options["tokenize"] or $MEMVUL_TOKENIZE = host (default) | gpu, parsed strictly: where the drivers tokenise the issue reports — "gpu" attaches
+    the reader's tokenizer to the model's device (tokenizer.PretrainedTransformerTokenizer.attach_device: ASCII rows through DeviceWordPiece, every other row
+    through the tokenizer it already has).  The option wins over the environment; an unknown value raises."""
+    v, src = (option, 'engine_options["tokenize"]') if option is not None else (os.environ.get("MEMVUL_TOKENIZE", "host"), "MEMVUL_TOKENIZE")
+    if v not in TOKENIZE_MODES:
+        raise ValueError(f"{src}={v!r}: expected 'host' or 'gpu'")
+    return v
+
+
 def _sink_token_list(ids) -> List[int]:
     """engine_options["sink_tokens"] / Engine.set_sink_tokens: a sequence of integer token ids (a string is MEMVUL_SINK_TOKENS' syntax), checked as strictly."""
     if isinstance(ids, str):
@@ -131,6 +144,7 @@ ABI_SYMBOLS = [
     "mv_set_sink_tokens", "mv_get_sink_tokens", "mv_route_stats", "mv_route_scan", "mv_corpus_route_flags", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
     "mv_debug_encode", "mv_debug_read", "mv_test_gemm", "mv_test_gemm_pp", "mv_test_gemm_f32", "mv_test_e4m3", "mv_format_records", "mv_comm_prepare", "mv_comm_unique_id", "mv_comm_init", "mv_comm_allgather",
     "mv_comm_destroy", "mv_comm_info", "mv_device_count",
+    "mv_tok_create", "mv_tok_encode", "mv_tok_encode_host", "mv_tok_kernel_ms", "mv_tok_destroy", "mv_tok_last_error",
 ]
 
 
@@ -225,6 +239,12 @@ def load_library(path: Optional[str] = None, dev: bool = False):
         "mv_comm_destroy": (C.c_int, [vp]),
         "mv_comm_info": (C.c_int, [vp, P(C.c_int), C.c_int]),
         "mv_device_count": (C.c_int, []),
+        "mv_tok_create": (C.c_int, [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(vp)]),
+        "mv_tok_encode": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "mv_tok_encode_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "mv_tok_kernel_ms": (C.c_int, [vp, P(C.c_float)]),
+        "mv_tok_destroy": (None, [vp]),
+        "mv_tok_last_error": (C.c_char_p, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
@@ -978,3 +998,73 @@ def e4m3_decode(b: np.ndarray) -> np.ndarray:
     v = np.where(e == 0, m * 2.0 ** -9, (8 + m) * 2.0 ** (e - 10))
     v = np.where((e == 15) & (m == 7), np.nan, v)
     return (np.where(b & 0x80, -v, v)).astype(np.float32)
+
+
+def _packed(strings) -> Tuple[bytes, np.ndarray]:
+    """Byte strings back to back + int64 offsets [n + 1]."""
+    off = np.zeros(len(strings) + 1, np.int64)
+    if len(strings):
+        np.cumsum(np.fromiter((len(b) for b in strings), np.int64, len(strings)), out=off[1:])
+    return b"".join(strings), off
+
+
+class DeviceWordPiece:
+    """The device WordPiece tokenizer (include/memvul_hip.h mv_tok_*): ASCII text -> the ids BertTokenizerFast's backend gives it.  ``vocab``: the pieces
+    as bytes, index = id (b"" for an unused id); ``literals``: the tokenizer's added tokens as bytes — a row that holds one, or a byte >= 0x80, comes back with
+    status 1, length 0 and a zero id row, for the caller to encode with the tokenizer it has.  ``device=None``: the table only; such an object serves
+    ``encode_host`` (the rule on the CPU: tests and reference) and needs no GPU.  Its own object in the library: usable from one thread while another drives
+    an ``Engine`` of the same device; not re-entrant itself."""
+
+    def __init__(self, vocab, literals, unk_id: int, cls_id: int, sep_id: int, max_chars_per_word: int = 100, lowercase: bool = True,
+                 device: Optional[int] = 0, lib=None):
+        self._lib = lib or load_library()
+        self._t = None
+        vb, vo = _packed(list(vocab))
+        lb, lo = _packed(list(literals))
+        t = C.c_void_p()
+        self.device = -1 if device is None else int(device)
+        rc = self._lib.mv_tok_create(self.device, vb, _ptr(vo), len(vo) - 1, lb, _ptr(lo), len(lo) - 1, int(unk_id), int(cls_id), int(sep_id),
+                                     int(max_chars_per_word), 1 if lowercase else 0, C.byref(t))
+        if rc != 0:
+            msg = self._lib.mv_tok_last_error(None)
+            raise RuntimeError(f"mv_tok_create failed ({rc}): {msg.decode() if msg else ''}")
+        self._t = t
+
+    def close(self):
+        if getattr(self, "_t", None):
+            self._lib.mv_tok_destroy(self._t)
+            self._t = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _run(self, fn, name: str, packed: bytes, offsets, max_length: int, add_special: bool):
+        off = _as(offsets, np.int64)
+        n = len(off) - 1
+        if n < 0:
+            raise ValueError(f"{name}: offsets must hold n + 1 values")
+        ids, lens, status = np.zeros((n, int(max_length)), np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        rc = fn(self._t, packed, _ptr(off), n, int(max_length), 1 if add_special else 0, _ptr(ids), _ptr(lens), _ptr(status))
+        if rc != 0:
+            msg = self._lib.mv_tok_last_error(self._t)
+            raise RuntimeError(f"{name} failed ({rc}): {msg.decode() if msg else ''}")
+        return ids, lens, status
+
+    def encode(self, packed: bytes, offsets, max_length: int, add_special: bool = True):
+        """The kernel: text i = packed[offsets[i]:offsets[i + 1]] -> (ids int32 [n, max_length] zero-padded, lens int32 [n], status uint8 [n])."""
+        return self._run(self._lib.mv_tok_encode, "mv_tok_encode", packed, offsets, max_length, add_special)
+
+    def kernel_ms(self) -> float:
+        """The kernel's own time of the last ``encode`` (HIP events around each chunk's launch), in milliseconds."""
+        ms = C.c_float()
+        rc = self._lib.mv_tok_kernel_ms(self._t, C.byref(ms))
+        if rc != 0:
+            raise RuntimeError(f"mv_tok_kernel_ms failed ({rc})")
+        return float(ms.value)
+
+    def encode_host(self, packed: bytes, offsets, max_length: int, add_special: bool = True):
+        """The same rule, single-threaded on the CPU (mv_tok_encode_host)."""
+        return self._run(self._lib.mv_tok_encode_host, "mv_tok_encode_host", packed, offsets, max_length, add_special)

@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libmemvul_hip.so")
 LIB_PATH_DEV = os.path.join(LIB_DIR, "libmemvul_hip_dev.so")
 DEV_FLAGS = ("-DMEMVUL_DEV_SWITCHES",)
 SOURCES = ["engine.hip"]
-HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", os.path.join(ROOT, "include", "memvul_hip.h")]
+HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", "wordpiece.h", os.path.join(ROOT, "include", "memvul_hip.h")]
 ARCH = "gfx950"
 
 

@@ -26,7 +26,7 @@ from typing import Any, Dict, List, Optional
 
 import numpy as np
 
-from .binding import Engine, compute_dtype_of, wanted_form
+from .binding import Engine, compute_dtype_of, wanted_form, tokenize_policy
 from .custom_metric import SiameseMeasureV1
 from .data import Instance, collate
 from .registry import HAVE_ALLENNLP, Model, TextFieldEmbedder, TokenEmbedder, Vocabulary, register_builtin
@@ -192,6 +192,9 @@ class ModelMemory(Model):
         # finalize and raises unless the form is "guarded" (binding.sink_tokens_policy).
         cd = opts.pop("compute_dtype", None)
         cd = wanted_form(cd) or compute_dtype_of(cd)
+        # engine_options["tokenize"] = host | gpu (or $MEMVUL_TOKENIZE) is the drivers' switch (predict_memory.attach_tokenizer), not an engine argument; it is
+        # checked here too, so that a typo raises wherever the options arrive first
+        tokenize_policy(opts.pop("tokenize", None))
         if self._engine is not None:
             self._engine.close()
         self._engine = Engine(self._device_index, vocab_size=vocab_size, layers=layers, max_pos=max_pos, type_vocab=type_vocab,

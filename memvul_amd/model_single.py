@@ -17,7 +17,7 @@ from typing import Any, Dict, List, Optional
 
 import numpy as np
 
-from .binding import Engine, compute_dtype_of, wanted_form
+from .binding import Engine, compute_dtype_of, wanted_form, tokenize_policy
 from .model_memory import PFX_BERT, _ClassificationCounts, _np
 from .registry import Model, TextFieldEmbedder, Vocabulary
 
@@ -64,6 +64,7 @@ class ModelSingle(Model):
         eng_sd["_projector.weight"] = np.zeros((2, 3 * 512), np.float32)
         opts = dict(max_tokens=128 * 512, max_batch=512, max_anchors=1)
         opts.update(self._engine_options)
+        tokenize_policy(opts.pop("tokenize", None))  # the drivers' switch (predict_memory.attach_tokenizer), not an engine argument; a typo raises here too
         opts_compute = opts.pop("compute_dtype", None)  # None: binding.default_compute() — precise unless $MEMVUL_COMPUTE says otherwise
         # (engine_options["sink_tokens"] = [id, ...] / $MEMVUL_SINK_TOKENS: the guarded form's sink-token list, applied by Engine.load_state_dict — guarded only)
         if self._engine is not None:

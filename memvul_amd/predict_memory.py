@@ -255,6 +255,22 @@ def _jsonable(x):
     return x
 
 
+def attach_tokenizer(archive, engine_options=None) -> bool:
+    """The tokenize switch (binding.tokenize_policy: engine_options["tokenize"] or $MEMVUL_TOKENIZE = host | gpu, host by default): with "gpu" the reader's
+    tokenizer is attached to the model's device (PretrainedTransformerTokenizer.attach_device), so that ``batch_ids`` — what read_arrays / iter_arrays and the
+    batched Instance readers call — tokenises its ASCII rows there.  A tokenizer the device rule does not restate raises; nothing falls back silently.
+    Returns True when a device was attached."""
+    from .binding import tokenize_policy
+
+    if tokenize_policy((engine_options or {}).get("tokenize")) != "gpu":
+        return False
+    tok = getattr(archive.dataset_reader, "_tokenizer", None)
+    if not hasattr(tok, "attach_device"):
+        raise RuntimeError(f"tokenize=gpu: the reader's tokenizer ({type(tok).__name__}) cannot be attached to a device")
+    tok.attach_device(getattr(archive.model, "_device_index", 0))
+    return True
+
+
 def test_siamese(archive_file, input_file, input_golden_file, test_config=None, weights_file=None, output_file=None,
                  predictions_output_file=None, batch_size=64, cuda_device=0, seed=2021, package="memvul_amd",
                  batch_weight_key="", file_friendly_logging=False, engine_options=None, sweep=False) -> Dict[str, Any]:
@@ -265,6 +281,7 @@ def test_siamese(archive_file, input_file, input_golden_file, test_config=None, 
     overrides = test_config or ""
     archive = load_archive(archive_file, weights_file=weights_file, cuda_device=cuda_device, overrides=overrides,
                            engine_options=engine_options)
+    attach_tokenizer(archive, engine_options)
     config = archive.config
     model = archive.model
     dataset_reader = archive.dataset_reader                        # loads the test samples
@@ -330,6 +347,7 @@ def test_siamese_sharded(archive_file, input_file, input_golden_file, test_confi
     overrides.setdefault("model", {})["device"] = f"cuda:{local_rank}"
     archive = load_archive(archive_file, weights_file=weights_file, cuda_device=local_rank, overrides=overrides,
                            engine_options=engine_options)
+    attach_tokenizer(archive, engine_options)
     model = archive.model
     model.eval()
     try:

@@ -11,7 +11,7 @@ import numpy as np
 
 from .archive import load_archive
 from .data import DataLoader
-from .predict_memory import _jsonable, evaluate, model_measure
+from .predict_memory import _jsonable, attach_tokenizer, evaluate, model_measure
 
 logger = logging.getLogger(__name__)
 
@@ -24,6 +24,7 @@ def test(archive_file, input_file, test_config=None, weights_file=None, output_f
     """predict_single.py:49-108."""
     archive = load_archive(archive_file, weights_file=weights_file, cuda_device=cuda_device, overrides=test_config or "",
                            engine_options=engine_options)
+    attach_tokenizer(archive, engine_options)
     config, model = archive.config, archive.model
     model.eval()
     dataset_reader = archive.dataset_reader

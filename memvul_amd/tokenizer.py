@@ -76,6 +76,9 @@ class PretrainedTransformerTokenizer(Tokenizer):
         self.model_name, self._add_special, self._max_length = model_name, add_special_tokens, max_length
         self.vocab_size = vocab_size
         self._hf = None
+        self._device = None          # attach_device: the binding.DeviceWordPiece the ASCII rows of batch_ids go through
+        self._device_encode = None
+        self.device_counts = {"device": 0, "literal": 0, "non_ascii": 0}  # rows batch_ids tokenised on the device / got back for an added-token literal / kept off it
         vocab = _find_vocab(model_name)
         if vocab is None:
             # a cached / local HuggingFace copy of `model_name` (what AllenNLP's tokenizer loads, reader_memory.py:88)
@@ -127,6 +130,112 @@ class PretrainedTransformerTokenizer(Tokenizer):
             return [CLS_ID] + ids + [SEP_ID]
         return ids[: self._max_length] if self._max_length is not None else ids
 
+    def device_spec(self) -> Dict:
+        """What binding.DeviceWordPiece needs, read from the serialised backend tokenizer — or a ValueError naming the field that makes this tokenizer something
+        the device rule (memvul_amd/csrc/wordpiece.h) does not restate.  No silent fallback: a tokenizer that is refused stays on the host because the caller
+        sees the error."""
+        import json
+
+        if self._hf is None or getattr(self._hf, "backend_tokenizer", None) is None:
+            raise ValueError("attach_device: the CRC32 hashing stand-in (no WordPiece backend) is not what the device tokenizer restates")
+        d = json.loads(self._hf.backend_tokenizer.to_str())
+        model, norm, pre, post = d.get("model") or {}, d.get("normalizer") or {}, d.get("pre_tokenizer") or {}, d.get("post_processor") or {}
+
+        def need(where, field, got, want):
+            if got != want:
+                raise ValueError(f"attach_device: {where}.{field} is {got!r}, the device tokenizer restates {want!r} only")
+
+        need("model", "type", model.get("type"), "WordPiece")
+        need("model", "continuing_subword_prefix", model.get("continuing_subword_prefix"), "##")
+        need("normalizer", "type", norm.get("type"), "BertNormalizer")
+        need("normalizer", "clean_text", norm.get("clean_text"), True)
+        need("pre_tokenizer", "type", pre.get("type"), "BertPreTokenizer")
+        vocab = model["vocab"]
+        if post.get("type") == "TemplateProcessing":
+            single = post.get("single") or []
+            shape = [next(iter(x)) for x in single]
+            if shape != ["SpecialToken", "Sequence", "SpecialToken"]:
+                raise ValueError(f"attach_device: post_processor.single is {shape!r}, the device tokenizer restates [CLS] A [SEP] only")
+            cls_tok, sep_tok = single[0]["SpecialToken"]["id"], single[2]["SpecialToken"]["id"]
+            cls_id, sep_id = post["special_tokens"][cls_tok]["ids"], post["special_tokens"][sep_tok]["ids"]
+            if len(cls_id) != 1 or len(sep_id) != 1:
+                raise ValueError("attach_device: post_processor.special_tokens: a special token of more than one id")
+            cls_id, sep_id = cls_id[0], sep_id[0]
+        elif post.get("type") == "BertProcessing":
+            cls_id, sep_id = post["cls"][1], post["sep"][1]
+        else:
+            raise ValueError(f"attach_device: post_processor.type is {post.get('type')!r}, the device tokenizer restates [CLS] A [SEP] only")
+        literals = []
+        for a in d.get("added_tokens") or []:
+            if a.get("normalized"):  # matched AFTER normalisation: a raw substring search does not find what the backend finds
+                raise ValueError(f"attach_device: added_tokens[{a.get('content')!r}].normalized is True, the device tokenizer hands back raw literals only")
+            if a.get("content"):
+                literals.append(a["content"].encode("utf-8"))
+        unk = model.get("unk_token")
+        if unk not in vocab:
+            raise ValueError(f"attach_device: model.unk_token {unk!r} is not in the vocabulary")
+        pieces = [b""] * (max(vocab.values()) + 1)
+        for tok, i in vocab.items():
+            pieces[i] = tok.encode("utf-8")
+        return {"vocab": pieces, "literals": literals, "unk_id": vocab[unk], "cls_id": cls_id, "sep_id": sep_id,
+                "max_chars_per_word": int(model.get("max_input_chars_per_word", 100)), "lowercase": bool(norm.get("lowercase"))}
+
+    def attach_device(self, device_index: int = 0, host_restatement: bool = False):
+        """Tokenise the ASCII rows of ``batch_ids`` on GPU ``device_index`` (binding.DeviceWordPiece); every other row, and every row that comes back for an
+        added-token literal, keeps going through the Rust tokenizer: the arrays are those of the host path for every input.  Raises, naming the field, when
+        the backend is not what the device rule restates (device_spec) or ``max_length`` is outside 2 .. 512.  ``max_length=None`` attaches but leaves
+        batch_ids on the host: without it neither the row width nor the work per row is bounded.  ``host_restatement``: run the same rule through
+        mv_tok_encode_host instead, no GPU — for tests; no switch selects it."""
+        from .binding import DeviceWordPiece
+
+        spec = self.device_spec()
+        if self._max_length is not None and not 2 <= int(self._max_length) <= 512:
+            raise ValueError(f"attach_device: max_length is {self._max_length!r}, the device tokenizer takes 2 .. 512")
+        self.detach_device()
+        self._device = DeviceWordPiece(device=None if host_restatement else int(device_index), **spec)
+        self._device_encode = self._device.encode_host if host_restatement else self._device.encode
+        return self
+
+    def detach_device(self):
+        if self._device is not None:
+            self._device.close()
+        self._device = self._device_encode = None
+
+    def _device_batch_ids(self, bt, texts: List[str]):
+        """batch_ids with a device attached: ASCII rows packed and encoded there, the rest — and the rows handed back — in ONE encode_batch call, merged in
+        the caller's order and trimmed to the longest row, exactly the arrays of the host path."""
+        import numpy as np
+
+        n, width = len(texts), int(self._max_length)
+        flags = np.fromiter((t.isascii() for t in texts), dtype=bool, count=n)  # (a flag read in CPython)
+        asc = np.flatnonzero(flags)
+        back = np.zeros(0, np.int64)
+        ids, lens = None, np.zeros(n, np.int32)
+        if len(asc):
+            rows = texts if len(asc) == n else [texts[i] for i in asc]
+            off = np.zeros(len(rows) + 1, np.int64)
+            np.cumsum(np.fromiter((len(t) for t in rows), np.int64, len(rows)), out=off[1:])  # (ASCII: characters = bytes)
+            d_ids, d_lens, d_status = self._device_encode("".join(rows).encode("ascii"), off, width, self._add_special)
+            back = asc[d_status != 0]
+            if len(asc) == n:
+                ids, lens = d_ids, d_lens
+            else:
+                ids = np.zeros((n, width), np.int32)
+                ids[asc], lens[asc] = d_ids, d_lens
+        else:
+            ids = np.zeros((n, width), np.int32)
+        rest = np.sort(np.concatenate([np.flatnonzero(~flags), back]))
+        if len(rest):
+            bt.enable_truncation(max_length=self._max_length)
+            bt.no_padding()
+            for i, e in zip(rest, bt.encode_batch([texts[i] for i in rest], add_special_tokens=self._add_special)):
+                lens[i] = len(e)
+                ids[i, :len(e)] = e.ids
+        self.device_counts["device"] += len(asc) - len(back)
+        self.device_counts["literal"] += len(back)
+        self.device_counts["non_ascii"] += n - len(asc)
+        return np.ascontiguousarray(ids[:, :int(lens.max())]), lens
+
     def batch_ids(self, texts: List[str], workers: int = 0):
         """Array form of ``tokenize`` for a whole file: ``(ids int32 [N, L] zero-padded, lens int32 [N])`` with exactly the
         ids ``tokenize`` gives text by text.  The WordPiece path is one batched call into the Rust tokenizer (parallel
@@ -134,6 +243,8 @@ class PretrainedTransformerTokenizer(Tokenizer):
         import numpy as np
 
         bt = getattr(self._hf, "backend_tokenizer", None) if self._hf is not None else None
+        if bt is not None and len(texts) and self._device_encode is not None and self._max_length is not None:
+            return self._device_batch_ids(bt, list(texts))
         if bt is not None and len(texts):
             # the Rust tokenizer itself, not the transformers wrapper around it: the wrapper turns every encoding into dicts of Python lists under the interpreter
             # lock (1.3 s of a 1.8 s call for 8 k reports; the same ids: tests/test_plumbing.py) — here the ids go from the encodings into ONE flat int32 array and from
