@@ -101,14 +101,82 @@ def device_code_objects(lib_path: str = None) -> list:
 
 
 def device_code_fingerprint(lib_path: str = None) -> str:
-    """sha256 of the gfx950 code object(s) embedded in the shared library: what the GPU executes.  Host-only edits of engine.hip leave it unchanged,
-    any kernel change moves it — bench.py keys the counter figures of profiles/pmc_current.json on this line of the stamp."""
+    """sha256 of the gfx950 code object(s) embedded in the shared library: what the GPU executes.  Any kernel change moves it — bench.py keys the counter
+    figures of profiles/pmc_current.json on this line of the stamp.  A host-only edit of engine.hip leaves the KERNELS unchanged (kernel_fingerprints
+    below compares them one by one), but this hash — the stamp's `dev` line — may still move: the kernels are laid out in the code object in the order
+    in which the host code first uses them."""
     import hashlib
 
     h = hashlib.sha256()
     for co in device_code_objects(lib_path):
         h.update(co)
     return h.hexdigest()
+
+
+STT_OBJECT, STT_FUNC, STB_GLOBAL = 1, 2, 1
+
+
+def code_object_symbols(co: bytes):
+    """The defined FUNC and OBJECT symbols of one code object (ELF64, little endian) as (name, type, binding, bytes), read from its section and symbol
+    tables; symbols of sections without file contents (.bss) are left out."""
+    import struct
+
+    def need(off, size, what):  # never trust offsets read from the file
+        if off < 0 or size < 0 or off + size > len(co):
+            raise RuntimeError(f"code object: {what} points outside the file")
+
+    need(0, 64, "ELF header")
+    if co[:6] != b"\x7fELF\x02\x01":
+        raise RuntimeError("code object: not a little-endian ELF64 file")
+    (shoff,) = struct.unpack_from("<Q", co, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", co, 0x3A)
+    if shentsize < 64:
+        raise RuntimeError("code object: section headers shorter than ELF64's")
+    need(shoff, shentsize * shnum, "section header table")
+    # (type, address, file offset, size, link, entry size) per section
+    secs = [struct.unpack_from("<4xI8xQQQI4x8xQ", co, shoff + i * shentsize) for i in range(shnum)]
+    out = []
+    for typ, _, off, size, link, entsize in secs:
+        if typ != 2:  # SHT_SYMTAB
+            continue
+        need(off, size, "symbol table")
+        if entsize < 24 or link >= shnum:
+            raise RuntimeError("code object: malformed symbol table header")
+        _, _, stroff, strsize, _, _ = secs[link]
+        need(stroff, strsize, "string table")
+        for s in range(off, off + size - entsize + 1, entsize):
+            name, info, shndx, value, nbytes = struct.unpack_from("<IBxHQQ", co, s)
+            if (info & 15) not in (STT_OBJECT, STT_FUNC) or shndx == 0 or shndx >= shnum or nbytes == 0:
+                continue
+            styp, saddr, soff, ssize, _, _ = secs[shndx]
+            if styp == 8:  # SHT_NOBITS
+                continue
+            if value < saddr or value - saddr + nbytes > ssize:
+                raise RuntimeError("code object: a symbol lies outside its section")
+            need(soff + value - saddr, nbytes, "symbol")
+            end = co.find(b"\0", stroff + name, stroff + strsize) if name < strsize else -1
+            if end < 0:
+                raise RuntimeError("code object: a symbol name lies outside the string table")
+            out.append((co[stroff + name:end].decode(), info & 15, info >> 4, co[soff + value - saddr:soff + value - saddr + nbytes]))
+    return out
+
+
+def kernel_fingerprints(lib_path: str = None) -> dict:
+    """The device code of the library kernel by kernel: {symbol: sha256}, for every function (its instruction bytes) and every kernel descriptor
+    `<kernel>.kd` (its 64 bytes with bytes 16 .. 23 zeroed: the offset from the descriptor to the kernel's entry, the one field that depends on where
+    the kernel lies in the code object).  Unlike device_code_fingerprint it does not move with the ORDER of the kernels, so it is equal before and
+    after a host-only edit of engine.hip, and between the product and the development build of one tree.  No external tool is called (a GPU box may have
+    none)."""
+    import hashlib
+
+    out = {}
+    for co in device_code_objects(lib_path):
+        for name, typ, _, data in code_object_symbols(co):
+            if typ == STT_FUNC:
+                out[name] = hashlib.sha256(data).hexdigest()
+            elif name.endswith(".kd") and len(data) == 64:
+                out[name] = hashlib.sha256(data[:16] + bytes(8) + data[24:]).hexdigest()
+    return out
 
 
 def read_stamp(dev: bool = False) -> dict:

@@ -23,7 +23,7 @@
 //   * NCH = 3 / 4 (S = 384 / 512, instantiated with NKB = 2): a work unit is (batch row, head, block of 128 queries)
 //     and its keys arrive as NCH chunks of 128 through the same ring; every chunk after the first rescales O and the row
 //     sums by exp2(m_old - m_new) (online softmax at chunk granularity), so 256 < S <= 512 keeps the LDS-DMA pipeline
-//     with 64 score registers per lane and two 4-wave workgroups per CU (engine.hip: attention_v2_kernel<2, S / 128>).
+//     with 64 score registers per lane and two 4-wave workgroups per CU (engine.hip ATTN_VARIANTS, the one list of the instantiations and their launch shapes: <2, S / 128>).
 #pragma once
 #include "attention.h"
 #include "gemm_pp.h"  // glds16, pack_h2, x8_planes4
@@ -41,7 +41,7 @@
 // ~ 1 / sqrt(keys), so short sequences feel it most (profiles/r05_f_length_envelope.txt: 9.4e-4 on the logits at 8 tokens against 2.3e-4 at 256) — and
 // there the second planes are nearly free: the lo planes of K and V^T (written by the QKV projection's epilogue, GemmArgs::k_lo / vt_lo) ride through the
 // ring next to K and V^T, Q's lo fragments are prefetched with Q's, P_lo = fp16(p - fp16(p)) is formed with the packing.
-// VLO 1 with NCH > 1 (the SAFE form of MV_F16X8, engine.hip mv_set_form: padded lengths 192 .. 512 as <1, 3>, <2, 2>, <2, 3>, <2, 4>): the same two planes through the chunked
+// VLO 1 with NCH > 1 (the SAFE form of MV_F16X8, engine.hip mv_set_form; ATTN_VARIANTS: padded lengths 192 .. 512 as <1, 3>, <2, 2>, <2, 3>, <2, 4>): the same two planes through the chunked
 // ring — a slot holds one chunk's K, V^T, V^T_lo, K_lo (32 NKB KiB), the lo products go into the accumulators the hi products go into, so the chunk rescale
 // exp2(m_old - m_new) carries them along, and P_lo is formed per chunk from that chunk's p.  A 128 KiB ring leaves room for ONE 4-wave workgroup per CU, one wave
 // per SIMD, so these instantiations take the whole 512-register budget (amdgpu_waves_per_eu(1, 1): at (2, 2) they spill 160 - 190 VGPRs); every other

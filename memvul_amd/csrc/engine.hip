@@ -488,20 +488,25 @@ int launch_gemm128(mv_handle* h, hipStream_t stream, int cls, GemmArgs a) {
 // 4x the workgroups of the 128^2 kernel and a K loop that is DMA-latency-bound per step rather than per tile
 constexpr int RING64_LDS = 4 * (64 + 64) * 64 * 2;
 template <int EPI>
+constexpr auto ring64_kernel = gemm_ring_kernel<EPI, 1, 1, 2, 2, 64, 4, 2>;
+template <int EPI>
 int launch_ring64(mv_handle* h, hipStream_t stream, int cls, GemmArgs a) {
   if (a.M % 64 || a.N % 64 || a.K % 64) return fail(h, MV_ERR_INVALID, "gemm_ring: shape not a multiple of the 64 x 64 x 64 tile");
   a.GN = choose_gn(a.N / 64, 8);
   const int grid = (a.M / 64) * (a.N / 64);
   ProfScope ps(h, stream, cls);
-  hipLaunchKernelGGL((gemm_ring_kernel<EPI, 1, 1, 2, 2, 64, 4, 2>), dim3(grid), dim3(256), RING64_LDS, stream, a);
+  hipLaunchKernelGGL(ring64_kernel<EPI>, dim3(grid), dim3(256), RING64_LDS, stream, a);
   return launch_check(h, "gemm_ring");
 }
 
 // The persistent ping-pong GEMM (gemm_pp.h): one workgroup per CU walks the 256^2 output tiles.  a.A8 set = the
 // MV_F16X8 build (a second, fp8 sweep over [A8 | W8]).
+template <int PPEPI, int X8>
+constexpr auto pp_kernel = gemm_pp_kernel<PPEPI, PPEPI != PP_RESLN3, X8>;  // (RAW: every kind but the residual one)
+template <int PPEPI>
+constexpr int pp_lds = PPEPI != PP_RESLN3 ? PP_LDS_BYTES_RAW : PP_LDS_BYTES;
 template <int PPEPI>
 int launch_pp(mv_handle* h, hipStream_t stream, int cls, GemmArgs a) {
-  constexpr int RAW = PPEPI != PP_RESLN3;
   if (a.M % 256 || a.N % 256 || a.K % 128 || a.K < 256 || a.N > MV_INTER)
     return fail(h, MV_ERR_INVALID, "gemm_pp: M,N % 256, K % 128, K >= 256, N <= 3072 required");  // K >= 256: the RAW kernels stage the
                                                                                               // next tile's statistics at K-tile 2
@@ -515,16 +520,24 @@ int launch_pp(mv_handle* h, hipStream_t stream, int cls, GemmArgs a) {
   const int grid = tiles < h->num_cu ? tiles : h->num_cu;
   // the A-stationary raster (gemm_pp.h raster_pp; MEMVUL_RASTER=1): only where its windows tile the sequence exactly
   a.raster_mode = (h->pp_raster == 1 && a.N / 256 > a.GN && ((a.M / 256) * a.GN) % grid == 0) ? 1 : 0;
-  const int lds = RAW ? PP_LDS_BYTES_RAW : PP_LDS_BYTES;
   ProfScope ps(h, stream, cls);
   if (a.A8) {
     if (!a.W8 || (PPEPI != PP_QK && !a.out8)) return fail(h, MV_ERR_STATE, "internal: MV_F16X8 GEMM without its fp8 planes");
-    hipLaunchKernelGGL((gemm_pp_kernel<PPEPI, RAW, 1>), dim3(grid), dim3(512), lds, stream, a);
+    hipLaunchKernelGGL((pp_kernel<PPEPI, 1>), dim3(grid), dim3(512), pp_lds<PPEPI>, stream, a);
   } else {
-    hipLaunchKernelGGL((gemm_pp_kernel<PPEPI, RAW, 0>), dim3(grid), dim3(512), lds, stream, a);
+    hipLaunchKernelGGL((pp_kernel<PPEPI, 0>), dim3(grid), dim3(512), pp_lds<PPEPI>, stream, a);
   }
   return launch_check(h, "gemm_pp");
 }
+
+// The kernels above that ask for more than 64 KiB of dynamic LDS, with the bytes their launchers pass: mv_create opts every one of them in
+struct GemmLdsOptIn { void (*kernel)(GemmArgs); int lds; };
+constexpr GemmLdsOptIn GEMM_LDS_OPT_INS[] = {
+    {ring64_kernel<EPI_F32>, RING64_LDS},       {ring64_kernel<EPI_QKV>, RING64_LDS},        {ring64_kernel<EPI_GELU>, RING64_LDS},
+    {ring64_kernel<EPI_RES>, RING64_LDS},       {pp_kernel<PP_QK, 0>, pp_lds<PP_QK>},        {pp_kernel<PP_GELU, 0>, pp_lds<PP_GELU>},
+    {pp_kernel<PP_RESLN3, 0>, pp_lds<PP_RESLN3>}, {pp_kernel<PP_QK, 1>, pp_lds<PP_QK>},      {pp_kernel<PP_GELU, 1>, pp_lds<PP_GELU>},
+    {pp_kernel<PP_RESLN3, 1>, pp_lds<PP_RESLN3>},
+};
 
 // path choice: the persistent kernels need enough 256^2 tiles to fill the CUs (one workgroup each); both residual GEMMs
 // have N = 768 and every K is a multiple of 128, so ONE predicate (on the padded token count) decides the path of a pass
@@ -566,9 +579,32 @@ struct PassForm {
   uint32_t* seq_over = nullptr;  // device [rows of the pass], zeroed by the caller: AttnArgs::seq_over
 };
 
+// The attention variants: one row per instantiation of attention_v2_kernel<NKB, NCH, X8, VLO> (padded length = 64 NKB NCH keys, workgroups of 2 NKB waves).
+// launch_attention looks its row up by (padded length, x8, two planes); mv_create opts every row in for its dynamic LDS.
+//   one plane: the whole key range up to 256 (8 waves and <= 128 KiB LDS per CU decide the resident workgroups); 384 / 512 as chunks of 128 keys per (row,
+//     head, 128-query block) through the same ring: 64 score registers per lane, two workgroups of 4 waves per CU, consecutive units of a workgroup are
+//     the query blocks of one head (K / V^T from L2);
+//   two planes (MV_F16X8: padded length <= 128, the safe form at every length): a 64 / 128 KiB ring = two / one workgroup per CU; above 128 keys chunks
+//     through that ring, 192 = 3 chunks of 64 keys (2 waves), 256 / 384 / 512 = 2 / 3 / 4 chunks of 128 (4 waves) — one wave per SIMD either way.
+struct AttnVariant {
+  int Sp; bool x8, two_plane;  // the key: padded length, MV_F16X8, Q / K / V / P as hi + lo planes
+  void (*kernel)(AttnArgs, int);
+  int block, lds;              // threads, dynamic LDS bytes
+  int wg_per_cu, units;        // resident workgroups per CU (the grid: that many per CU, or one per unit if there are fewer); work units per (row, head)
+};
+#define MV_ATT_1P(SP, NKB, NCH, WG)                                                                          \
+  {SP, false, false, attention_v2_kernel<NKB, NCH, 0>, NKB * 128, ATT2_LDS_BYTES(NKB), WG, NCH},             \
+  {SP, true, false, attention_v2_kernel<NKB, NCH, 1>, NKB * 128, ATT2_LDS_BYTES(NKB), WG, NCH}
+#define MV_ATT_2P(SP, NKB, NCH, WG) {SP, true, true, attention_v2_kernel<NKB, NCH, 1, 1>, NKB * 128, ATT2_LDS_BYTES_VLO(NKB), WG, NCH}
+constexpr AttnVariant ATTN_VARIANTS[] = {
+    MV_ATT_1P(64, 1, 1, 4),  MV_ATT_1P(128, 2, 1, 2), MV_ATT_1P(192, 3, 1, 1), MV_ATT_1P(256, 4, 1, 1), MV_ATT_1P(384, 2, 3, 2), MV_ATT_1P(512, 2, 4, 2),
+    MV_ATT_2P(64, 1, 1, 2),  MV_ATT_2P(128, 2, 1, 1), MV_ATT_2P(192, 1, 3, 2), MV_ATT_2P(256, 2, 2, 1), MV_ATT_2P(384, 2, 3, 1), MV_ATT_2P(512, 2, 4, 1),
+};
+#undef MV_ATT_1P
+#undef MV_ATT_2P
+
 int launch_attention(mv_handle* h, Work& wk, const int32_t* d_lens, int B, int Sp, bool x8, bool sp_out = false, const PassForm& pf = PassForm()) {
-  const bool safe = pf.safe;
-  const bool vlo = two_plane_pass(h, x8, safe, Sp);
+  const bool vlo = two_plane_pass(h, x8, pf.safe, Sp);
   AttnArgs a{wk.q, wk.k, wk.vt, d_lens, wk.ctx, Sp, B, x8 ? wk.ctx8 : nullptr, h->x8_sat, vlo ? wk.vt_lo : nullptr,
              vlo ? wk.q_lo : nullptr, vlo ? wk.k_lo : nullptr,
              (x8 && !vlo) ? wk.vlo_sp : nullptr,     // special rows: V of keys 0, 1 as hi + lo (the two-plane short passes carry every key's lo plane)
@@ -576,52 +612,13 @@ int launch_attention(mv_handle* h, Work& wk, const int32_t* d_lens, int B, int S
              sp_out ? h->cls_min_len : 0,               // [CLS]-row form: no lo8 plane of the context for the sequences that take it
              sp_out ? wk.cls_lo : nullptr,
              (x8 && pf.monitor) ? pf.seq_over : nullptr};
+  const AttnVariant* v = nullptr;
+  for (const AttnVariant& r : ATTN_VARIANTS)
+    if (r.Sp == Sp && r.x8 == x8 && r.two_plane == vlo) v = &r;
+  if (!v) return fail(h, MV_ERR_INVALID, "internal: attention at a padded length other than 64 .. 256 / 384 / 512");
+  const int units = B * MV_HEADS * v->units, slots = h->num_cu * v->wg_per_cu;
   ProfScope ps(h, wk.stream, KC_ATTENTION);
-  if (vlo && Sp > 128) {
-    // the safe form above 128 keys: chunks through the two-plane ring.  192 = 3 chunks of 64 keys (2 waves, a 64 KiB ring: two workgroups per CU), 256 / 384 / 512 =
-    // 2 / 3 / 4 chunks of 128 (4 waves, a 128 KiB ring: one workgroup per CU) — one wave per SIMD either way
-    const int nch = Sp == 192 ? 3 : Sp / 128, units = B * MV_HEADS * nch;
-    const int slots = h->num_cu * (Sp == 192 ? 2 : 1);
-    const int grid = units < slots ? units : slots;
-    switch (Sp) {
-      case 192: hipLaunchKernelGGL((attention_v2_kernel<1, 3, 1, 1>), dim3(grid), dim3(128), ATT2_LDS_BYTES_VLO(1), wk.stream, a, units); break;
-      case 256: hipLaunchKernelGGL((attention_v2_kernel<2, 2, 1, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES_VLO(2), wk.stream, a, units); break;
-      case 384: hipLaunchKernelGGL((attention_v2_kernel<2, 3, 1, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES_VLO(2), wk.stream, a, units); break;
-      case 512: hipLaunchKernelGGL((attention_v2_kernel<2, 4, 1, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES_VLO(2), wk.stream, a, units); break;
-      default: return fail(h, MV_ERR_INVALID, "internal: attention at a padded length other than 64 .. 256 / 384 / 512");
-    }
-  } else if (vlo) {
-    const int nkb = Sp / 64, items = B * MV_HEADS;
-    const int slots = h->num_cu * (nkb == 1 ? 2 : 1);  // resident workgroups by LDS: 64 / 128 KiB each
-    const int grid = items < slots ? items : slots;
-    if (nkb == 1) hipLaunchKernelGGL((attention_v2_kernel<1, 1, 1, 1>), dim3(grid), dim3(128), ATT2_LDS_BYTES_VLO(1), wk.stream, a, items);
-    else hipLaunchKernelGGL((attention_v2_kernel<2, 1, 1, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES_VLO(2), wk.stream, a, items);
-  } else if (Sp <= 256) {
-    const int nkb = Sp / 64, items = B * MV_HEADS;
-    const int slots = h->num_cu * (nkb == 1 ? 4 : nkb == 2 ? 2 : 1);  // resident workgroups: 8 waves and <= 128 KiB LDS per CU
-    const int grid = items < slots ? items : slots;
-#define MV_ATT(NKB)                                                                                                              \
-    if (x8) hipLaunchKernelGGL((attention_v2_kernel<NKB, 1, 1>), dim3(grid), dim3(NKB * 128), ATT2_LDS_BYTES(NKB), wk.stream, a, items); \
-    else hipLaunchKernelGGL((attention_v2_kernel<NKB, 1, 0>), dim3(grid), dim3(NKB * 128), ATT2_LDS_BYTES(NKB), wk.stream, a, items)
-    switch (nkb) {
-      case 1: MV_ATT(1); break;
-      case 2: MV_ATT(2); break;
-      case 3: MV_ATT(3); break;
-      default: MV_ATT(4); break;
-    }
-#undef MV_ATT
-  } else if (Sp == 384 || Sp == 512) {
-    // chunks of 128 keys per (row, head, 128-query block) through the same ring: 64 score registers per lane, two
-    // workgroups of 4 waves per CU; consecutive units of a workgroup are the query blocks of one head (K / V^T from L2)
-    const int nch = Sp / 128, units = B * MV_HEADS * nch;
-    const int grid = units < 2 * h->num_cu ? units : 2 * h->num_cu;
-    if (nch == 3 && x8) hipLaunchKernelGGL((attention_v2_kernel<2, 3, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), wk.stream, a, units);
-    else if (nch == 3) hipLaunchKernelGGL((attention_v2_kernel<2, 3, 0>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), wk.stream, a, units);
-    else if (x8) hipLaunchKernelGGL((attention_v2_kernel<2, 4, 1>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), wk.stream, a, units);
-    else hipLaunchKernelGGL((attention_v2_kernel<2, 4, 0>), dim3(grid), dim3(256), ATT2_LDS_BYTES(2), wk.stream, a, units);
-  } else {
-    return fail(h, MV_ERR_INVALID, "internal: attention at a padded length other than 64 .. 256 / 384 / 512");
-  }
+  hipLaunchKernelGGL(v->kernel, dim3(units < slots ? units : slots), dim3(v->block), v->lds, wk.stream, a, units);
   return launch_check(h, "attention");
 }
 
@@ -689,21 +686,14 @@ int encode_f32_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* 
 //   * small passes: one-tile-per-workgroup GEMMs (gemm.h) on an fp32 stream with explicit LayerNorm kernels.
 // The last layer is pruned to the [CLS] rows when the pooler follows (cls_prune); `full` (debug taps) disables that and
 // leaves the normalised fp32 stream of the last layer run in xres.
-int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_lens, int min_len, int B, int S_in, int n_layers, float* u_out,
-               const PassForm& pf = PassForm(), bool full = false, int pitch = 0) {  // min_len: the shortest sequence of the pass as the HOST knows it (Pass::min_len; 0 = unknown)
-  if (pitch <= 0) pitch = S_in;  // ints between the rows of d_ids
-  if (h->f32) return encode_f32_dev(h, wk, d_ids, d_lens, B, S_in, n_layers, u_out, pitch);  // MV_F32: no forms, no monitors, no pruning
-  const mv_config& c = h->cfg;
-  const int Sp = padded_len(S_in);
-  const int64_t M = (int64_t)B * Sp, Mpad = round_up(M, 256);
-  if (S_in > c.max_pos) return fail(h, MV_ERR_INVALID, "sequence longer than max_pos");
-  if (Mpad > h->cap_tokens) return fail(h, MV_ERR_CAPACITY, "B*S exceeds mv_config.max_tokens");
-  if (n_layers < 0 || n_layers > c.layers) n_layers = c.layers;
-  h->dbg_B = B;
-  h->dbg_Sp = Sp;
-  const bool big = pp_selected(h, Mpad);  // persistent GEMMs, raw stream as hi + a low part (x16 = hi; MV_F16: xlo, MV_F16X8: the lo8 plane of x8 + st_lo), virtual LayerNorm
-  const bool x8 = h->precise;             // MV_F16X8: + fp8 correction sweeps (forces the persistent path, pp_selected)
-  const bool prune = !full && h->cls_prune && u_out && n_layers == c.layers && n_layers > 0;
+// One pass: its shape and every decision about it, taken once (encode_dev) and read by the launches below.
+struct PassPlan {
+  int B, S_in, Sp, pitch;  // pitch: ints between the rows of d_ids
+  int64_t M, Mpad;
+  bool big;    // persistent GEMMs, raw stream as hi + a low part (x16 = hi; MV_F16: xlo, MV_F16X8: the lo8 plane of x8 + st_lo), virtual LayerNorm
+  bool x8;     // MV_F16X8: + fp8 correction sweeps (forces the persistent path, pp_selected)
+  bool safe;   // (the form of the planned job, read from the handle when the job was made: work in flight keeps the form it was enqueued with)
+  bool prune;  // the last layer on the [CLS] rows only
   // The [CLS]-row form (mv_handle::cls_aside): every persistent GEMM of this pass sweeps the weight-side correction term only (x8_terms = 1) and the
   // A-side term A_lo W_hi^T is formed for the B [CLS] rows alone: their low parts (2^11 x, fp16) gathered from the operand's lo plane (raw stream) or
   // lo8 plane (context, GELU output), one skinny fp16 GEMM [B x K] x [K x N], and the launch adds the result to those rows' accumulators
@@ -712,232 +702,309 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
   // result stays independent of the batch it travels in.  Passes of padded length 192 / 384 (a tile there spans two sequences, a per-tile rule would mix the
   // forms inside a sequence): the form for the WHOLE pass when its shortest sequence has cls_min_len tokens — what a length-sorted sweep hands over by
   // construction (ModelMemory.sweep / Engine.bucketed_sweep: a pass at 192 holds 129 .. 192 tokens, at 384 257 .. 384) — else the both-terms form for the whole pass.
-  const bool one_seq_tiles = Sp == 256 || Sp == 512;
-  const bool whole_pass = (Sp == 192 || Sp == 384) && min_len >= h->cls_min_len;
-  const bool safe = x8 && pf.safe;  // (the form of the planned job, read from the handle when the job was made: work in flight keeps the form it was enqueued with)
-  const bool cls_as = big && x8 && !safe && h->cls_aside && (one_seq_tiles || whole_pass);
-  const int qkv_mask = safe ? 7 : h->qkv_aside_mask;
-  const bool two_plane = two_plane_pass(h, x8, safe, Sp);
-  if (cls_as && one_seq_tiles) {
-    const int ntile = (int)(Mpad / 256);
-    hipLaunchKernelGGL(cls_tile_flags_kernel, dim3((unsigned)((ntile + 255) / 256)), dim3(256), 0, wk.stream, d_lens, B, Sp, h->cls_min_len, ntile,
-                       wk.tile_both);
-    if (int rc = launch_check(h, "cls_tile_flags")) return rc;
-  }
+  bool cls_as, one_seq_tiles;
   // Special rows (round 6): rows 0 and 1 of every sequence hold its [CLS] and its [SEP] token (embed_ln_kernel swaps the last token into row 1) — the token the
   // pooler reads and the two tokens trained BERT heads use as attention sinks, i.e. the rows whose roundings can reach the pooler un-averaged.  For them every
   // GEMM whose sweep carried the weight-side term only gets the A-side term from a skinny GEMM over the 2 B compact rows the PRODUCER's epilogue left in cls_lo
   // (no gather launch), and attention adds p[:, 0..1] V_lo[0..1].  The K and V blocks of the QKV projection take it in every pass of this compute dtype (they
   // never sweep the A-side term for all rows by default), the other three GEMMs where the [CLS]-row form is in force.
-  const bool special = big && x8;
-  auto row_term = [&](const half_t* A, const half_t* W, int N, int K) -> int {  // cls_corr [2 B][N] = A [2 B][K] W^T (both 2^11 x); A = st_lo (stream) or cls_lo (context, GELU output)
-    ProfScope ps(h, wk.stream, KC_CLS_ROW_TERM);
+  bool special;
+  bool two_plane;  // Q, K, V^T as hi + lo planes (two_plane_pass: launch_attention asks the same predicate)
+  int qkv_mask;    // GemmArgs::x8_aside_mask of the QKV projection
+};
+
+// what every GEMM of the layer stack is given, whatever its kind
+GemmArgs pass_gemm(const mv_handle* h, const Work& wk, const PassPlan& p) {
+  GemmArgs g{};
+  g.M = (int)p.Mpad; g.Mreal = (int)p.M; g.S = p.Sp; g.ln_eps = h->cfg.ln_eps; g.x8_sat = h->x8_sat;
+  g.tile_both = (p.cls_as && p.one_seq_tiles) ? wk.tile_both : nullptr;  // (the whole-pass form: no tile is short)
+  return g;
+}
+
+// The row term of the launch `g` is being built for: cls_corr [2 B][N] = A [2 B][K] W^T (both 2^11 x), A = st_lo (stream) or cls_lo (context, GELU output)
+int row_term(mv_handle* h, Work& wk, const PassPlan& p, const half_t* A, GemmArgs& g) {
+  GemmArgs t{};
+  t.M = (int)round_up(2 * p.B, 64); t.Mreal = 2 * p.B; t.S = 64; t.A = A; t.W = g.W; t.N = g.N; t.K = g.K; t.outf = wk.cls_corr;
+  g.cls_corr = wk.cls_corr;
+  return launch_ring64<EPI_F32>(h, wk.stream, KC_CLS_ROW_TERM, t);
+}
+
+// V of the special rows as hi + lo, for the attention that follows (a two-plane pass carries every key's lo plane instead)
+inline half_t* special_v_lo(const Work& wk, const PassPlan& p) { return (p.special && !p.two_plane) ? wk.vlo_sp : nullptr; }
+
+// K2: Q, K, V^T projection of the stream (persistent path: the raw stream, LayerNorm folded into W'' / b').  kv_only: the K and V blocks alone (the pruned last layer)
+int launch_qkv(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w, bool kv_only) {
+  const size_t col0 = kv_only ? MV_HIDDEN : 0;  // first packed-QKV column of the launch
+  const int cls = kv_only ? KC_GEMM_KV_LAST : KC_GEMM_QKV;
+  GemmArgs g = pass_gemm(h, wk, p);
+  g.A = wk.x16; g.W = (p.big ? w.wqkv_f : w.wqkv) + col0 * MV_HIDDEN; g.bias = (p.big ? w.bqkv_f : w.bqkv) + col0;
+  g.N = 3 * MV_HIDDEN - (int)col0; g.K = MV_HIDDEN; g.col0 = (int)col0;
+  g.q = wk.q; g.k = wk.k; g.vt = wk.vt;
+  if (!p.big) return launch_small<EPI_QKV>(h, wk.stream, cls, g);
+  g.lnstats = wk.lnstats;
+  if (p.x8) { g.A8 = wk.x8; g.W8 = w.wqkv_f8 + col0 * 2 * MV_HIDDEN; g.x8_scale = w.sc_qkv; g.x8_terms = 3; g.x8_aside_mask = p.qkv_mask; }
+  // Q, K, V^T as hi + lo planes: wherever the two-plane attention follows; of the pruned layer only in the safe form, whose single-query attention reads K and
+  // V as hi + lo (the [CLS] query itself is fp32: cls_tail_f32)
+  if (kv_only ? p.safe : p.two_plane) { g.vt_lo = wk.vt_lo; g.q_lo = wk.q_lo; g.k_lo = wk.k_lo; }
+  // x8_terms stays 3 — a block of x8_aside_mask (Q by default) keeps its A-side term for EVERY row; the other blocks take it for the special rows from
+  // the row term (the launch skips it in blocks that swept both terms: gemm_pp.h).  With diffuse attention K and V of one token are one key among S for
+  // every query and the term buys nothing (round 5: model, four draws); with an attention sink on that token they reach every row un-averaged.
+  if (p.special) {
+    const int blocks = kv_only ? 6 : 7;  // the Q / K / V blocks of this launch, as bits of x8_aside_mask
+    if ((p.qkv_mask & blocks) != blocks) { if (int rc = row_term(h, wk, p, wk.st_lo, g)) return rc; }
+    g.vlo_sp = special_v_lo(wk, p);
+  }
+  return launch_pp<PP_QK>(h, wk.stream, cls, g);
+}
+
+// The fields of the two residual GEMMs of the persistent path (K4, K6: N = 768, in place on the raw stream): + bias + LayerNorm(residual) with gamma / beta of
+// the LayerNorm pending on the stream, whose statistics lie in `stats`; the vstats of the new rows go to `stats_out`
+void residual_fields(const Work& wk, const PassPlan& p, GemmArgs& g, const float* stats, float* stats_out, const float* gamma, const float* beta) {
+  g.lnstats = stats; g.lng = gamma; g.lnb = beta; g.lnpart = stats_out; g.out16 = wk.x16; g.out16b = wk.xlo;
+  if (p.x8) { g.out8 = wk.x8; g.x8_terms = p.cls_as ? 1 : 2; }
+  // [CLS]-row form: out8_hi_only stays 0 — the consumers sweep the weight-side term only (the next QKV projection's Q block apart), but the lo8 plane IS the
+  // stream's low part: the next residual GEMM reads it back (gemm.h GemmArgs::out16b).  special: the stream rows' special low parts, read back and rewritten in
+  // place — the operand of the row terms of FFN-1 and of the next QKV projection, in every pass of this compute dtype
+  if (p.special) g.sp_lo_out = wk.st_lo;
+}
+
+// K4: attention output projection + bias + LayerNorm(residual), in place on the stream; persistent path: + vstats of the new rows (wk.lnpart)
+int launch_out_proj(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w, const float* pend_g, const float* pend_b) {
+  GemmArgs g = pass_gemm(h, wk, p);
+  g.A = wk.ctx; g.W = w.wo; g.bias = w.bo; g.N = MV_HIDDEN; g.K = MV_HIDDEN;
+  if (!p.big) { g.xres = wk.xres; return launch_small<EPI_RES>(h, wk.stream, KC_GEMM_OUT, g); }
+  residual_fields(wk, p, g, wk.lnstats, wk.lnpart, pend_g, pend_b);
+  if (p.x8) { g.A8 = wk.ctx8; g.W8 = w.wo8; g.x8_scale = w.sc_o; }
+  if (p.cls_as) { if (int rc = row_term(h, wk, p, wk.cls_lo, g)) return rc; }  // (the context's special low parts: launch_attention)
+  return launch_pp<PP_RESLN3>(h, wk.stream, KC_GEMM_OUT, g);
+}
+
+// K5: FFN-1 + exact-erf GELU
+int launch_ffn1(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w) {
+  GemmArgs g = pass_gemm(h, wk, p);
+  g.A = wk.x16; g.N = MV_INTER; g.K = MV_HIDDEN; g.out16 = wk.h16;
+  if (!p.big) { g.W = w.w1; g.bias = w.b1; return launch_small<EPI_GELU>(h, wk.stream, KC_GEMM_FFN1, g); }
+  g.W = w.w1_f; g.bias = w.b1_f; g.lnstats = wk.lnpart;
+  if (p.x8) { g.A8 = wk.x8; g.W8 = w.w1_f8; g.x8_scale = w.sc_1; g.out8 = wk.h8; g.x8_terms = p.cls_as ? 1 : 2; }
+  if (p.cls_as) {
+    if (int rc = row_term(h, wk, p, wk.st_lo, g)) return rc;
+    g.out8_hi_only = 1;       // h8 is FFN-2's A8: hi8 alone
+    g.sp_lo_out = wk.cls_lo;  // the GELU output's special low parts: FFN-2's row term
+  }
+  return launch_pp<PP_GELU>(h, wk.stream, KC_GEMM_FFN1, g);
+}
+
+// K6: FFN-2 + bias + LayerNorm(residual); persistent path: + vstats of the new rows (wk.lnstats: the next layer's input)
+int launch_ffn2(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w) {
+  GemmArgs g = pass_gemm(h, wk, p);
+  g.A = wk.h16; g.W = w.w2; g.bias = w.b2; g.N = MV_HIDDEN; g.K = MV_INTER;
+  if (!p.big) { g.xres = wk.xres; return launch_small<EPI_RES>(h, wk.stream, KC_GEMM_FFN2, g); }
+  residual_fields(wk, p, g, wk.lnpart, wk.lnstats, w.ln1g, w.ln1b);
+  if (p.x8) { g.A8 = wk.h8; g.W8 = w.w28; g.x8_scale = w.sc_2; }
+  if (p.cls_as) { if (int rc = row_term(h, wk, p, wk.cls_lo, g)) return rc; }
+  return launch_pp<PP_RESLN3>(h, wk.stream, KC_GEMM_FFN2, g);
+}
+
+int run_ln(mv_handle* h, Work& wk, float* x32, half_t* x16, int rows, const float* g, const float* b) {
+  ProfScope ps(h, wk.stream, KC_LN);
+  hipLaunchKernelGGL(ln_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, wk.stream, x32, x16, rows, g, b, h->cfg.ln_eps, (float*)nullptr);
+  return launch_check(h, "layernorm");
+}
+
+// persistent path: two-plane raw stream -> normalised fp32 rows (pooler / debug taps)
+int final_ln(mv_handle* h, Work& wk, const PassPlan& p, const float* g, const float* b) {
+  const size_t n4 = (size_t)p.M * MV_HIDDEN / 4;
+  hipLaunchKernelGGL(hilo_to_f32_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, wk.stream, wk.x16, wk.xlo, n4, wk.xres,
+                     p.special ? (const half_t*)wk.st_lo : (const half_t*)nullptr, p.Sp, (const uint8_t*)wk.x8);
+  if (int rc = launch_check(h, "hilo_to_f32")) return rc;
+  return run_ln(h, wk, wk.xres, wk.x16, (int)p.M, g, b);
+}
+
+// A layer of the persistent path: five launches (+ the row terms; + the sink census).  pend_g / pend_b: gamma / beta of the LayerNorm whose statistics are
+// pending in wk.lnstats (the embedding's, or the previous layer's second one) — the output projection applies it; wk.lnstats = vstats of the layer's input
+// rows, wk.lnpart = of the rows after the output projection; no statistics kernel in between (gemm_pp.h)
+int persistent_layer(mv_handle* h, Work& wk, const PassPlan& p, const PassForm& pf, int l, const int32_t* d_ids, const int32_t* d_lens, const float* pend_g, const float* pend_b) {
+  const LayerW& w = h->L[l];
+  if (int rc = launch_qkv(h, wk, p, w, false)) return rc;
+  // the sink census: the layers whose attention launch feeds the concentration monitor, and only where it is attached (a rescoring pass counts nothing twice)
+  if (h->census && p.x8 && pf.monitor) {
+    ProfScope ps(h, wk.stream, KC_ATTENTION);
+    hipLaunchKernelGGL(sink_census_kernel, dim3((unsigned)((p.B * MV_HEADS + 3) / 4)), dim3(256), 0, wk.stream, (const half_t*)wk.q, (const half_t*)wk.k, d_lens,
+                       d_ids, p.pitch, p.S_in, p.Sp, p.B * MV_HEADS, h->cfg.vocab_size, h->census_items, h->census_share, h->census_heads + (size_t)l * MV_HEADS);
+    if (int rc = launch_check(h, "sink_census")) return rc;
+  }
+  // K3: attention (cls_as: + the context's special rows' low parts for the output projection's row term)
+  if (int rc = launch_attention(h, wk, d_lens, p.B, p.Sp, p.x8, p.cls_as, pf)) return rc;
+  if (int rc = launch_out_proj(h, wk, p, w, pend_g, pend_b)) return rc;
+  if (int rc = launch_ffn1(h, wk, p, w)) return rc;
+  return launch_ffn2(h, wk, p, w);
+}
+
+// A layer of a small pass: fp32 stream, explicit LayerNorm kernels, one-plane MV_F16 attention
+int small_layer(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w, const int32_t* d_lens) {
+  if (int rc = launch_qkv(h, wk, p, w, false)) return rc;
+  if (int rc = launch_attention(h, wk, d_lens, p.B, p.Sp, false)) return rc;
+  if (int rc = launch_out_proj(h, wk, p, w, nullptr, nullptr)) return rc;
+  if (int rc = run_ln(h, wk, wk.xres, wk.x16, (int)p.M, w.ln1g, w.ln1b)) return rc;
+  if (int rc = launch_ffn1(h, wk, p, w)) return rc;
+  if (int rc = launch_ffn2(h, wk, p, w)) return rc;
+  return run_ln(h, wk, wk.xres, wk.x16, (int)p.M, w.ln2g, w.ln2b);
+}
+
+// MV_F16X8: the B [CLS] rows in full fp32 on the fp32-input matrix cores (their operand rounding would reach the pooler un-attenuated): Q projection,
+// single-query attention (fp16 K / V^T of the main path, fp32 context), output projection + residual, LayerNorm, FFN, LayerNorm
+int cls_tail_f32(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w, const int32_t* d_lens, float* u_out) {
+  const int B = p.B;
+  const unsigned gx = (unsigned)((B + 31) / 32);
+  hipLaunchKernelGGL((dense768_kernel<2, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.c32,
+                     (size_t)MV_HIDDEN, B, (const float*)w.wqT32, (const float*)w.bqkv, MV_HIDDEN, wk.cq, (const float*)nullptr);
+  if (int rc = launch_check(h, "cls q")) return rc;
+  const half_t* vlo_sp = special_v_lo(wk, p);
+  if (p.safe)
+    hipLaunchKernelGGL(attention_cls_kernel<true>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt, d_lens, wk.cctx, p.Sp,
+                       B * MV_HEADS, wk.pooled, vlo_sp, (const half_t*)wk.k_lo, (const half_t*)wk.vt_lo);
+  else
+    hipLaunchKernelGGL(attention_cls_kernel<false>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt, d_lens, wk.cctx, p.Sp,
+                       B * MV_HEADS, wk.pooled, vlo_sp, (const half_t*)nullptr, (const half_t*)nullptr);
+  if (int rc = launch_check(h, "attention_cls")) return rc;
+  hipLaunchKernelGGL((dense768_kernel<4, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.pooled,
+                     (size_t)MV_HIDDEN, B, (const float*)w.woT32, (const float*)w.bo, MV_HIDDEN, wk.c32, (const float*)wk.c32);
+  if (int rc = launch_check(h, "cls out")) return rc;
+  if (int rc = run_ln(h, wk, wk.c32, wk.c16, B, w.ln1g, w.ln1b)) return rc;
+  hipLaunchKernelGGL((dense768_kernel<3, MV_HIDDEN>), dim3(gx, MV_INTER / 32), dim3(512), 0, wk.stream, (const float*)wk.c32,
+                     (size_t)MV_HIDDEN, B, (const float*)w.w1T32, (const float*)w.b1, MV_INTER, wk.ch32, (const float*)nullptr);
+  if (int rc = launch_check(h, "cls ffn1")) return rc;
+  hipLaunchKernelGGL((dense768_kernel<4, MV_INTER>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.ch32,
+                     (size_t)MV_INTER, B, (const float*)w.w2T32, (const float*)w.b2, MV_HIDDEN, wk.c32, (const float*)wk.c32);
+  if (int rc = launch_check(h, "cls ffn2")) return rc;
+  if (int rc = run_ln(h, wk, wk.c32, wk.c16, B, w.ln2g, w.ln2b)) return rc;
+  return pool_head(h, wk, wk.c32, MV_HIDDEN, B, u_out);
+}
+
+// MV_F16: the same tail as fp16 skinny GEMMs on an fp32 stream of B rows
+int cls_tail_f16(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w, const int32_t* d_lens, float* u_out) {
+  const int B = p.B;
+  auto skinny = [&](const half_t* A, const half_t* W, const float* bias, int N, int K) {
     GemmArgs t{};
-    t.M = (int)round_up(2 * B, 64); t.Mreal = 2 * B; t.S = 64; t.A = A; t.W = W; t.N = N; t.K = K; t.outf = wk.cls_corr;
-    t.GN = choose_gn(N / 64, 8);
-    hipLaunchKernelGGL((gemm_ring_kernel<EPI_F32, 1, 1, 2, 2, 64, 4, 2>), dim3((unsigned)((t.M / 64) * (N / 64))), dim3(256), RING64_LDS, wk.stream, t);
-    return launch_check(h, "row term gemm_ring");
+    t.M = (int)round_up(B, 128); t.Mreal = B; t.S = 64; t.A = A; t.W = W; t.bias = bias; t.N = N; t.K = K;
+    return t;
   };
-  const unsigned ln_grid = (unsigned)((M + 3) / 4);
+  GemmArgs q = skinny(wk.c16, w.wqkv, w.bqkv, MV_HIDDEN, MV_HIDDEN);
+  q.outf = wk.cq;
+  if (int rc = launch_small<EPI_F32>(h, wk.stream, KC_CLS_TAIL, q)) return rc;
+  hipLaunchKernelGGL(attention_cls_kernel<false>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt,
+                     d_lens, wk.cctx, p.Sp, B * MV_HEADS, (float*)nullptr, (const half_t*)nullptr, (const half_t*)nullptr, (const half_t*)nullptr);
+  if (int rc = launch_check(h, "attention_cls")) return rc;
+  GemmArgs o = skinny(wk.cctx, w.wo, w.bo, MV_HIDDEN, MV_HIDDEN);
+  o.xres = wk.c32;
+  if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_CLS_TAIL, o)) return rc;
+  if (int rc = run_ln(h, wk, wk.c32, wk.c16, B, w.ln1g, w.ln1b)) return rc;
+  GemmArgs f1 = skinny(wk.c16, w.w1, w.b1, MV_INTER, MV_HIDDEN);
+  f1.out16 = wk.ch16;
+  if (int rc = launch_small<EPI_GELU>(h, wk.stream, KC_CLS_TAIL, f1)) return rc;
+  GemmArgs f2 = skinny(wk.ch16, w.w2, w.b2, MV_HIDDEN, MV_INTER);
+  f2.xres = wk.c32;
+  if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_CLS_TAIL, f2)) return rc;
+  if (int rc = run_ln(h, wk, wk.c32, wk.c16, B, w.ln2g, w.ln2b)) return rc;
+  return pool_head(h, wk, wk.c32, MV_HIDDEN, B, u_out);
+}
+
+// The last layer on the [CLS] rows only: K and V of every token, everything else on B rows, down to the embedding
+int pruned_last_layer(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w, const int32_t* d_lens, const float* pend_g, const float* pend_b, float* u_out) {
+  if (int rc = launch_qkv(h, wk, p, w, true)) return rc;
+  ProfScope tail(h, wk.stream, KC_CLS_TAIL);
+  struct Restore { mv_handle* h; uint32_t mask; ~Restore() { h->prof_mask = mask; } } restore{h, h->prof_mask};  // (on every return)
+  h->prof_mask = 0;  // the tail is one profiled span; its inner launches carry no events of their own
+  hipLaunchKernelGGL(cls_gather_kernel, dim3((p.B + 3) / 4), dim3(256), 0, wk.stream, wk.xres, wk.x16, p.Sp, p.B,
+                     p.big ? (const float*)wk.lnstats : (const float*)nullptr, pend_g, pend_b, wk.c32, wk.c16, p.big ? 1 : 0,
+                     (p.big && !p.x8) ? wk.xlo : (const half_t*)nullptr, p.big ? 1 : 0, h->cfg.ln_eps,
+                     p.special ? (const half_t*)wk.st_lo : (const half_t*)nullptr);
+  if (int rc = launch_check(h, "cls_gather")) return rc;
+  return p.x8 ? cls_tail_f32(h, wk, p, w, d_lens, u_out) : cls_tail_f16(h, wk, p, w, d_lens, u_out);
+}
+
+int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_lens, int min_len, int B, int S_in, int n_layers, float* u_out,
+               const PassForm& pf = PassForm(), bool full = false, int pitch = 0) {  // min_len: the shortest sequence of the pass as the HOST knows it (Pass::min_len; 0 = unknown)
+  if (pitch <= 0) pitch = S_in;
+  if (h->f32) return encode_f32_dev(h, wk, d_ids, d_lens, B, S_in, n_layers, u_out, pitch);  // MV_F32: no forms, no monitors, no pruning
+  const mv_config& c = h->cfg;
+  PassPlan p{};
+  p.B = B; p.S_in = S_in; p.Sp = padded_len(S_in); p.pitch = pitch;
+  p.M = (int64_t)B * p.Sp; p.Mpad = round_up(p.M, 256);
+  if (S_in > c.max_pos) return fail(h, MV_ERR_INVALID, "sequence longer than max_pos");
+  if (p.Mpad > h->cap_tokens) return fail(h, MV_ERR_CAPACITY, "B*S exceeds mv_config.max_tokens");
+  if (n_layers < 0 || n_layers > c.layers) n_layers = c.layers;
+  h->dbg_B = B;
+  h->dbg_Sp = p.Sp;
+  p.big = pp_selected(h, p.Mpad);
+  p.x8 = h->precise;
+  p.safe = p.x8 && pf.safe;
+  p.prune = !full && h->cls_prune && u_out && n_layers == c.layers && n_layers > 0;
+  p.one_seq_tiles = p.Sp == 256 || p.Sp == 512;
+  const bool whole_pass = (p.Sp == 192 || p.Sp == 384) && min_len >= h->cls_min_len;
+  p.cls_as = p.big && p.x8 && !p.safe && h->cls_aside && (p.one_seq_tiles || whole_pass);
+  p.special = p.big && p.x8;
+  p.two_plane = two_plane_pass(h, p.x8, p.safe, p.Sp);
+  p.qkv_mask = p.safe ? 7 : h->qkv_aside_mask;
+  const int M = (int)p.M, Sp = p.Sp, ntile = (int)(p.Mpad / 256);
+  if (p.cls_as && p.one_seq_tiles) {
+    hipLaunchKernelGGL(cls_tile_flags_kernel, dim3((unsigned)((ntile + 255) / 256)), dim3(256), 0, wk.stream, d_lens, B, Sp, h->cls_min_len, ntile,
+                       wk.tile_both);
+    if (int rc = launch_check(h, "cls_tile_flags")) return rc;
+  }
   {
     ProfScope ps(h, wk.stream, KC_EMBED_LN);
-    if (big)
-      hipLaunchKernelGGL(embed_ln_kernel<true>, dim3(ln_grid), dim3(256), 0, wk.stream, d_ids, pitch, S_in, Sp, (int)M, c.vocab_size,
+    const unsigned ln_grid = (unsigned)((M + 3) / 4);
+    if (p.big)
+      hipLaunchKernelGGL(embed_ln_kernel<true>, dim3(ln_grid), dim3(256), 0, wk.stream, d_ids, pitch, S_in, Sp, M, c.vocab_size,
                          h->wemb, h->pemb, h->temb, h->embg, h->embb, c.ln_eps, wk.xres, wk.x16, wk.lnstats,
-                         x8 ? (half_t*)nullptr : wk.xlo, x8 ? wk.x8 : (uint8_t*)nullptr, h->x8_sat, special ? d_lens : (const int32_t*)nullptr,
-                         special ? wk.st_lo : (half_t*)nullptr);
+                         p.x8 ? (half_t*)nullptr : wk.xlo, p.x8 ? wk.x8 : (uint8_t*)nullptr, h->x8_sat, p.special ? d_lens : (const int32_t*)nullptr,
+                         p.special ? wk.st_lo : (half_t*)nullptr);
     else
-      hipLaunchKernelGGL(embed_ln_kernel<false>, dim3(ln_grid), dim3(256), 0, wk.stream, d_ids, pitch, S_in, Sp, (int)M, c.vocab_size,
+      hipLaunchKernelGGL(embed_ln_kernel<false>, dim3(ln_grid), dim3(256), 0, wk.stream, d_ids, pitch, S_in, Sp, M, c.vocab_size,
                          h->wemb, h->pemb, h->temb, h->embg, h->embb, c.ln_eps, wk.xres, wk.x16, (float*)nullptr,
                          (half_t*)nullptr, (uint8_t*)nullptr, (unsigned long long*)nullptr);
     if (int rc = launch_check(h, "embed_ln")) return rc;
   }
-  // big: the LayerNorm whose statistics are pending in the vstats buffers — gamma / beta the next residual GEMM applies
+  // persistent path: the LayerNorm whose statistics are pending in the vstats buffers — gamma / beta the next residual GEMM applies
   const float *pend_g = h->embg, *pend_b = h->embb;
-  auto run_ln = [&](float* x32, half_t* x16, int rows, const float* g, const float* b) -> int {
-    ProfScope ps(h, wk.stream, KC_LN);
-    hipLaunchKernelGGL(ln_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, wk.stream, x32, x16, rows, g, b, c.ln_eps,
-                       (float*)nullptr);
-    return launch_check(h, "layernorm");
-  };
-  auto final_ln = [&](const float* g, const float* b) -> int {  // two-plane raw stream -> normalised fp32 rows (pooler / debug taps)
-    const size_t n4 = (size_t)M * MV_HIDDEN / 4;
-    hipLaunchKernelGGL(hilo_to_f32_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, wk.stream, wk.x16, wk.xlo, n4, wk.xres,
-                       special ? (const half_t*)wk.st_lo : (const half_t*)nullptr, Sp, (const uint8_t*)wk.x8);
-    if (int rc = launch_check(h, "hilo_to_f32")) return rc;
-    return run_ln(wk.xres, wk.x16, (int)M, g, b);
-  };
-  if (big && n_layers == 0) { if (int rc = final_ln(h->embg, h->embb)) return rc; }
-  // big: st_in = vstats of the layer's input rows (embedding / previous FFN-2), st_mid = of the rows after the
-  // attention-output projection; no statistics kernel in between (gemm_pp.h)
-  float *st_in = wk.lnstats, *st_mid = wk.lnpart;
+  if (p.big && n_layers == 0) { if (int rc = final_ln(h, wk, p, pend_g, pend_b)) return rc; }
   for (int l = 0; l < n_layers; ++l) {
     const LayerW& w = h->L[l];
     const bool last = (l == n_layers - 1);
-    GemmArgs g{};
-    g.M = (int)Mpad; g.Mreal = (int)M; g.S = Sp; g.ln_eps = c.ln_eps; g.x8_sat = h->x8_sat;
-    g.tile_both = (cls_as && one_seq_tiles) ? wk.tile_both : nullptr;  // (whole_pass: no tile is short)
-    g.q = wk.q; g.k = wk.k; g.vt = wk.vt;
-    const half_t* wqkv = big ? w.wqkv_f : w.wqkv;
-    const float* bqkv = big ? w.bqkv_f : w.bqkv;
-    if (last && prune) {
-      // ---- last layer, [CLS] rows only: K and V of every token, everything else on B rows
-      const int Bp = (int)round_up(B, 128);
-      g.A = wk.x16; g.W = wqkv + (size_t)MV_HIDDEN * MV_HIDDEN; g.bias = bqkv + MV_HIDDEN; g.N = 2 * MV_HIDDEN; g.K = MV_HIDDEN;
-      g.col0 = MV_HIDDEN;
-      if (big) {
-        g.lnstats = st_in;
-        if (x8) { g.A8 = wk.x8; g.W8 = w.wqkv_f8 + (size_t)MV_HIDDEN * 2 * MV_HIDDEN; g.x8_scale = w.sc_qkv; g.x8_terms = 3; g.x8_aside_mask = qkv_mask; }
-        if (special) {  // K and V of the special rows: row term wherever a block sweeps the weight-side term only; V also as hi + lo (the [CLS] query itself is fp32: the tail below)
-          if ((qkv_mask & 6) != 6) {
-            if (int rc = row_term(wk.st_lo, g.W, g.N, g.K)) return rc;
-            g.cls_corr = wk.cls_corr;
-          }
-          g.vlo_sp = two_plane ? nullptr : wk.vlo_sp;
-        }
-        if (safe) { g.vt_lo = wk.vt_lo; g.q_lo = wk.q_lo; g.k_lo = wk.k_lo; }  // the single-query attention below reads K and V as hi + lo
-        if (int rc = launch_pp<PP_QK>(h, wk.stream, KC_GEMM_KV_LAST, g)) return rc;
-      } else if (int rc = launch_small<EPI_QKV>(h, wk.stream, KC_GEMM_KV_LAST, g)) return rc;
-      ProfScope tail(h, wk.stream, KC_CLS_TAIL);
-      const uint32_t keep_mask = h->prof_mask;
-      h->prof_mask = 0;  // the tail is one profiled span; its inner launches carry no events of their own
-      auto tail_rc = [&]() -> int {
-        hipLaunchKernelGGL(cls_gather_kernel, dim3((B + 3) / 4), dim3(256), 0, wk.stream, wk.xres, wk.x16, Sp, B,
-                           big ? st_in : (const float*)nullptr, pend_g, pend_b, wk.c32, wk.c16, big ? 1 : 0,
-                           (big && !x8) ? wk.xlo : (const half_t*)nullptr, big ? 1 : 0, c.ln_eps, special ? (const half_t*)wk.st_lo : (const half_t*)nullptr);
-        if (int rc = launch_check(h, "cls_gather")) return rc;
-        if (x8) {
-          // MV_F16X8: the B [CLS] rows in full fp32 on the fp32-input matrix cores (their operand rounding would reach the
-          // pooler un-attenuated): Q projection, single-query attention (fp16 K / V^T of the main path, fp32 context), output
-          // projection + residual, LayerNorm, FFN, LayerNorm — the fp16 skinny GEMMs below are MV_F16's tail
-          const unsigned gx = (unsigned)((B + 31) / 32);
-          hipLaunchKernelGGL((dense768_kernel<2, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.c32,
-                             (size_t)MV_HIDDEN, B, (const float*)w.wqT32, (const float*)w.bqkv, MV_HIDDEN, wk.cq, (const float*)nullptr);
-          if (int rc = launch_check(h, "cls q")) return rc;
-          if (safe)
-            hipLaunchKernelGGL(attention_cls_kernel<true>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt, d_lens, wk.cctx, Sp,
-                               B * MV_HEADS, wk.pooled, (const half_t*)g.vlo_sp, (const half_t*)wk.k_lo, (const half_t*)wk.vt_lo);
-          else
-            hipLaunchKernelGGL(attention_cls_kernel<false>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt, d_lens, wk.cctx, Sp,
-                               B * MV_HEADS, wk.pooled, (const half_t*)g.vlo_sp, (const half_t*)nullptr, (const half_t*)nullptr);
-          if (int rc = launch_check(h, "attention_cls")) return rc;
-          hipLaunchKernelGGL((dense768_kernel<4, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.pooled,
-                             (size_t)MV_HIDDEN, B, (const float*)w.woT32, (const float*)w.bo, MV_HIDDEN, wk.c32, (const float*)wk.c32);
-          if (int rc = launch_check(h, "cls out")) return rc;
-          if (int rc = run_ln(wk.c32, wk.c16, B, w.ln1g, w.ln1b)) return rc;
-          hipLaunchKernelGGL((dense768_kernel<3, MV_HIDDEN>), dim3(gx, MV_INTER / 32), dim3(512), 0, wk.stream, (const float*)wk.c32,
-                             (size_t)MV_HIDDEN, B, (const float*)w.w1T32, (const float*)w.b1, MV_INTER, wk.ch32, (const float*)nullptr);
-          if (int rc = launch_check(h, "cls ffn1")) return rc;
-          hipLaunchKernelGGL((dense768_kernel<4, MV_INTER>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.ch32,
-                             (size_t)MV_INTER, B, (const float*)w.w2T32, (const float*)w.b2, MV_HIDDEN, wk.c32, (const float*)wk.c32);
-          if (int rc = launch_check(h, "cls ffn2")) return rc;
-          if (int rc = run_ln(wk.c32, wk.c16, B, w.ln2g, w.ln2b)) return rc;
-          return pool_head(h, wk, wk.c32, MV_HIDDEN, B, u_out);
-        }
-        GemmArgs t{};
-        t.M = Bp; t.Mreal = B; t.S = 64;
-        t.A = wk.c16; t.W = w.wqkv; t.bias = w.bqkv; t.N = MV_HIDDEN; t.K = MV_HIDDEN; t.outf = wk.cq;
-        if (int rc = launch_small<EPI_F32>(h, wk.stream, KC_CLS_TAIL, t)) return rc;
-        hipLaunchKernelGGL(attention_cls_kernel<false>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt,
-                           d_lens, wk.cctx, Sp, B * MV_HEADS, (float*)nullptr, (const half_t*)nullptr, (const half_t*)nullptr, (const half_t*)nullptr);
-        if (int rc = launch_check(h, "attention_cls")) return rc;
-        t.A = wk.cctx; t.W = w.wo; t.bias = w.bo; t.N = MV_HIDDEN; t.K = MV_HIDDEN; t.xres = wk.c32; t.outf = nullptr;
-        if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_CLS_TAIL, t)) return rc;
-        if (int rc = run_ln(wk.c32, wk.c16, B, w.ln1g, w.ln1b)) return rc;
-        t.A = wk.c16; t.W = w.w1; t.bias = w.b1; t.N = MV_INTER; t.K = MV_HIDDEN; t.out16 = wk.ch16;
-        if (int rc = launch_small<EPI_GELU>(h, wk.stream, KC_CLS_TAIL, t)) return rc;
-        t.A = wk.ch16; t.W = w.w2; t.bias = w.b2; t.N = MV_HIDDEN; t.K = MV_INTER; t.xres = wk.c32;
-        if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_CLS_TAIL, t)) return rc;
-        if (int rc = run_ln(wk.c32, wk.c16, B, w.ln2g, w.ln2b)) return rc;
-        return pool_head(h, wk, wk.c32, MV_HIDDEN, B, u_out);
-      }();
-      h->prof_mask = keep_mask;
-      return tail_rc;
-    }
-    if (big) {
-      // K2: Q, K, V^T projection of the raw stream (LayerNorm folded into W'' / b')
-      g.A = wk.x16; g.W = wqkv; g.bias = bqkv; g.N = 3 * MV_HIDDEN; g.K = MV_HIDDEN; g.lnstats = st_in;
-      if (x8) { g.A8 = wk.x8; g.W8 = w.wqkv_f8; g.x8_scale = w.sc_qkv; g.x8_terms = 3; g.x8_aside_mask = qkv_mask; }
-      g.vt_lo = two_plane ? wk.vt_lo : nullptr;  // short passes (the safe form: every pass): Q, K, V^T as hi + lo planes (launch_attention: the same predicate)
-      g.q_lo = wk.q_lo; g.k_lo = wk.k_lo;
-      // x8_terms stays 3 — a block of x8_aside_mask (Q by default) keeps its A-side term for EVERY row; the other blocks take it for the special rows from
-      // the row term (the launch skips it in blocks that swept both terms: gemm_pp.h).  With diffuse attention K and V of one token are one key among S for
-      // every query and the term buys nothing (round 5: model, four draws); with an attention sink on that token they reach every row un-averaged.
-      if (special) {
-        if (qkv_mask != 7) {
-          if (int rc = row_term(wk.st_lo, g.W, g.N, g.K)) return rc;
-          g.cls_corr = wk.cls_corr;
-        }
-        g.vlo_sp = g.vt_lo ? nullptr : wk.vlo_sp;
-      }
-      if (int rc = launch_pp<PP_QK>(h, wk.stream, KC_GEMM_QKV, g)) return rc;
-      g.cls_corr = nullptr; g.vlo_sp = nullptr;
-      // the sink census: the layers whose attention launch feeds the concentration monitor, and only where it is attached (a rescoring pass counts nothing twice)
-      if (h->census && x8 && pf.monitor) {
-        ProfScope ps(h, wk.stream, KC_ATTENTION);
-        hipLaunchKernelGGL(sink_census_kernel, dim3((unsigned)((B * MV_HEADS + 3) / 4)), dim3(256), 0, wk.stream, (const half_t*)wk.q, (const half_t*)wk.k, d_lens,
-                           d_ids, pitch, S_in, Sp, B * MV_HEADS, c.vocab_size, h->census_items, h->census_share, h->census_heads + (size_t)l * MV_HEADS);
-        if (int rc = launch_check(h, "sink_census")) return rc;
-      }
-      // K3: attention (cls_as: + the context's special rows' low parts for the output projection's row term)
-      if (int rc = launch_attention(h, wk, d_lens, B, Sp, x8, cls_as, pf)) return rc;
-      // K4: attention output projection + bias + LayerNorm(residual), in place on the raw stream; + vstats of the new rows
-      g.A = wk.ctx; g.W = w.wo; g.bias = w.bo; g.N = MV_HIDDEN; g.K = MV_HIDDEN;
-      g.lnstats = st_in; g.lng = pend_g; g.lnb = pend_b; g.lnpart = st_mid; g.out16 = wk.x16; g.out16b = wk.xlo;
-      if (x8) { g.A8 = wk.ctx8; g.W8 = w.wo8; g.x8_scale = w.sc_o; g.out8 = wk.x8; g.x8_terms = 2; }
-      if (cls_as) {
-        if (int rc = row_term(wk.cls_lo, g.W, g.N, g.K)) return rc;  // (the context's special low parts: launch_attention)
-        g.cls_corr = wk.cls_corr; g.x8_terms = 1;  // (cls_corr stays set for the rest of the layer: every GEMM's term goes through the same buffer)
-        g.out8_hi_only = 0;  // FFN-1 sweeps the weight-side term only (hi8), but the lo8 plane IS the stream's low part: FFN-2 reads it back (gemm.h GemmArgs::out16b)
-      }
-      if (special) g.sp_lo_out = wk.st_lo;  // the stream rows' special low parts, read back and rewritten in place: FFN-1's row term, and FFN-2's residual
-      if (int rc = launch_pp<PP_RESLN3>(h, wk.stream, KC_GEMM_OUT, g)) return rc;
-      pend_g = w.ln1g; pend_b = w.ln1b;
-      // K5: FFN-1 + exact-erf GELU
-      g.A = wk.x16; g.W = w.w1_f; g.bias = w.b1_f; g.N = MV_INTER; g.K = MV_HIDDEN; g.lnstats = st_mid; g.out16 = wk.h16;
-      g.out16b = nullptr; g.lnpart = nullptr; g.sp_lo_out = nullptr;
-      if (x8) { g.A8 = wk.x8; g.W8 = w.w1_f8; g.x8_scale = w.sc_1; g.out8 = wk.h8; g.x8_terms = 2; }
-      if (cls_as) {
-        if (int rc = row_term(wk.st_lo, g.W, g.N, g.K)) return rc;
-        g.x8_terms = 1;
-        g.out8_hi_only = 1;  // h8 is FFN-2's A8: hi8 alone
-        g.sp_lo_out = wk.cls_lo;  // the GELU output's special low parts: FFN-2's row term
-      }
-      if (int rc = launch_pp<PP_GELU>(h, wk.stream, KC_GEMM_FFN1, g)) return rc;
-      // K6: FFN-2 + bias + LayerNorm(residual)
-      g.A = wk.h16; g.W = w.w2; g.bias = w.b2; g.N = MV_HIDDEN; g.K = MV_INTER;
-      g.lnstats = st_mid; g.lng = pend_g; g.lnb = pend_b; g.lnpart = st_in; g.out16 = wk.x16; g.out16b = wk.xlo;
-      if (x8) { g.A8 = wk.h8; g.W8 = w.w28; g.x8_scale = w.sc_2; g.out8 = wk.x8; g.x8_terms = 2; }
-      if (cls_as) {
-        if (int rc = row_term(wk.cls_lo, g.W, g.N, g.K)) return rc;
-        g.x8_terms = 1;
-        g.out8_hi_only = 0;  // the lo8 plane is the stream's low part as well as the A-side operand of the next QKV projection's Q block
-      } else {
-        g.cls_corr = nullptr;
-      }
-      if (special) g.sp_lo_out = wk.st_lo;  // the next layer's QKV row term reads the new stream rows' special low parts in every pass of this compute dtype
-      if (int rc = launch_pp<PP_RESLN3>(h, wk.stream, KC_GEMM_FFN2, g)) return rc;
-      pend_g = w.ln2g; pend_b = w.ln2b;
-      if (last) { if (int rc = final_ln(w.ln2g, w.ln2b)) return rc; }  // the pooler reads a normalised stream
-    } else {
-      g.A = wk.x16; g.W = wqkv; g.bias = bqkv; g.N = 3 * MV_HIDDEN; g.K = MV_HIDDEN;
-      if (int rc = launch_small<EPI_QKV>(h, wk.stream, KC_GEMM_QKV, g)) return rc;
-      if (int rc = launch_attention(h, wk, d_lens, B, Sp, false)) return rc;
-      g.A = wk.ctx; g.W = w.wo; g.bias = w.bo; g.N = MV_HIDDEN; g.K = MV_HIDDEN; g.xres = wk.xres;
-      if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_GEMM_OUT, g)) return rc;
-      if (int rc = run_ln(wk.xres, wk.x16, (int)M, w.ln1g, w.ln1b)) return rc;
-      g.A = wk.x16; g.W = w.w1; g.bias = w.b1; g.N = MV_INTER; g.K = MV_HIDDEN; g.out16 = wk.h16;
-      if (int rc = launch_small<EPI_GELU>(h, wk.stream, KC_GEMM_FFN1, g)) return rc;
-      g.A = wk.h16; g.W = w.w2; g.bias = w.b2; g.N = MV_HIDDEN; g.K = MV_INTER; g.xres = wk.xres;
-      if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_GEMM_FFN2, g)) return rc;
-      if (int rc = run_ln(wk.xres, wk.x16, (int)M, w.ln2g, w.ln2b)) return rc;
-    }
+    if (last && p.prune) return pruned_last_layer(h, wk, p, w, d_lens, pend_g, pend_b, u_out);
+    if (int rc = p.big ? persistent_layer(h, wk, p, pf, l, d_ids, d_lens, pend_g, pend_b) : small_layer(h, wk, p, w, d_lens)) return rc;
+    if (!p.big) continue;
+    pend_g = w.ln2g; pend_b = w.ln2b;
+    if (last) { if (int rc = final_ln(h, wk, p, pend_g, pend_b)) return rc; }  // the pooler reads a normalised stream
   }
   if (u_out) {
     ProfScope ps(h, wk.stream, KC_POOL_HEAD);
     if (int rc = pool_head(h, wk, wk.xres, (size_t)Sp * MV_HIDDEN, B, u_out)) return rc;
   }
   return MV_OK;
+}
+
+// The mv_test_gemm* hooks: one warm-up / correctness launch, `iters` launches between two events, a synchronise; *ms = the time per launch, the status = the
+// first error (the events are destroyed on every path)
+template <typename Run>
+int timed_launches(mv_handle* h, hipStream_t s0, int iters, float* ms, const char* what, Run run) {
+  if (iters < 1) iters = 1;
+  hipEvent_t e0, e1;
+  hipEventCreate(&e0); hipEventCreate(&e1);
+  int rc = run();
+  if (rc == MV_OK) {
+    hipEventRecord(e0, s0);
+    for (int i = 0; i < iters && rc == MV_OK; ++i) rc = run();
+    hipEventRecord(e1, s0);
+  }
+  const hipError_t se = hipStreamSynchronize(s0);
+  float t = 0.f;
+  hipEventElapsedTime(&t, e0, e1);
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  if (ms) *ms = t / (float)iters;
+  if (rc == MV_OK && se != hipSuccess) rc = fail(h, MV_ERR_HIP, std::string(what) + ": " + hipGetErrorString(se));
+  return rc;
 }
 
 // largest batch one encoder pass can take at padded length Sp
@@ -1716,28 +1783,9 @@ int mv_create(int device, const mv_config* cfg, mv_handle** out) try {
       return MV_ERR_HIP;  // the guard destroys the handle
     }
   }
-  // dynamic LDS above 64 KiB needs an explicit opt-in — per device, so here and not behind a process-wide flag
-  hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI_F32, 1, 1, 2, 2, 64, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, RING64_LDS);
-  hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI_QKV, 1, 1, 2, 2, 64, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, RING64_LDS);
-  hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI_GELU, 1, 1, 2, 2, 64, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, RING64_LDS);
-  hipFuncSetAttribute((const void*)gemm_ring_kernel<EPI_RES, 1, 1, 2, 2, 64, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, RING64_LDS);
-  hipFuncSetAttribute((const void*)gemm_pp_kernel<PP_QK, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES_RAW);
-  hipFuncSetAttribute((const void*)gemm_pp_kernel<PP_GELU, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES_RAW);
-  hipFuncSetAttribute((const void*)gemm_pp_kernel<PP_RESLN3, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES);
-  hipFuncSetAttribute((const void*)gemm_pp_kernel<PP_QK, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES_RAW);
-  hipFuncSetAttribute((const void*)gemm_pp_kernel<PP_GELU, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES_RAW);
-  hipFuncSetAttribute((const void*)gemm_pp_kernel<PP_RESLN3, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES);
-#define MV_ATT_ATTR(NKB, NCH)                                                                                                     \
-  hipFuncSetAttribute((const void*)attention_v2_kernel<NKB, NCH, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES(NKB)); \
-  hipFuncSetAttribute((const void*)attention_v2_kernel<NKB, NCH, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES(NKB))
-  MV_ATT_ATTR(1, 1); MV_ATT_ATTR(2, 1); MV_ATT_ATTR(3, 1); MV_ATT_ATTR(4, 1); MV_ATT_ATTR(2, 3); MV_ATT_ATTR(2, 4);
-#undef MV_ATT_ATTR
-  hipFuncSetAttribute((const void*)attention_v2_kernel<1, 1, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(1));
-  hipFuncSetAttribute((const void*)attention_v2_kernel<2, 1, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(2));
-  hipFuncSetAttribute((const void*)attention_v2_kernel<1, 3, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(1));  // the safe form above 128 keys
-  hipFuncSetAttribute((const void*)attention_v2_kernel<2, 2, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(2));
-  hipFuncSetAttribute((const void*)attention_v2_kernel<2, 3, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(2));
-  hipFuncSetAttribute((const void*)attention_v2_kernel<2, 4, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES_VLO(2));
+  // dynamic LDS above 64 KiB needs an explicit opt-in — per device, so here and not behind a process-wide flag: every kernel of the two lists the launchers read
+  for (const GemmLdsOptIn& k : GEMM_LDS_OPT_INS) hipFuncSetAttribute((const void*)k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
+  for (const AttnVariant& v : ATTN_VARIANTS) hipFuncSetAttribute((const void*)v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds);
   (void)hipGetLastError();
   if (!env_flag("MEMVUL_CLS_PRUNE", &h->cls_prune)) return MV_ERR_INVALID;
   if (const char* e = getenv("MEMVUL_QKV_ASIDE")) {
@@ -2875,26 +2923,9 @@ int mv_test_gemm(mv_handle* h, int variant, int M, int N, int K, const uint16_t*
   if (bias) HIPCHK(h, hipMemcpyAsync(dB, bias, (size_t)N * 4, hipMemcpyHostToDevice, s0));
   GemmArgs g{};
   g.A = dA; g.W = dW; g.bias = dB; g.M = M; g.Mreal = M; g.N = N; g.K = K; g.outf = dC; g.S = 64;
-  if (iters < 1) iters = 1;
-  hipEvent_t e0, e1;
-  hipEventCreate(&e0);
-  hipEventCreate(&e1);
-  auto run = [&]() -> int { return variant == 0 ? launch_gemm128<EPI_F32>(h, s0, KC_TEST_GEMM, g) : launch_ring64<EPI_F32>(h, s0, KC_TEST_GEMM, g); };
-  rc = run();  // warm-up / correctness launch
-  if (rc == MV_OK) {
-    hipEventRecord(e0, s0);
-    for (int i = 0; i < iters && rc == MV_OK; ++i) rc = run();
-    hipEventRecord(e1, s0);
-  }
-  hipError_t se = hipStreamSynchronize(s0);
-  float t = 0.f;
-  hipEventElapsedTime(&t, e0, e1);
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  if (ms) *ms = t / (float)iters;
-  if (rc == MV_OK && se != hipSuccess) rc = fail(h, MV_ERR_HIP, std::string("test gemm: ") + hipGetErrorString(se));
+  rc = timed_launches(h, s0, iters, ms, "test gemm", [&]() -> int { return variant == 0 ? launch_gemm128<EPI_F32>(h, s0, KC_TEST_GEMM, g) : launch_ring64<EPI_F32>(h, s0, KC_TEST_GEMM, g); });
   if (rc == MV_OK && C) {
-    se = hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost);
+    hipError_t se = hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost);
     if (se != hipSuccess) rc = fail(h, MV_ERR_HIP, std::string("test gemm copy: ") + hipGetErrorString(se));
   }
   dev_free(h, dA); dev_free(h, dW); dev_free(h, dB); dev_free(h, dC);
@@ -2920,10 +2951,6 @@ int mv_test_gemm_f32(mv_handle* h, int act, int M, int N, int K, const float* A,
   HIPCHK(h, hipMemcpyAsync(dW, W, (size_t)N * K * 4, hipMemcpyHostToDevice, s0));
   if (bias) HIPCHK(h, hipMemcpyAsync(dB, bias, (size_t)N * 4, hipMemcpyHostToDevice, s0));
   if (res) HIPCHK(h, hipMemcpyAsync(dR, res, (size_t)M * N * 4, hipMemcpyHostToDevice, s0));
-  if (iters < 1) iters = 1;
-  hipEvent_t e0, e1;
-  hipEventCreate(&e0);
-  hipEventCreate(&e1);
   auto run = [&]() -> int {
     switch (act) {
       case RF_ACT_GELU: return launch_gemm_f32<RF_ACT_GELU>(h, s0, KC_TEST_GEMM, dA, dW, dB, nullptr, dC, M, N, K);
@@ -2931,21 +2958,9 @@ int mv_test_gemm_f32(mv_handle* h, int act, int M, int N, int K, const float* A,
       default: return launch_gemm_f32<RF_ACT_NONE>(h, s0, KC_TEST_GEMM, dA, dW, dB, nullptr, dC, M, N, K);
     }
   };
-  rc = run();  // warm-up / correctness launch
-  if (rc == MV_OK) {
-    hipEventRecord(e0, s0);
-    for (int i = 0; i < iters && rc == MV_OK; ++i) rc = run();
-    hipEventRecord(e1, s0);
-  }
-  hipError_t se = hipStreamSynchronize(s0);
-  float t = 0.f;
-  hipEventElapsedTime(&t, e0, e1);
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  if (ms) *ms = t / (float)iters;
-  if (rc == MV_OK && se != hipSuccess) rc = fail(h, MV_ERR_HIP, std::string("test gemm_f32: ") + hipGetErrorString(se));
+  rc = timed_launches(h, s0, iters, ms, "test gemm_f32", run);
   if (rc == MV_OK && C) {
-    se = hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost);
+    hipError_t se = hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost);
     if (se != hipSuccess) rc = fail(h, MV_ERR_HIP, std::string("test gemm_f32 copy: ") + hipGetErrorString(se));
   }
   dev_free(h, dA); dev_free(h, dW); dev_free(h, dB); dev_free(h, dR); dev_free(h, dC);
@@ -3006,25 +3021,9 @@ int mv_test_gemm_pp(mv_handle* h, int x8, int M, int N, int K, const float* A, c
     g.A8 = dA8; g.W8 = dW8; g.out8 = dO8; g.x8_scale = scale_word;
     g.x8_terms = (x8 == 2) ? 1 : 2;  // x8 = 2: the weight-side term only (the QKV projection's form)
   }
-  if (iters < 1) iters = 1;
-  hipEvent_t e0, e1;
-  hipEventCreate(&e0);
-  hipEventCreate(&e1);
-  rc = launch_pp<PP_GELU>(h, s0, KC_TEST_GEMM, g);
+  rc = timed_launches(h, s0, iters, ms, "test gemm_pp", [&]() -> int { return launch_pp<PP_GELU>(h, s0, KC_TEST_GEMM, g); });
   if (rc == MV_OK) {
-    hipEventRecord(e0, s0);
-    for (int i = 0; i < iters && rc == MV_OK; ++i) rc = launch_pp<PP_GELU>(h, s0, KC_TEST_GEMM, g);
-    hipEventRecord(e1, s0);
-  }
-  hipError_t se = hipStreamSynchronize(s0);
-  float t = 0.f;
-  hipEventElapsedTime(&t, e0, e1);
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  if (ms) *ms = t / (float)iters;
-  if (rc == MV_OK && se != hipSuccess) rc = fail(h, MV_ERR_HIP, std::string("test gemm_pp: ") + hipGetErrorString(se));
-  if (rc == MV_OK) {
-    se = hipMemcpy(out16, dO, (size_t)M * N * 2, hipMemcpyDeviceToHost);
+    hipError_t se = hipMemcpy(out16, dO, (size_t)M * N * 2, hipMemcpyDeviceToHost);
     if (se == hipSuccess && x8 && out8) se = hipMemcpy(out8, dO8, (size_t)M * 2 * N, hipMemcpyDeviceToHost);
     if (se != hipSuccess) rc = fail(h, MV_ERR_HIP, std::string("test gemm_pp copy: ") + hipGetErrorString(se));
   }

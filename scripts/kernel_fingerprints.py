@@ -1,0 +1,49 @@
+"""Per-kernel fingerprints of the library's device code (memvul_amd/build.py kernel_fingerprints): print them, write them, or compare them with a
+recorded map.
+
+  python scripts/kernel_fingerprints.py [--dev] [--lib FILE.so] [--out FILE.json] [--against FILE.json]
+
+--against lists the symbols that were added, removed or changed and exits 1 if there are any: a host-only edit of engine.hip must report none, for the
+product and for the development build (profiles/kernel_fingerprints*.json hold the maps of the tree as committed)."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from memvul_amd import build  # noqa: E402
+
+
+def diff(old: dict, new: dict) -> list:
+    lines = ["added   " + k for k in sorted(set(new) - set(old))]
+    lines += ["removed " + k for k in sorted(set(old) - set(new))]
+    lines += ["changed " + k for k in sorted(set(old) & set(new)) if old[k] != new[k]]
+    return lines
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--dev", action="store_true", help="the development build (libmemvul_hip_dev.so)")
+    ap.add_argument("--lib", help="another library file")
+    ap.add_argument("--against", help="a map written by --out: compare, exit 1 on any difference")
+    ap.add_argument("--out", help="write the map here instead of printing it")
+    a = ap.parse_args(argv)
+    fp = build.kernel_fingerprints(a.lib or (build.LIB_PATH_DEV if a.dev else build.LIB_PATH))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(fp, f, indent=0, sort_keys=True)
+            f.write("\n")
+    elif not a.against:
+        json.dump(fp, sys.stdout, indent=0, sort_keys=True)
+        print()
+    if a.against:
+        with open(a.against) as f:
+            lines = diff(json.load(f), fp)
+        print("\n".join(lines) if lines else f"{len(fp)} symbols, no difference")
+        return 1 if lines else 0
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -54,7 +54,7 @@ def two_plane(engine, Sp):
 
 
 def chunk_keys(Sp, planes2):
-    """Keys per chunk of the online softmax (engine.hip launch_attention): one-plane passes hold the whole key range up to 256 and walk chunks of 128 at 384 / 512;
+    """Keys per chunk of the online softmax (engine.hip ATTN_VARIANTS, the table launch_attention reads): one-plane passes hold the whole key range up to 256 and walk chunks of 128 at 384 / 512;
     the two-plane ring holds it up to 128, walks chunks of 64 at 192 and of 128 above."""
     if planes2:
         return Sp if Sp <= 128 else 64 if Sp == 192 else 128

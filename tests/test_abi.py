@@ -75,9 +75,25 @@ def test_no_cpp_exception_can_cross_the_abi():
     assert block.count("catch (...) { return on_exception(") == sum(1 for _, _, guard, _ in heads if guard)
 
 
+def test_kernel_fingerprints_do_not_depend_on_the_build_or_the_layout(lib):
+    """build.kernel_fingerprints hashes the device code kernel by kernel: the product and the development build of one tree differ in host code only, so their
+    maps are equal (their `dev` hashes need not be); every kernel has its descriptor in the map; reading one file twice gives one map."""
+    from memvul_amd import build
+
+    build.build(verbose=False, dev=True)
+    fp = build.kernel_fingerprints()
+    assert fp and fp == build.kernel_fingerprints(build.LIB_PATH_DEV)
+    assert fp == build.kernel_fingerprints(build.LIB_PATH)
+    kernels = [name for co in build.device_code_objects() for name, typ, bind, _ in build.code_object_symbols(co)
+               if typ == build.STT_FUNC and bind == build.STB_GLOBAL]  # -fno-gpu-rdc: the only functions visible outside the code object are the __global__ ones
+    assert kernels and all(k in fp and k + ".kd" in fp for k in kernels)
+    assert sum(k.endswith(".kd") for k in fp) == len(kernels)
+
+
 def test_stamp_carries_the_device_code_fingerprint(lib):
     """bench.py keys the counter figures of profiles/pmc_current.json on the stamp's `dev` line = sha256 of the gfx950 code
-    object inside the .so: it must describe the binary next to it, and the committed counter file must be readable."""
+    object inside the .so: it must describe the binary next to it, and the committed counter file must be readable.  (A host-only edit of engine.hip leaves
+    the kernels unchanged — build.kernel_fingerprints — but the `dev` line may move with the order in which the host code first uses them.)"""
     import json
 
     import bench
