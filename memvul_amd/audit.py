@@ -73,7 +73,7 @@ def sample_rows(lens, n: Optional[int]) -> np.ndarray:
     return np.sort(order[pick])
 
 
-def _padded_len(n: int) -> int:  # engine.hip padded_len
+def _padded_len(n: int) -> int:  # encoder_pass.h padded_len
     n = max(int(n), 1)
     return (n + 63) // 64 * 64 if n <= 256 else (n + 127) // 128 * 128
 

@@ -13,11 +13,14 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmemvul_hip.so")
 # the same sources with -DMEMVUL_DEV_SWITCHES: the development A/B knobs (MEMVUL_GEMM_TILE, MEMVUL_SHORT_VLO, MEMVUL_RASTER, MEMVUL_GN_MAX,
-# MEMVUL_NUM_CU; engine.hip mv_create) exist only in this build — GPU tests that force a kernel path at test sizes and the A/B scripts load it
+# MEMVUL_NUM_CU; engine.hip read_switches) exist only in this build — GPU tests that force a kernel path at test sizes and the A/B scripts load it
 LIB_PATH_DEV = os.path.join(LIB_DIR, "libmemvul_hip_dev.so")
 DEV_FLAGS = ("-DMEMVUL_DEV_SWITCHES",)
 SOURCES = ["engine.hip"]
-HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", "wordpiece.h", os.path.join(ROOT, "include", "memvul_hip.h")]
+KERNEL_HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", "wordpiece.h"]
+# the host code of the library: engine.hip includes each of these parts once, in this order
+HOST_PARTS = ["host_base.h", "weights.h", "workspace.h", "encoder_pass.h", "batch_flow.h", "corpus.h", "comm.h", "records_format.h", "tokenizer_object.h"]
+HEADERS = KERNEL_HEADERS + HOST_PARTS + [os.path.join(ROOT, "include", "memvul_hip.h")]
 ARCH = "gfx950"
 
 
@@ -102,7 +105,7 @@ def device_code_objects(lib_path: str = None) -> list:
 
 def device_code_fingerprint(lib_path: str = None) -> str:
     """sha256 of the gfx950 code object(s) embedded in the shared library: what the GPU executes.  Any kernel change moves it — bench.py keys the counter
-    figures of profiles/pmc_current.json on this line of the stamp.  A host-only edit of engine.hip leaves the KERNELS unchanged (kernel_fingerprints
+    figures of profiles/pmc_current.json on this line of the stamp.  A host-only edit of engine.hip or of a part it includes leaves the KERNELS unchanged (kernel_fingerprints
     below compares them one by one), but this hash — the stamp's `dev` line — may still move: the kernels are laid out in the code object in the order
     in which the host code first uses them."""
     import hashlib
@@ -165,7 +168,7 @@ def kernel_fingerprints(lib_path: str = None) -> dict:
     """The device code of the library kernel by kernel: {symbol: sha256}, for every function (its instruction bytes) and every kernel descriptor
     `<kernel>.kd` (its 64 bytes with bytes 16 .. 23 zeroed: the offset from the descriptor to the kernel's entry, the one field that depends on where
     the kernel lies in the code object).  Unlike device_code_fingerprint it does not move with the ORDER of the kernels, so it is equal before and
-    after a host-only edit of engine.hip, and between the product and the development build of one tree.  No external tool is called (a GPU box may have
+    after a host-only edit of engine.hip or its parts, and between the product and the development build of one tree.  No external tool is called (a GPU box may have
     none)."""
     import hashlib
 

@@ -23,7 +23,7 @@
 //   * NCH = 3 / 4 (S = 384 / 512, instantiated with NKB = 2): a work unit is (batch row, head, block of 128 queries)
 //     and its keys arrive as NCH chunks of 128 through the same ring; every chunk after the first rescales O and the row
 //     sums by exp2(m_old - m_new) (online softmax at chunk granularity), so 256 < S <= 512 keeps the LDS-DMA pipeline
-//     with 64 score registers per lane and two 4-wave workgroups per CU (engine.hip ATTN_VARIANTS, the one list of the instantiations and their launch shapes: <2, S / 128>).
+//     with 64 score registers per lane and two 4-wave workgroups per CU (encoder_pass.h ATTN_VARIANTS, the one list of the instantiations and their launch shapes: <2, S / 128>).
 #pragma once
 #include "attention.h"
 #include "gemm_pp.h"  // glds16, pack_h2, x8_planes4

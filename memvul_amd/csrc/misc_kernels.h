@@ -354,7 +354,7 @@ __global__ __launch_bounds__(512) void dense768_kernel(const float* __restrict__
 
 // K9 + K10 (anchor match, softmax_2, best anchor / top-k): match_topk.h
 
-// The guarded form on the resident corpus (engine.hip rescore_corpus): rows idx[0 .. n) of the corpus' ids (rows of S ints) into a pass buffer at `width` ints per
+// The guarded form on the resident corpus (corpus.h rescore_corpus): rows idx[0 .. n) of the corpus' ids (rows of S ints) into a pass buffer at `width` ints per
 // row (width <= S), their lengths beside them ...
 __global__ __launch_bounds__(256) void corpus_gather_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ lens, int S, const int32_t* __restrict__ idx,
                                                             int n, int width, int32_t* __restrict__ ids_out, int32_t* __restrict__ lens_out) {

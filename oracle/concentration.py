@@ -12,8 +12,8 @@ from . import memvul_oracle as orc
 from . import precision_model as pm
 
 THRESHOLD = 0.25  # MV_SINK_COLLISION (memvul_amd/csrc/attention.h)
-MIN_LEN = 16      # sequences of fewer tokens are not looked at (attention_v2.h, engine.hip guard_flagged)
-GUARD_SHARE = 0.02  # kGuardShare (engine.hip)
+MIN_LEN = 16      # sequences of fewer tokens are not looked at (attention_v2.h, batch_flow.h guard_flagged)
+GUARD_SHARE = 0.02  # kGuardShare (batch_flow.h)
 _SPY = "_cls_row_spy"
 
 
@@ -57,5 +57,5 @@ def items_total(lens, monitored_layers, heads=12):
 
 
 def rule(over, lens, monitored_layers, heads=12):
-    """The per-sequence rule of the guarded form (engine.hip guard_flagged): more than GUARD_SHARE of the sequence's own items over THRESHOLD."""
+    """The per-sequence rule of the guarded form (batch_flow.h guard_flagged): more than GUARD_SHARE of the sequence's own items over THRESHOLD."""
     return np.asarray(over) > GUARD_SHARE * items_total(lens, monitored_layers, heads)

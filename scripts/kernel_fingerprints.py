@@ -3,7 +3,7 @@ recorded map.
 
   python scripts/kernel_fingerprints.py [--dev] [--lib FILE.so] [--out FILE.json] [--against FILE.json]
 
---against lists the symbols that were added, removed or changed and exits 1 if there are any: a host-only edit of engine.hip must report none, for the
+--against lists the symbols that were added, removed or changed and exits 1 if there are any: a host-only edit of engine.hip or of its parts must report none, for the
 product and for the development build (profiles/kernel_fingerprints*.json hold the maps of the tree as committed)."""
 import argparse
 import json

@@ -5,6 +5,20 @@ import numpy as np
 
 HEADS, HEAD_DIM = 12, 64
 
+
+def host_source():
+    """The host source of the library as one text, for the tests that read it: engine.hip, then the parts it includes, in include order — taken from
+    build.SOURCES and build.HEADERS (a part engine.hip includes but the build does not list, or in another order, fails here)."""
+    import os
+    import re
+
+    from memvul_amd import build
+
+    texts = [open(os.path.join(build.CSRC, s)).read() for s in build.SOURCES]
+    included = [i for t in texts for i in re.findall(r'^#include "([^"/]+)"', t, flags=re.M)]
+    assert included == [h for h in build.HEADERS if not os.path.isabs(h)] == build.KERNEL_HEADERS + build.HOST_PARTS, included
+    return "\n".join(texts + [open(os.path.join(build.CSRC, p)).read() for p in build.HOST_PARTS])
+
 # ---- the passes --------------------------------------------------------------------------------------------------------------------------------------------------
 # (padded length, input width, the lengths of the rows): one batch per padded length, its rows ON the edges of the key mask (thr = len - j S - 8 hi: every
 # 8-key half, 16-key k-slot group, 32-key fragment, 64-key block and 128-key chunk from both sides), of the chunk hand-over (a chunk wholly past len still
@@ -24,7 +38,7 @@ ITEM_LOOP_SHAPES = ((48, 256), (70, 128), (40, 192), (26, 512), (30, 384), (21, 
 
 
 def padded_len(S):
-    """engine.hip padded_len: 64 .. 256 in steps of 64, then 384, 512."""
+    """encoder_pass.h padded_len: 64 .. 256 in steps of 64, then 384, 512."""
     return (S + 63) // 64 * 64 if S <= 256 else (S + 127) // 128 * 128
 
 
@@ -48,13 +62,13 @@ def boundary_ids(width, lens, vocab_size, seed=0):
 
 
 def two_plane(engine, Sp):
-    """The pass carries Q, K, V, P as hi + lo fp16 planes (engine.hip two_plane_pass): the safe form at every padded length, the default form of MV_F16X8 up to
+    """The pass carries Q, K, V, P as hi + lo fp16 planes (encoder_pass.h two_plane_pass): the safe form at every padded length, the default form of MV_F16X8 up to
     128; MV_F16 never."""
     return engine == "safe" or (engine == "precise" and Sp <= 128)
 
 
 def chunk_keys(Sp, planes2):
-    """Keys per chunk of the online softmax (engine.hip ATTN_VARIANTS, the table launch_attention reads): one-plane passes hold the whole key range up to 256 and walk chunks of 128 at 384 / 512;
+    """Keys per chunk of the online softmax (encoder_pass.h ATTN_VARIANTS, the table launch_attention reads): one-plane passes hold the whole key range up to 256 and walk chunks of 128 at 384 / 512;
     the two-plane ring holds it up to 128, walks chunks of 64 at 192 and of 128 above."""
     if planes2:
         return Sp if Sp <= 128 else 64 if Sp == 192 else 128

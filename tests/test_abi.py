@@ -63,13 +63,17 @@ def test_product_code_never_imports_the_oracle():
 
 
 def test_no_cpp_exception_can_cross_the_abi():
-    """include/memvul_hip.h promises that no C++ exception leaves the library: every `int mv_*` entry of engine.hip that has a
-    body of its own is a function-try-block whose handler translates to a status (engine.hip on_exception); only one-line
+    """include/memvul_hip.h promises that no C++ exception leaves the library: every `int mv_*` entry the header declares has its head
+    in engine.hip or one of its parts, and each that has a body of its own is a function-try-block whose handler translates to a status (host_base.h on_exception); only one-line
     accessors that cannot throw are exempt."""
-    src = open(os.path.join(ROOT, "memvul_amd", "csrc", "engine.hip")).read()
-    block = src[src.index('extern "C" {'):src.index('}  // extern "C"')]
+    from stage_kit import host_source
+
+    src = host_source()
+    block = src  # engine.hip and every part it includes (stage_kit.host_source)
     heads = re.findall(r"^int (mv_\w+)\(([^{;]*?)\)\s*(try\s*)?\{(.*)$", block, flags=re.M)
-    assert len(heads) >= 30
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "memvul_hip.h")).read(), flags=re.S)
+    declared = sorted(set(re.findall(r"^\s*int\s+(mv_\w+)\s*\(", hdr, flags=re.M)))
+    assert len(declared) >= 30 and sorted(name for name, _, _, _ in heads) == declared  # one head for every int mv_* the header declares, and no other
     unguarded = [name for name, _, guard, rest in heads if not guard and not rest.rstrip().endswith("}")]
     assert not unguarded, unguarded
     assert block.count("catch (...) { return on_exception(") == sum(1 for _, _, guard, _ in heads if guard)

@@ -41,7 +41,9 @@ def test_header_binding_and_library_carry_the_four_entries():
     assert "model_memory.py:105-115" in hdr[hdr.index("the editable memory"):hdr.index("int mv_corpus_keep(")]
     assert "model_memory.py:135-147" in hdr[hdr.index("the editable memory"):hdr.index("int mv_corpus_keep(")]
     # the four are function-try-blocks like every other entry (test_abi checks the whole file; here: they are in it)
-    src = open(os.path.join(ROOT, "memvul_amd", "csrc", "engine.hip")).read()
+    from stage_kit import host_source
+
+    src = host_source()
     for name in NAMES:
         assert re.search(r"^int %s\([^{;]*\) try \{" % name, src, flags=re.M), name
 

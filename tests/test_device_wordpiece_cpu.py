@@ -49,7 +49,9 @@ def rig(request, lib):
 def test_header_binding_and_library_carry_the_entries(lib):
     declared = test_abi._declared_symbols()
     hdr = open(os.path.join(ROOT, "include", "memvul_hip.h")).read()
-    src = open(os.path.join(ROOT, "memvul_amd", "csrc", "engine.hip")).read()
+    from stage_kit import host_source
+
+    src = host_source()
     for name in NAMES:
         assert name in declared and name in binding.ABI_SYMBOLS and hasattr(lib, name), name
     assert declared == sorted(binding.ABI_SYMBOLS)
@@ -61,7 +63,7 @@ def test_header_binding_and_library_carry_the_entries(lib):
     assert "typedef struct mv_tokenizer mv_tokenizer;" in hdr
     for name in ("mv_tok_create", "mv_tok_encode", "mv_tok_encode_host"):  # function-try-blocks like every other entry (test_abi checks the whole file)
         assert re.search(r"^int %s\([^{;]*\) try \{" % name, src, flags=re.M), name
-    assert "struct mv_tokenizer {" in src and "mv_tokenizer" not in src[src.index("struct mv_handle {"):src.index("struct mv_tokenizer {")]  # not part of a handle
+    assert "struct mv_tokenizer {" in src and "mv_tokenizer" not in src[src.index("struct mv_handle {"):src.index("\n};\n", src.index("struct mv_handle {"))]  # not part of a handle (the struct's own text)
 
 
 def _raw(lib, dwp, fn, text, off, n, max_length, ids, lens, status):

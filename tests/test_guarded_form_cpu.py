@@ -34,7 +34,9 @@ def test_header_binding_and_library_carry_the_guarded_form():
     env = hdr[hdr.index("Environment switches read HERE"):]
     assert "six" in env[:200] and re.search(r"MEMVUL_FORM\s+default \| safe \| guarded", env)
     # every int mv_* is a function-try-block
-    src = open(os.path.join(ROOT, "memvul_amd", "csrc", "engine.hip")).read()
+    from stage_kit import host_source
+
+    src = host_source()
     for name in ("mv_form_stats", "mv_last_row_forms", "mv_corpus_row_forms"):
         assert re.search(r"\nint %s\([^)]*\) try \{" % name, src), name
 

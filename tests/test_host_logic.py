@@ -194,7 +194,9 @@ def test_documented_switch_defaults_match_the_library_source():
 
     import bench
 
-    src = open(os.path.join(ROOT, "memvul_amd", "csrc", "engine.hip")).read()
+    from stage_kit import host_source
+
+    src = host_source()
     m = re.search(r"bool cls_aside = (true|false);", src)
     assert m and bench.DEFAULT_CLS_ASIDE == ("1" if m.group(1) == "true" else "0")
     n = re.search(r"int cls_min_len = (\d+);", src)

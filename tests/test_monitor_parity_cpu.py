@@ -125,7 +125,9 @@ def test_fixture_meets_the_conditions_the_gpu_tests_rely_on(refs):
 
 def test_the_rule_in_numpy_agrees_with_the_numbers_the_sources_state():
     """over > 0.02 x 12 x monitored layers, no items below 16 tokens: 132 items (12 layers, the last one pruned) rescore at >= 3, 12 items (2 layers) at >= 1."""
-    src = open(os.path.join(ROOT, "memvul_amd", "csrc", "engine.hip")).read()
+    from stage_kit import host_source
+
+    src = host_source()
     hdr = open(os.path.join(ROOT, "include", "memvul_hip.h")).read()
     att = open(os.path.join(ROOT, "memvul_amd", "csrc", "attention.h")).read()
     kern = open(os.path.join(ROOT, "memvul_amd", "csrc", "attention_v2.h")).read()

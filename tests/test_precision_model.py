@@ -84,7 +84,7 @@ def test_fp8_correction_sweeps_hold_the_budget(case):
 
 
 def test_host_e4m3_encoder_matches_the_rounding_model():
-    """The library's host-side e4m3 encoder (engine.hip f32_to_e4m3_bits: the MV_F16X8 weight planes) against the model's
+    """The library's host-side e4m3 encoder (weights.h f32_to_e4m3_bits: the MV_F16X8 weight planes) against the model's
     rounding function, bit-exactly after decoding, on every binade, ties, subnormals, saturation and signs (no GPU needed)."""
     from memvul_amd.binding import e4m3_bits, e4m3_decode
 

@@ -37,7 +37,9 @@ def test_header_and_binding_declare_the_two_entry_points():
     assert re.search(r"\bint mv_sink_census_read\(mv_handle\* h, uint32_t\* items, uint64_t\* share_q20, int vocab, uint32_t\* by_head, int layers_x_heads, int reset\);", hdr)
     for name in NAMES:
         assert name in binding.ABI_SYMBOLS
-    src = open(os.path.join(ROOT, "memvul_amd", "csrc", "engine.hip")).read()
+    from stage_kit import host_source
+
+    src = host_source()
     for name in NAMES:  # function-try-blocks, like every entry point
         assert re.search(r"^int %s\([^{;]*\) try \{" % name, src, flags=re.M), name
     assert "sink_census.h" in open(os.path.join(ROOT, "memvul_amd", "build.py")).read()  # (a kernel edit must move the build's fingerprint)

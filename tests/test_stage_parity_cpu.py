@@ -57,7 +57,7 @@ def test_each_fault_leaves_the_bound(batch, mutation, path, planes2):
 
 
 def test_the_faults_apply_where_the_kernel_has_the_structure():
-    """Every fault is exercised on both paths, the rescale on every chunked geometry the engine launches (engine.hip launch_attention)."""
+    """Every fault is exercised on both paths, the rescale on every chunked geometry the engine launches (encoder_pass.h launch_attention)."""
     for _, planes2 in PATHS:
         for mutation in sk.MUTATIONS:
             assert any(_applies(mutation, b, planes2) for b in sk.BOUNDARY_BATCHES), (mutation, planes2)
