@@ -434,7 +434,20 @@ int mv_format_records(const char* prefixes, const int64_t* prefix_off, int64_t r
  * untouched; n == 0 -> MV_OK, nothing read or written (also on an object without a device).  A HIP failure in the middle of a call waits for whatever the
  * call had queued before it returns: the caller's arrays are not written after a failed call.
  * mv_tok_kernel_ms: *ms = the kernel's own time, from HIP events around each chunk's launch, summed over the chunks of the last mv_tok_encode (0 before the
- * first): what of a call is tokenising and what is copying. */
+ * first): what of a call is tokenising and what is copying.  It covers whichever kernel ran last (mv_tok_encode or mv_tok_encode_u8).
+ *
+ * UTF-8 text (opt-in; the rule: memvul_amd/csrc/wordpiece.h).  mv_tok_set_unicode attaches a code-point table to an existing object and uploads it when the
+ * object has a device: n_entries (1 .. 131072) entries of 16 bytes, entry i for code point i (entries below 0x80 are never read; code points from n_entries
+ * on count as uncovered): bytes 0 .. 11 the UTF-8 of the tokenizer's normalizer applied to that one code point, byte 12 their count (0 .. 12), byte 13 the
+ * classes of the output code points, two bits each, the first in the low bits (1 whitespace, 2 punctuation, 3 word), byte 14 the covered flag (0 / 1), byte 15
+ * the number of output code points (0 .. 3).  MV_ERR_INVALID, the object unchanged, on a malformed table — a byte count over 12, output bytes that are not
+ * well-formed UTF-8, a class outside the three, a character count that is not the bytes' — and when a word of max_chars_per_word characters plus one
+ * 64-byte step's largest output under this table does not fit the kernel's word buffer (640 bytes: max_chars_per_word 100 fits the tables BertNormalizer
+ * gives).  memvul_amd/tokenizer.py builds the table from the tokenizer's own normalizer and pre-tokenizer and decides there which code points are covered.
+ * mv_tok_encode_u8 / mv_tok_encode_u8_host: the arguments, checks, chunking and "outputs untouched on error" of mv_tok_encode / mv_tok_encode_host, for text
+ * in UTF-8.  status[i] is 0 (tokenised, byte-equal to the Rust backend), 1 (an added-token literal in the raw bytes, as above, here also a literal with bytes >= 0x80; it wins over 2) or 2 (a
+ * malformed UTF-8 sequence, a code point >= U+20000 or one the table marks uncovered); rows of status 1 and 2 have length 0 and a zero id row.  On an object
+ * without a table -> MV_ERR_STATE.  mv_tok_encode and mv_tok_encode_host are unchanged on an object with a table: they hand back every byte >= 0x80. */
 typedef struct mv_tokenizer mv_tokenizer;
 int mv_tok_create(int device, const char* vocab_bytes, const int64_t* vocab_off, int n_vocab, const char* literal_bytes, const int64_t* literal_off,
                   int n_literals, int unk_id, int cls_id, int sep_id, int max_chars_per_word, int lowercase, mv_tokenizer** out);
@@ -443,6 +456,11 @@ int mv_tok_encode(mv_tokenizer* tok, const char* text, const int64_t* off, int n
 int mv_tok_encode_host(mv_tokenizer* tok, const char* text, const int64_t* off, int n, int max_length, int add_special, int32_t* ids, int32_t* lens,
                        uint8_t* status);
 int mv_tok_kernel_ms(mv_tokenizer* tok, float* ms);
+int mv_tok_set_unicode(mv_tokenizer* tok, const void* entries, int n_entries);
+int mv_tok_encode_u8(mv_tokenizer* tok, const char* text, const int64_t* off, int n, int max_length, int add_special, int32_t* ids, int32_t* lens,
+                     uint8_t* status);
+int mv_tok_encode_u8_host(mv_tokenizer* tok, const char* text, const int64_t* off, int n, int max_length, int add_special, int32_t* ids, int32_t* lens,
+                          uint8_t* status);
 void mv_tok_destroy(mv_tokenizer* tok);
 /* Last error message of this object (or of a failed mv_tok_create when tok == NULL). */
 const char* mv_tok_last_error(mv_tokenizer* tok);

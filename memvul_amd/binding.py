@@ -94,16 +94,17 @@ def sink_tokens_policy() -> Optional[List[int]]:
     return None if v is None else parse_sink_tokens(v)
 
 
-TOKENIZE_MODES = ("host", "gpu")
+TOKENIZE_MODES = ("host", "gpu", "gpu-utf8")
 
 
 def tokenize_policy(option=None) -> str:
-    """engine_options["tokenize"] or $MEMVUL_TOKENIZE = host (default) | gpu, parsed strictly: where the drivers tokenise the issue reports — "gpu" attaches
-    the reader's tokenizer to the model's device (tokenizer.PretrainedTransformerTokenizer.attach_device: ASCII rows through DeviceWordPiece, every other row
-    through the tokenizer it already has).  The option wins over the environment; an unknown value raises."""
+    """engine_options["tokenize"] or $MEMVUL_TOKENIZE = host (default) | gpu | gpu-utf8, parsed strictly: where the drivers tokenise the issue reports — "gpu"
+    attaches the reader's tokenizer to the model's device (tokenizer.PretrainedTransformerTokenizer.attach_device: ASCII rows through DeviceWordPiece, every
+    other row through the tokenizer it already has); "gpu-utf8" attaches it with unicode=True (every row goes to the device in UTF-8; the rows its code-point
+    table does not cover come back and go through the tokenizer it already has).  The option wins over the environment; an unknown value raises."""
     v, src = (option, 'engine_options["tokenize"]') if option is not None else (os.environ.get("MEMVUL_TOKENIZE", "host"), "MEMVUL_TOKENIZE")
     if v not in TOKENIZE_MODES:
-        raise ValueError(f"{src}={v!r}: expected 'host' or 'gpu'")
+        raise ValueError(f"{src}={v!r}: expected one of {', '.join(map(repr, TOKENIZE_MODES))}")
     return v
 
 
@@ -145,6 +146,7 @@ ABI_SYMBOLS = [
     "mv_debug_encode", "mv_debug_read", "mv_test_gemm", "mv_test_gemm_pp", "mv_test_gemm_f32", "mv_test_e4m3", "mv_format_records", "mv_comm_prepare", "mv_comm_unique_id", "mv_comm_init", "mv_comm_allgather",
     "mv_comm_destroy", "mv_comm_info", "mv_device_count",
     "mv_tok_create", "mv_tok_encode", "mv_tok_encode_host", "mv_tok_kernel_ms", "mv_tok_destroy", "mv_tok_last_error",
+    "mv_tok_set_unicode", "mv_tok_encode_u8", "mv_tok_encode_u8_host",
 ]
 
 
@@ -243,6 +245,9 @@ def load_library(path: Optional[str] = None, dev: bool = False):
         "mv_tok_encode": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "mv_tok_encode_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "mv_tok_kernel_ms": (C.c_int, [vp, P(C.c_float)]),
+        "mv_tok_set_unicode": (C.c_int, [vp, vp, C.c_int]),
+        "mv_tok_encode_u8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "mv_tok_encode_u8_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "mv_tok_destroy": (None, [vp]),
         "mv_tok_last_error": (C.c_char_p, [vp]),
     }
@@ -1008,11 +1013,17 @@ def _packed(strings) -> Tuple[bytes, np.ndarray]:
     return b"".join(strings), off
 
 
+# one entry of the code-point table of mv_tok_set_unicode (include/memvul_hip.h; memvul_amd/csrc/wordpiece.h WpCp)
+CODE_POINT_DTYPE = np.dtype([("out", np.uint8, 12), ("nbytes", np.uint8), ("cls", np.uint8), ("covered", np.uint8), ("nchars", np.uint8)])
+CODE_POINTS = 0x20000
+
+
 class DeviceWordPiece:
     """The device WordPiece tokenizer (include/memvul_hip.h mv_tok_*): ASCII text -> the ids BertTokenizerFast's backend gives it.  ``vocab``: the pieces
     as bytes, index = id (b"" for an unused id); ``literals``: the tokenizer's added tokens as bytes — a row that holds one, or a byte >= 0x80, comes back with
     status 1, length 0 and a zero id row, for the caller to encode with the tokenizer it has.  ``device=None``: the table only; such an object serves
-    ``encode_host`` (the rule on the CPU: tests and reference) and needs no GPU.  Its own object in the library: usable from one thread while another drives
+    ``encode_host`` (the rule on the CPU: tests and reference) and needs no GPU.  After ``set_unicode`` (a code-point table: tokenizer.code_point_table)
+    ``encode_u8`` / ``encode_u8_host`` take text in UTF-8 and hand back only what the table does not cover (status 2).  Its own object in the library: usable from one thread while another drives
     an ``Engine`` of the same device; not re-entrant itself."""
 
     def __init__(self, vocab, literals, unk_id: int, cls_id: int, sep_id: int, max_chars_per_word: int = 100, lowercase: bool = True,
@@ -1068,3 +1079,24 @@ class DeviceWordPiece:
     def encode_host(self, packed: bytes, offsets, max_length: int, add_special: bool = True):
         """The same rule, single-threaded on the CPU (mv_tok_encode_host)."""
         return self._run(self._lib.mv_tok_encode_host, "mv_tok_encode_host", packed, offsets, max_length, add_special)
+
+    def set_unicode(self, entries):
+        """Attach a code-point table (mv_tok_set_unicode): uint8 [n, 16], row i for code point i, laid out as include/memvul_hip.h says (CODE_POINT_DTYPE).
+        ``encode_u8`` / ``encode_u8_host`` need one; ``encode`` / ``encode_host`` do not change."""
+        e = np.ascontiguousarray(entries)
+        if e.dtype == CODE_POINT_DTYPE:
+            e = e.view(np.uint8).reshape(-1, 16)
+        if e.dtype != np.uint8 or e.ndim != 2 or e.shape[1] != 16:
+            raise ValueError("set_unicode: entries must be uint8 [n, 16] or CODE_POINT_DTYPE [n]")
+        rc = self._lib.mv_tok_set_unicode(self._t, _ptr(e), len(e))
+        if rc != 0:
+            msg = self._lib.mv_tok_last_error(self._t)
+            raise RuntimeError(f"mv_tok_set_unicode failed ({rc}): {msg.decode() if msg else ''}")
+
+    def encode_u8(self, packed: bytes, offsets, max_length: int, add_special: bool = True):
+        """The UTF-8 kernel (mv_tok_encode_u8): as ``encode`` for text in UTF-8; status 0 tokenised, 1 an added-token literal, 2 malformed or not covered."""
+        return self._run(self._lib.mv_tok_encode_u8, "mv_tok_encode_u8", packed, offsets, max_length, add_special)
+
+    def encode_u8_host(self, packed: bytes, offsets, max_length: int, add_special: bool = True):
+        """The UTF-8 rule, single-threaded on the CPU (mv_tok_encode_u8_host)."""
+        return self._run(self._lib.mv_tok_encode_u8_host, "mv_tok_encode_u8_host", packed, offsets, max_length, add_special)

@@ -1,4 +1,4 @@
-"""Build libmemvul_hip.so (gfx950) in-tree with hipcc.  No torch involved."""
+"""Build libmemvul_hip.so and libmemvul_tok_u8.so (gfx950) in-tree with hipcc.  No torch involved."""
 from __future__ import annotations
 
 import os
@@ -16,6 +16,12 @@ LIB_PATH = os.path.join(LIB_DIR, "libmemvul_hip.so")
 # MEMVUL_NUM_CU; engine.hip read_switches) exist only in this build — GPU tests that force a kernel path at test sizes and the A/B scripts load it
 LIB_PATH_DEV = os.path.join(LIB_DIR, "libmemvul_hip_dev.so")
 DEV_FLAGS = ("-DMEMVUL_DEV_SWITCHES",)
+# the UTF-8 tokenise kernel and its launch function, a library and a code object of its own (csrc/wordpiece_u8.hip says why); the two libraries above link
+# against it and find it beside themselves ($ORIGIN), so it is built before them
+TOK_LIB_NAME = "libmemvul_tok_u8.so"
+LIB_PATH_TOK = os.path.join(LIB_DIR, TOK_LIB_NAME)
+TOK_SOURCES = ["wordpiece_u8.hip"]
+TOK_HEADERS = ["wordpiece.h"]
 SOURCES = ["engine.hip"]
 KERNEL_HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", "wordpiece.h"]
 # the host code of the library: engine.hip includes each of these parts once, in this order
@@ -47,14 +53,14 @@ def _compiler_id():
         return None
 
 
-def source_fingerprint(extra_flags=()) -> str:
+def source_fingerprint(extra_flags=(), sources=None, headers=None) -> str:
     """sha256 of the flags and the CONTENT of every source / header (not mtimes — a checkout or a copy to another box
-    rewrites those)."""
+    rewrites those).  sources / headers: those of another library than libmemvul_hip.so."""
     import hashlib
 
     h = hashlib.sha256()
     h.update(" ".join([ARCH, *FLAGS, *extra_flags]).encode())
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [h_ if os.path.isabs(h_) else os.path.join(CSRC, h_) for h_ in HEADERS]
+    deps = [os.path.join(CSRC, s) for s in (sources or SOURCES)] + [h_ if os.path.isabs(h_) else os.path.join(CSRC, h_) for h_ in (headers or HEADERS)]
     for d in deps:
         h.update(os.path.basename(d).encode())
         with open(d, "rb") as f:
@@ -205,8 +211,44 @@ def is_stale(extra_flags=(), dev: bool = False) -> bool:
     return want["cc"] != "unknown" and have.get("cc") != want["cc"]
 
 
+def tok_is_stale() -> bool:
+    """is_stale for libmemvul_tok_u8.so (its own stamp: its sources are wordpiece_u8.hip and wordpiece.h)."""
+    stamp_path = LIB_PATH_TOK + ".stamp"
+    if not os.path.exists(LIB_PATH_TOK) or not os.path.exists(stamp_path):
+        return True
+    with open(stamp_path) as f:
+        have = dict(line.split(" ", 1) for line in f.read().strip().splitlines() if " " in line)
+    cc = _compiler_id()
+    import hashlib
+
+    if have.get("src") != source_fingerprint((), TOK_SOURCES, TOK_HEADERS):
+        return True
+    return cc is not None and have.get("cc") != hashlib.sha256(cc).hexdigest()
+
+
+def build_tok(force: bool = False, verbose: bool = True) -> str:
+    """Compile libmemvul_tok_u8.so for gfx950; returns its path."""
+    if not force and not tok_is_stale():
+        return LIB_PATH_TOK
+    import hashlib
+
+    os.makedirs(LIB_DIR, exist_ok=True)
+    cmd = [hipcc_path(), f"--offload-arch={ARCH}", *FLAGS, f"-Wl,-soname,{TOK_LIB_NAME}", *[os.path.join(CSRC, s) for s in TOK_SOURCES], "-o", LIB_PATH_TOK + ".tmp"]
+    if verbose:
+        print("[memvul_amd.build]", " ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    cc = _compiler_id()
+    with open(LIB_PATH_TOK + ".stamp.tmp", "w") as f:
+        f.write("src %s\ncc %s\n" % (source_fingerprint((), TOK_SOURCES, TOK_HEADERS), hashlib.sha256(cc).hexdigest() if cc is not None else "unknown"))
+    os.replace(LIB_PATH_TOK + ".tmp", LIB_PATH_TOK)
+    os.replace(LIB_PATH_TOK + ".stamp.tmp", LIB_PATH_TOK + ".stamp")
+    return LIB_PATH_TOK
+
+
 def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool = False) -> str:
-    """Compile the HIP library for gfx950; returns the .so path.  dev: the -DMEMVUL_DEV_SWITCHES build (libmemvul_hip_dev.so)."""
+    """Compile the HIP library for gfx950; returns the .so path.  dev: the -DMEMVUL_DEV_SWITCHES build (libmemvul_hip_dev.so).  libmemvul_tok_u8.so, which
+    both link against, is brought up to date first."""
+    tok = build_tok(False, verbose)  # (forced by build_all, once for both)
     if not force and not is_stale(extra_flags, dev):
         return _paths(dev)[0]
     lib_path, stamp_path = _paths(dev)
@@ -217,6 +259,7 @@ def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool =
         hipcc_path(), f"--offload-arch={ARCH}", *FLAGS,  # -Wno-unused-value: hipError_t of calls checked by launch_check
         *extra_flags,
         *[os.path.join(CSRC, s) for s in SOURCES],
+        "-L" + os.path.dirname(tok), "-l:" + TOK_LIB_NAME, "-Wl,-rpath,$ORIGIN",  # (found beside this library wherever the tree lies)
         "-o", lib_path + ".tmp",
     ]
     if verbose:
@@ -239,9 +282,10 @@ def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool =
 
 
 def build_all(force: bool = False, verbose: bool = True):
-    """Both builds, compiled side by side (two hipcc processes)."""
+    """Both builds, compiled side by side (two hipcc processes), after the library both link against."""
     from concurrent.futures import ThreadPoolExecutor
 
+    build_tok(force, verbose)
     with ThreadPoolExecutor(2) as ex:
         futs = [ex.submit(build, force, verbose, (), d) for d in (False, True)]
         return [f.result() for f in futs]

@@ -256,18 +256,19 @@ def _jsonable(x):
 
 
 def attach_tokenizer(archive, engine_options=None) -> bool:
-    """The tokenize switch (binding.tokenize_policy: engine_options["tokenize"] or $MEMVUL_TOKENIZE = host | gpu, host by default): with "gpu" the reader's
-    tokenizer is attached to the model's device (PretrainedTransformerTokenizer.attach_device), so that ``batch_ids`` — what read_arrays / iter_arrays and the
-    batched Instance readers call — tokenises its ASCII rows there.  A tokenizer the device rule does not restate raises; nothing falls back silently.
-    Returns True when a device was attached."""
+    """The tokenize switch (binding.tokenize_policy: engine_options["tokenize"] or $MEMVUL_TOKENIZE = host | gpu | gpu-utf8, host by default): with "gpu" the
+    reader's tokenizer is attached to the model's device (PretrainedTransformerTokenizer.attach_device), so that ``batch_ids`` — what read_arrays / iter_arrays
+    and the batched Instance readers call — tokenises its ASCII rows there; with "gpu-utf8" it is attached with unicode=True and tokenises there every row its
+    code-point table covers.  A tokenizer the device rule does not restate raises; nothing falls back silently.  Returns True when a device was attached."""
     from .binding import tokenize_policy
 
-    if tokenize_policy((engine_options or {}).get("tokenize")) != "gpu":
+    mode = tokenize_policy((engine_options or {}).get("tokenize"))
+    if mode == "host":
         return False
     tok = getattr(archive.dataset_reader, "_tokenizer", None)
     if not hasattr(tok, "attach_device"):
-        raise RuntimeError(f"tokenize=gpu: the reader's tokenizer ({type(tok).__name__}) cannot be attached to a device")
-    tok.attach_device(getattr(archive.model, "_device_index", 0))
+        raise RuntimeError(f"tokenize={mode}: the reader's tokenizer ({type(tok).__name__}) cannot be attached to a device")
+    tok.attach_device(getattr(archive.model, "_device_index", 0), unicode=mode == "gpu-utf8")
     return True
 
 

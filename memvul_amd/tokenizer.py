@@ -35,6 +35,49 @@ def _find_vocab(model_name: str) -> Optional[str]:
     return None
 
 
+def code_point_table(backend_tokenizer):
+    """The code-point table of the device tokenizer's UTF-8 rule (memvul_amd/csrc/wordpiece.h; binding.CODE_POINT_DTYPE [0x20000], entry i for code point i),
+    read from the tokenizer itself: the output bytes are ``normalizer.normalize_str(chr(cp))`` — clean, CJK spacing, accent stripping and lower-casing are
+    whatever this normalizer does, probed, not assumed — and the class of every output character is what ``pre_tokenizer.pre_tokenize_str("a" + c + "a")``
+    shows: ["a", c, "a"] punctuation, ["a", "a"] whitespace, ["a" + c + "a"] a word character.  A code point is left UNCOVERED (a row that holds it is handed
+    back, status 2) when Python's unicodedata calls it unassigned (the Rust crate may know a newer Unicode), when its output keeps a character of non-zero
+    canonical combining class (NFD reorders those: the normalizer is not context-free there), when the output exceeds 3 code points or 12 bytes, or when an
+    output character's probe is none of the three patterns.  Entries below 0x80 stay zero: the ASCII rule never reads them."""
+    import unicodedata
+
+    import numpy as np
+
+    from .binding import CODE_POINT_DTYPE, CODE_POINTS
+
+    norm, pre = backend_tokenizer.normalizer, backend_tokenizer.pre_tokenizer
+    raw = bytearray(16 * CODE_POINTS)
+    classes: Dict[str, int] = {}
+
+    def class_of(c: str) -> int:
+        k = classes.get(c)
+        if k is None:
+            got = [w for w, _ in pre.pre_tokenize_str("a" + c + "a")]
+            k = classes[c] = 3 if got == ["a" + c + "a"] else 2 if got == ["a", c, "a"] else 1 if got == ["a", "a"] else 0
+        return k
+
+    for cp in range(0x80, CODE_POINTS):
+        if 0xD800 <= cp <= 0xDFFF:  # no scalar values: in UTF-8 they are malformed sequences
+            continue
+        ch = chr(cp)
+        if unicodedata.category(ch) == "Cn":
+            continue
+        out = norm.normalize_str(ch)
+        if len(out) > 3 or any(unicodedata.combining(c) for c in out):
+            continue
+        b = out.encode("utf-8")
+        ks = [class_of(c) for c in out]
+        if len(b) > 12 or 0 in ks:
+            continue
+        raw[16 * cp:16 * cp + len(b)] = b
+        raw[16 * cp + 12:16 * cp + 16] = bytes((len(b), sum(k << (2 * j) for j, k in enumerate(ks)), 1, len(out)))
+    return np.frombuffer(bytes(raw), CODE_POINT_DTYPE)
+
+
 class TokenRow:
     """The tokens of one text as a sequence over its id array: ``len``, iteration and indexing give ``Token`` objects (built when asked for: with
     the WordPiece backend their ``text`` is looked up then), ``ids`` gives the int32 array the collation reads directly — a file of 40 k issue
@@ -78,7 +121,12 @@ class PretrainedTransformerTokenizer(Tokenizer):
         self._hf = None
         self._device = None          # attach_device: the binding.DeviceWordPiece the ASCII rows of batch_ids go through
         self._device_encode = None
-        self.device_counts = {"device": 0, "literal": 0, "non_ascii": 0}  # rows batch_ids tokenised on the device / got back for an added-token literal / kept off it
+        # rows batch_ids tokenised on the device / got back for an added-token literal (status 1) / kept off it for a byte >= 0x80, or with unicode=True got back
+        # for a malformed sequence or an uncovered code point (status 2)
+        self.device_counts = {"device": 0, "literal": 0, "non_ascii": 0}
+        self._device_unicode = False   # attach_device(unicode=True): batch_ids sends every row to the device in UTF-8
+        self._code_points = None       # its code-point table, built once per tokenizer object
+        self.device_unicode_rows = 0   # rows with a byte >= 0x80 that batch_ids tokenised on the device
         vocab = _find_vocab(model_name)
         if vocab is None:
             # a cached / local HuggingFace copy of `model_name` (what AllenNLP's tokenizer loads, reader_memory.py:88)
@@ -180,12 +228,15 @@ class PretrainedTransformerTokenizer(Tokenizer):
         return {"vocab": pieces, "literals": literals, "unk_id": vocab[unk], "cls_id": cls_id, "sep_id": sep_id,
                 "max_chars_per_word": int(model.get("max_input_chars_per_word", 100)), "lowercase": bool(norm.get("lowercase"))}
 
-    def attach_device(self, device_index: int = 0, host_restatement: bool = False):
+    def attach_device(self, device_index: int = 0, host_restatement: bool = False, unicode: bool = False):
         """Tokenise the ASCII rows of ``batch_ids`` on GPU ``device_index`` (binding.DeviceWordPiece); every other row, and every row that comes back for an
         added-token literal, keeps going through the Rust tokenizer: the arrays are those of the host path for every input.  Raises, naming the field, when
         the backend is not what the device rule restates (device_spec) or ``max_length`` is outside 2 .. 512.  ``max_length=None`` attaches but leaves
         batch_ids on the host: without it neither the row width nor the work per row is bounded.  ``host_restatement``: run the same rule through
-        mv_tok_encode_host instead, no GPU — for tests; no switch selects it."""
+        mv_tok_encode_host instead, no GPU — for tests; no switch selects it.  ``unicode``: the UTF-8 rule instead — EVERY row goes to the device, packed as
+        UTF-8 (mv_tok_encode_u8), with the code-point table built from this tokenizer's own normalizer and pre-tokenizer (code_point_table, once per tokenizer
+        object); the rows that come back — an added-token literal, or a malformed sequence / a code point the table does not cover — go through the Rust
+        tokenizer as before."""
         from .binding import DeviceWordPiece
 
         spec = self.device_spec()
@@ -194,12 +245,23 @@ class PretrainedTransformerTokenizer(Tokenizer):
         self.detach_device()
         self._device = DeviceWordPiece(device=None if host_restatement else int(device_index), **spec)
         self._device_encode = self._device.encode_host if host_restatement else self._device.encode
+        self._device_unicode = bool(unicode)
+        if unicode:
+            try:
+                if self._code_points is None:
+                    self._code_points = code_point_table(self._hf.backend_tokenizer)
+                self._device.set_unicode(self._code_points)
+            except Exception:
+                self.detach_device()
+                raise
+            self._device_encode = self._device.encode_u8_host if host_restatement else self._device.encode_u8
         return self
 
     def detach_device(self):
         if self._device is not None:
             self._device.close()
         self._device = self._device_encode = None
+        self._device_unicode = False
 
     def _device_batch_ids(self, bt, texts: List[str]):
         """batch_ids with a device attached: ASCII rows packed and encoded there, the rest — and the rows handed back — in ONE encode_batch call, merged in
@@ -236,6 +298,32 @@ class PretrainedTransformerTokenizer(Tokenizer):
         self.device_counts["non_ascii"] += n - len(asc)
         return np.ascontiguousarray(ids[:, :int(lens.max())]), lens
 
+    def _device_batch_ids_unicode(self, bt, texts: List[str]):
+        """batch_ids with a device attached with unicode=True: all rows packed as UTF-8 (a lone surrogate passes as the malformed sequence it is and comes
+        back) and encoded there in ONE call; the rows handed back in ONE encode_batch call, as above."""
+        import numpy as np
+
+        n, width = len(texts), int(self._max_length)
+        flags = np.fromiter((t.isascii() for t in texts), dtype=bool, count=n)
+        nbytes = np.fromiter((len(t) for t in texts), np.int64, n)  # (characters = bytes for the ASCII rows; the others are counted below)
+        for i in np.flatnonzero(~flags):
+            nbytes[i] = len(texts[i].encode("utf-8", "surrogatepass"))
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(nbytes, out=off[1:])
+        ids, lens, status = self._device_encode("".join(texts).encode("utf-8", "surrogatepass"), off, width, self._add_special)
+        back = np.flatnonzero(status != 0)
+        if len(back):
+            bt.enable_truncation(max_length=self._max_length)
+            bt.no_padding()
+            for i, e in zip(back, bt.encode_batch([texts[i] for i in back], add_special_tokens=self._add_special)):
+                lens[i] = len(e)
+                ids[i, :len(e)] = e.ids
+        self.device_counts["device"] += n - len(back)
+        self.device_counts["literal"] += int((status == 1).sum())
+        self.device_counts["non_ascii"] += int((status == 2).sum())
+        self.device_unicode_rows += int((~flags & (status == 0)).sum())
+        return np.ascontiguousarray(ids[:, :int(lens.max())]), lens
+
     def batch_ids(self, texts: List[str], workers: int = 0):
         """Array form of ``tokenize`` for a whole file: ``(ids int32 [N, L] zero-padded, lens int32 [N])`` with exactly the
         ids ``tokenize`` gives text by text.  The WordPiece path is one batched call into the Rust tokenizer (parallel
@@ -244,7 +332,7 @@ class PretrainedTransformerTokenizer(Tokenizer):
 
         bt = getattr(self._hf, "backend_tokenizer", None) if self._hf is not None else None
         if bt is not None and len(texts) and self._device_encode is not None and self._max_length is not None:
-            return self._device_batch_ids(bt, list(texts))
+            return (self._device_batch_ids_unicode if self._device_unicode else self._device_batch_ids)(bt, list(texts))
         if bt is not None and len(texts):
             # the Rust tokenizer itself, not the transformers wrapper around it: the wrapper turns every encoding into dicts of Python lists under the interpreter
             # lock (1.3 s of a 1.8 s call for 8 k reports; the same ids: tests/test_plumbing.py) — here the ids go from the encodings into ONE flat int32 array and from
