@@ -9,7 +9,8 @@ import ctypes as C
 import os
 import re
 import warnings
-from typing import Dict, Iterable, List, Optional, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -57,21 +58,23 @@ def compute_dtype_of(name_or_code) -> int:
     return int(name_or_code)
 
 
+def _strict(value, source: str, allowed):
+    """A switch that takes one of a few spellings and nothing else: `value` when it is one of `allowed`, else the ValueError that names `source` and them."""
+    if value not in allowed:
+        names = [repr(a) for a in allowed]
+        raise ValueError(f"{source}={value!r}: expected {' or '.join(names) if len(names) == 2 else 'one of ' + ', '.join(names)}")
+    return value
+
+
 def on_sink_policy() -> str:
     """$MEMVUL_ON_SINK = warn (default) | safe, parsed strictly: what an MV_F16X8 engine does when the concentration monitor reports attention sinks on ordinary
     tokens — warn once and go on in the default form, or switch to the safe form (Engine._on_sink_trip)."""
-    v = os.environ.get("MEMVUL_ON_SINK", "warn")
-    if v not in ("warn", "safe"):
-        raise ValueError(f"MEMVUL_ON_SINK={v!r}: expected 'warn' or 'safe'")
-    return v
+    return _strict(os.environ.get("MEMVUL_ON_SINK", "warn"), "MEMVUL_ON_SINK", ("warn", "safe"))
 
 
 def sink_census_policy() -> bool:
     """$MEMVUL_SINK_CENSUS = 0 (default) | 1, parsed strictly: whether an MV_F16X8 engine keeps the sink census from construction on (Engine.sink_census)."""
-    v = os.environ.get("MEMVUL_SINK_CENSUS", "0")
-    if v not in ("0", "1"):
-        raise ValueError(f"MEMVUL_SINK_CENSUS={v!r}: expected '0' or '1'")
-    return v == "1"
+    return _strict(os.environ.get("MEMVUL_SINK_CENSUS", "0"), "MEMVUL_SINK_CENSUS", ("0", "1")) == "1"
 
 
 MAX_SINK_TOKENS = 64  # include/memvul_hip.h MV_MAX_SINK_TOKENS
@@ -102,10 +105,9 @@ def tokenize_policy(option=None) -> str:
     attaches the reader's tokenizer to the model's device (tokenizer.PretrainedTransformerTokenizer.attach_device: ASCII rows through DeviceWordPiece, every
     other row through the tokenizer it already has); "gpu-utf8" attaches it with unicode=True (every row goes to the device in UTF-8; the rows its code-point
     table does not cover come back and go through the tokenizer it already has).  The option wins over the environment; an unknown value raises."""
-    v, src = (option, 'engine_options["tokenize"]') if option is not None else (os.environ.get("MEMVUL_TOKENIZE", "host"), "MEMVUL_TOKENIZE")
-    if v not in TOKENIZE_MODES:
-        raise ValueError(f"{src}={v!r}: expected one of {', '.join(map(repr, TOKENIZE_MODES))}")
-    return v
+    if option is not None:
+        return _strict(option, 'engine_options["tokenize"]', TOKENIZE_MODES)
+    return _strict(os.environ.get("MEMVUL_TOKENIZE", "host"), "MEMVUL_TOKENIZE", TOKENIZE_MODES)
 
 
 def _sink_token_list(ids) -> List[int]:
@@ -136,20 +138,6 @@ def wanted_form(name_or_code) -> Optional[str]:
 
 NUM_KERNEL_CLASSES = 14
 
-# every symbol include/memvul_hip.h declares (tests check the .so exports all of them)
-ABI_SYMBOLS = [
-    "mv_create", "mv_destroy", "mv_last_error", "mv_sync", "mv_load_tensor", "mv_finalize_weights",
-    "mv_anchor_reset", "mv_anchor_append", "mv_anchor_count", "mv_anchor_get", "mv_anchor_set",
-    "mv_forward", "mv_forward_ragged", "mv_forward_ragged_begin", "mv_forward_ragged_end", "mv_encode", "mv_match", "mv_topk", "mv_corpus_upload", "mv_corpus_run", "mv_corpus_run_len",
-    "mv_corpus_results", "mv_corpus_keep", "mv_corpus_rematch", "mv_corpus_embeddings", "mv_corpus_topk", "mv_x8_saturation", "mv_attention_concentration", "mv_sink_census_enable", "mv_sink_census_read", "mv_set_form", "mv_get_form", "mv_form_stats", "mv_last_row_forms", "mv_corpus_row_forms",
-    "mv_set_sink_tokens", "mv_get_sink_tokens", "mv_route_stats", "mv_route_scan", "mv_corpus_route_flags", "mv_set_streams", "mv_profile_enable", "mv_profile_select", "mv_profile_read", "mv_kernel_class_name",
-    "mv_debug_encode", "mv_debug_read", "mv_test_gemm", "mv_test_gemm_pp", "mv_test_gemm_f32", "mv_test_e4m3", "mv_format_records", "mv_comm_prepare", "mv_comm_unique_id", "mv_comm_init", "mv_comm_allgather",
-    "mv_comm_destroy", "mv_comm_info", "mv_device_count",
-    "mv_tok_create", "mv_tok_encode", "mv_tok_encode_host", "mv_tok_kernel_ms", "mv_tok_destroy", "mv_tok_last_error",
-    "mv_tok_set_unicode", "mv_tok_encode_u8", "mv_tok_encode_u8_host",
-]
-
-
 class MvConfig(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
@@ -157,6 +145,81 @@ class MvConfig(C.Structure):
         ("ln_eps", C.c_float), ("max_tokens", C.c_int32), ("max_batch", C.c_int32), ("max_anchors", C.c_int32),
         ("same_idx", C.c_int32),
     ]
+
+
+# every entry include/memvul_hip.h declares (ABI_SYMBOLS: tests check the header and the .so against them): name -> (result type, argument types)
+_vp, _i32p, _P = C.c_void_p, C.POINTER(C.c_int32), C.POINTER
+_SIGNATURES = {
+    "mv_create": (C.c_int, [C.c_int, _P(MvConfig), _P(_vp)]),
+    "mv_destroy": (None, [_vp]),
+    "mv_last_error": (C.c_char_p, [_vp]),
+    "mv_sync": (C.c_int, [_vp]),
+    "mv_load_tensor": (C.c_int, [_vp, C.c_char_p, _vp, C.c_int, _P(C.c_int64), C.c_int]),
+    "mv_finalize_weights": (C.c_int, [_vp, C.c_int]),
+    "mv_anchor_reset": (C.c_int, [_vp]),
+    "mv_anchor_append": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int]),
+    "mv_anchor_count": (C.c_int, [_vp]),
+    "mv_anchor_get": (C.c_int, [_vp, _vp]),
+    "mv_anchor_set": (C.c_int, [_vp, _vp, C.c_int]),
+    "mv_forward": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "mv_forward_ragged": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "mv_forward_ragged_begin": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int)]),
+    "mv_forward_ragged_end": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "mv_encode": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "mv_match": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "mv_topk": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "mv_corpus_upload": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int]),
+    "mv_corpus_run": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mv_corpus_run_len": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "mv_corpus_results": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "mv_corpus_keep": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "mv_corpus_rematch": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mv_corpus_embeddings": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp]),
+    "mv_corpus_topk": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "mv_x8_saturation": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_int]),
+    "mv_attention_concentration": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
+    "mv_sink_census_enable": (C.c_int, [_vp, C.c_int]),
+    "mv_sink_census_read": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int]),
+    "mv_set_streams": (C.c_int, [_vp, C.c_int]),
+    "mv_set_form": (C.c_int, [_vp, C.c_int]),
+    "mv_get_form": (C.c_int, [_vp]),
+    "mv_form_stats": (C.c_int, [_vp, _P(C.c_int64), _P(C.c_int64), C.c_int]),
+    "mv_last_row_forms": (C.c_int, [_vp, _vp, C.c_int]),
+    "mv_corpus_row_forms": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp]),
+    "mv_set_sink_tokens": (C.c_int, [_vp, _i32p, C.c_int]),
+    "mv_get_sink_tokens": (C.c_int, [_vp, _i32p, C.c_int]),
+    "mv_route_stats": (C.c_int, [_vp, _P(C.c_int64), C.c_int]),
+    "mv_route_scan": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _vp]),
+    "mv_corpus_route_flags": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp]),
+    "mv_profile_enable": (C.c_int, [_vp, C.c_int]),
+    "mv_profile_select": (C.c_int, [_vp, C.c_uint32]),
+    "mv_profile_read": (C.c_int, [_vp, _P(C.c_double), _P(C.c_int64), C.c_int]),
+    "mv_kernel_class_name": (C.c_char_p, [C.c_int]),
+    "mv_debug_encode": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int]),
+    "mv_debug_read": (C.c_int, [_vp, C.c_int, _vp, C.c_int64]),
+    "mv_test_gemm": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _P(C.c_float)]),
+    "mv_test_gemm_pp": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _P(C.c_float)]),
+    "mv_test_gemm_f32": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _P(C.c_float)]),
+    "mv_test_e4m3": (C.c_int, [_vp, _vp, C.c_int64]),
+    "mv_format_records": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_char_p, _vp, _vp, C.c_int64, _P(C.c_int64)]),
+    "mv_comm_prepare": (C.c_int, [_vp]),
+    "mv_comm_unique_id": (C.c_int, [_vp, _vp, C.c_int]),
+    "mv_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int]),
+    "mv_comm_allgather": (C.c_int, [_vp, _vp, _vp, C.c_int64]),
+    "mv_comm_destroy": (C.c_int, [_vp]),
+    "mv_comm_info": (C.c_int, [_vp, _P(C.c_int), C.c_int]),
+    "mv_device_count": (C.c_int, []),
+    "mv_tok_create": (C.c_int, [C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(_vp)]),
+    "mv_tok_encode": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "mv_tok_encode_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "mv_tok_kernel_ms": (C.c_int, [_vp, _P(C.c_float)]),
+    "mv_tok_set_unicode": (C.c_int, [_vp, _vp, C.c_int]),
+    "mv_tok_encode_u8": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "mv_tok_encode_u8_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "mv_tok_destroy": (None, [_vp]),
+    "mv_tok_last_error": (C.c_char_p, [_vp]),
+}
+ABI_SYMBOLS = list(_SIGNATURES)
 
 
 _libs = {}
@@ -170,88 +233,14 @@ def load_library(path: Optional[str] = None, dev: bool = False):
     if path in _libs:
         return _libs[path]
     if not os.path.exists(path):
-        raise RuntimeError(
-            f"libmemvul_hip.so not found at {path}: build it with `python -m memvul_amd.build` "
-            "(hipcc --offload-arch=gfx950); the MemVul hot path has no CPU fallback"
-        )
+        raise RuntimeError(f"libmemvul_hip.so not found at {path}: build it with `python -m memvul_amd.build` "
+                           "(hipcc --offload-arch=gfx950); the MemVul hot path has no CPU fallback")
     try:
         # the product library as always (RTLD_GLOBAL); the development build, which a test process may load NEXT TO it, privately
         lib = C.CDLL(path, mode=C.RTLD_LOCAL if path == LIB_PATH_DEV else C.RTLD_GLOBAL)
     except OSError as e:  # pragma: no cover
         raise RuntimeError(f"cannot load {path}: {e}") from e
-    vp, i32p, f32p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)
-    P = C.POINTER
-    sig = {
-        "mv_create": (C.c_int, [C.c_int, P(MvConfig), P(vp)]),
-        "mv_destroy": (None, [vp]),
-        "mv_last_error": (C.c_char_p, [vp]),
-        "mv_sync": (C.c_int, [vp]),
-        "mv_load_tensor": (C.c_int, [vp, C.c_char_p, vp, C.c_int, P(C.c_int64), C.c_int]),
-        "mv_finalize_weights": (C.c_int, [vp, C.c_int]),
-        "mv_anchor_reset": (C.c_int, [vp]),
-        "mv_anchor_append": (C.c_int, [vp, vp, vp, C.c_int, C.c_int]),
-        "mv_anchor_count": (C.c_int, [vp]),
-        "mv_anchor_get": (C.c_int, [vp, vp]),
-        "mv_anchor_set": (C.c_int, [vp, vp, C.c_int]),
-        "mv_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
-        "mv_forward_ragged": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
-        "mv_forward_ragged_begin": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int)]),
-        "mv_forward_ragged_end": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
-        "mv_encode": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
-        "mv_match": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp]),
-        "mv_topk": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
-        "mv_corpus_upload": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int]),
-        "mv_corpus_run": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int]),
-        "mv_corpus_run_len": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int]),
-        "mv_corpus_results": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, vp]),
-        "mv_corpus_keep": (C.c_int, [vp, C.c_int, C.c_int]),
-        "mv_corpus_rematch": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int]),
-        "mv_corpus_embeddings": (C.c_int, [vp, C.c_int64, C.c_int64, vp]),
-        "mv_corpus_topk": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp]),
-        "mv_x8_saturation": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int]),
-        "mv_attention_concentration": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
-        "mv_sink_census_enable": (C.c_int, [vp, C.c_int]),
-        "mv_sink_census_read": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int]),
-        "mv_set_streams": (C.c_int, [vp, C.c_int]),
-        "mv_set_form": (C.c_int, [vp, C.c_int]),
-        "mv_get_form": (C.c_int, [vp]),
-        "mv_form_stats": (C.c_int, [vp, P(C.c_int64), P(C.c_int64), C.c_int]),
-        "mv_last_row_forms": (C.c_int, [vp, vp, C.c_int]),
-        "mv_corpus_row_forms": (C.c_int, [vp, C.c_int64, C.c_int64, vp]),
-        "mv_set_sink_tokens": (C.c_int, [vp, i32p, C.c_int]),
-        "mv_get_sink_tokens": (C.c_int, [vp, i32p, C.c_int]),
-        "mv_route_stats": (C.c_int, [vp, P(C.c_int64), C.c_int]),
-        "mv_route_scan": (C.c_int, [vp, vp, C.c_int, C.c_int, i32p, C.c_int, C.c_int, vp]),
-        "mv_corpus_route_flags": (C.c_int, [vp, C.c_int64, C.c_int64, vp]),
-        "mv_profile_enable": (C.c_int, [vp, C.c_int]),
-        "mv_profile_select": (C.c_int, [vp, C.c_uint32]),
-        "mv_profile_read": (C.c_int, [vp, P(C.c_double), P(C.c_int64), C.c_int]),
-        "mv_kernel_class_name": (C.c_char_p, [C.c_int]),
-        "mv_debug_encode": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
-        "mv_debug_read": (C.c_int, [vp, C.c_int, vp, C.c_int64]),
-        "mv_test_gemm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, P(C.c_float)]),
-        "mv_test_gemm_pp": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, P(C.c_float)]),
-        "mv_test_gemm_f32": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, P(C.c_float)]),
-        "mv_test_e4m3": (C.c_int, [vp, vp, C.c_int64]),
-        "mv_format_records": (C.c_int, [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_char_p, vp, vp, C.c_int64, P(C.c_int64)]),
-        "mv_comm_prepare": (C.c_int, [vp]),
-        "mv_comm_unique_id": (C.c_int, [vp, vp, C.c_int]),
-        "mv_comm_init": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int]),
-        "mv_comm_allgather": (C.c_int, [vp, vp, vp, C.c_int64]),
-        "mv_comm_destroy": (C.c_int, [vp]),
-        "mv_comm_info": (C.c_int, [vp, P(C.c_int), C.c_int]),
-        "mv_device_count": (C.c_int, []),
-        "mv_tok_create": (C.c_int, [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(vp)]),
-        "mv_tok_encode": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-        "mv_tok_encode_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-        "mv_tok_kernel_ms": (C.c_int, [vp, P(C.c_float)]),
-        "mv_tok_set_unicode": (C.c_int, [vp, vp, C.c_int]),
-        "mv_tok_encode_u8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-        "mv_tok_encode_u8_host": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-        "mv_tok_destroy": (None, [vp]),
-        "mv_tok_last_error": (C.c_char_p, [vp]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -260,7 +249,7 @@ def load_library(path: Optional[str] = None, dev: bool = False):
     quick = C.PyDLL(path)
     for name in ("mv_anchor_count", "mv_x8_saturation", "mv_attention_concentration"):
         fn = getattr(quick, name)
-        fn.restype, fn.argtypes = sig[name]
+        fn.restype, fn.argtypes = _SIGNATURES[name]
     lib.quick = quick
     _libs[path] = lib
     return lib
@@ -275,9 +264,38 @@ def _as(a, dtype) -> np.ndarray:
 
 
 def _outputs(B: int, G: int, P: int, want_logits: bool, want_probs: bool, want_embed: bool) -> Dict[str, Optional[np.ndarray]]:
-    """The result arrays of the forward entry points (None = not asked for; best / best_idx always)."""
+    """The result arrays of the forward entry points, in the order those take them (None = not asked for; best / best_idx always)."""
     return {"logits": np.empty((B, G, 2), np.float32) if want_logits else None, "probs": np.empty((B, G, 2), np.float32) if want_probs else None,
             "best": np.empty((B, 2), np.float32), "best_idx": np.empty((B,), np.int32), "embed": np.empty((B, P), np.float32) if want_embed else None}
+
+
+def _row_forms(f: np.ndarray) -> list:
+    """uint8 form codes, one per row (mv_last_row_forms / mv_corpus_row_forms) -> "default" / "safe"."""
+    return ["safe" if x == MV_FORM_SAFE else "default" for x in f]
+
+
+class _Redo(NamedTuple):  # what a ticket begun in the default form under MEMVUL_ON_SINK=safe keeps: its batch, scored again if the form has switched by collection
+    ids: np.ndarray
+    lens: np.ndarray
+    min_tokens: Optional[int]
+
+
+class Ticket(NamedTuple):  # what forward_by_length_begin hands out; [0] is the state, [1] what it holds, [-1] the redo record
+    state: str                     # "pending": the library has the batch; "done": it was scored at once
+    held: object                   # pending: the library's ticket (int); done: the results (_outputs)
+    B: int                         # pending: rows, and ...
+    G: int                         # ... the anchors the batch began with: what the library scatters
+    want: Tuple[bool, bool, bool]  # want_logits, want_probs, want_embed
+    redo: Optional[_Redo]
+
+
+@dataclass
+class _KeptSweep:  # the last bucketed_sweep(keep= / topk=): its row order, and the bank its stored results cover
+    n: int
+    inv: np.ndarray  # original row -> row of the length-sorted upload
+    embed: bool      # the corpus keeps its embeddings (rematch_sweep needs them)
+    epoch: int       # Engine._bank_epoch when the stored results were computed
+    covered: int     # the anchors they were computed against
 
 
 class Engine:
@@ -290,36 +308,43 @@ class Engine:
         config) or 768 (use_header=False: the pooler output, no ``_projector_single`` in the state dict).  dev: load the development
         build (tests / A/B scripts: the only one that reads DEV_SWITCHES).  sink_tokens: the sink-token list of the guarded form (what MEMVUL_SINK_TOKENS sets; it wins
         over the environment), applied by load_state_dict — it raises there unless the form is "guarded"."""
-        on_sink_policy()  # (a malformed MEMVUL_ON_SINK raises before anything is created)
-        sink_census_policy()
-        sink_tokens_policy()
-        self._sink_tokens_wanted = None if sink_tokens is None else _sink_token_list(sink_tokens)
+        for policy in (on_sink_policy, sink_census_policy, sink_tokens_policy):  # (a malformed switch raises before anything is created)
+            policy()
+        wanted = None if sink_tokens is None else _sink_token_list(sink_tokens)
         self._lib = load_library(dev=dev)
         self.P = int(proj_dim)
         self.cfg = MvConfig(vocab_size, 768, layers, 12, 3072, max_pos, type_vocab, self.P, ln_eps, max_tokens,
                             max_batch, max_anchors, same_idx)
-        h = C.c_void_p()
-        rc = self._lib.mv_create(device, C.byref(self.cfg), C.byref(h))
-        if rc != 0:
-            msg = self._lib.mv_last_error(None)
-            raise RuntimeError(f"mv_create failed ({rc}): {msg.decode() if msg else ''}")
+        self._h, h = None, C.c_void_p()
+        self._check(self._lib.mv_create(device, C.byref(self.cfg), C.byref(h)), "mv_create")
         self._h = h
         self.device = device
-        self._tickets = []  # forward_by_length_begin: batches in flight, oldest first
-        self._init_sink_state()
+        self._init_sink_state(precise=False, sink_tokens=wanted)
 
-    def _init_sink_state(self):
-        """Host state of the MEMVUL_ON_SINK fall-back (no library call: a stand-in engine can use it)."""
-        self._on_sink = on_sink_policy()
-        self._form = "default"
-        self._anchor_log = []        # the (ids, lens) of every anchor_append since the last reset: what a switch of form re-encodes the bank from
+    def _init_sink_state(self, precise: Optional[bool] = None, sink_tokens: Optional[List[int]] = None):
+        """Every attribute Engine keeps on the host besides _lib, _h, P, cfg and device, declared once (no library call: a stand-in engine calls it too; the name is
+        from when the MEMVUL_ON_SINK fall-back was all of it).  The methods below only assign to these.  precise None: a stand-in, which has no load_state_dict,
+        has said before this call whether it is."""
+        self._tickets = []            # forward_by_length_begin: the library's tickets in flight, oldest first
+        self._sink_tokens_wanted = sink_tokens  # the constructor's sink_tokens, applied by load_state_dict
+        if precise is not None:
+            self._precise = precise   # the compute dtype is MV_F16X8: the only one the monitors below speak of (load_state_dict)
+        self._dbg = None              # debug_encode: (rows, padded length, lens) of the taps debug_read hands back
+        self.comm_rank, self.comm_world = 0, 1  # comm_world: the ranks comm_allgather gathers over (comm_init)
+        # the resident corpus
+        self._corpus_k = 0            # corpus_keep's topk: the width of corpus_topk (an upload resets it)
+        self._sweep_kept: Optional[_KeptSweep] = None
+        self._bank_epoch = 0          # bumped by whatever rewrites anchors the bank already holds (anchor_reset, anchor_set, the MEMVUL_ON_SINK=safe switch), not by anchor_append
+        # the monitors (_monitors)
+        self._conc_warned = self._guard_warned = self._sat_warned = False  # _sink_monitor has tripped (warned, or switched the form); the other two have warned
+        self._census = False          # the sink census is on (sink_census_enable / MEMVUL_SINK_CENSUS=1): the sink warning names its top tokens
+        self._last_rows = 0           # rows of the last call last_row_forms() speaks of
+        # the MEMVUL_ON_SINK fall-back
+        self._on_sink = on_sink_policy()  # "warn" | "safe", read once
+        self._form = "default"        # the form the passes enqueued now run in (set_form; load_state_dict)
+        self._anchor_log = []         # the (ids, lens) of every anchor_append since the last reset: what a switch of form re-encodes the bank from
         self._bank_replayable = True  # False once anchor_set installed embeddings the binding cannot re-encode
-        self._corpus_runs = []       # the corpus_run calls since the last corpus_upload: what a switch of form sweeps once more
-        self._guard_warned = False   # the guarded form's one warning (more than GUARDED_WARN_SHARE of the sequences rescored)
-        self._last_rows = 0          # rows of the last call last_row_forms() speaks of
-        self._census = False         # the sink census is on (sink_census_enable / MEMVUL_SINK_CENSUS=1)
-        self._bank_epoch = 0         # bumped by whatever rewrites anchors the bank already holds (anchor_reset, anchor_set, the MEMVUL_ON_SINK=safe switch), not by anchor_append
-        self._sweep_kept = None      # the last bucketed_sweep(keep= / topk=): its row order, and the bank (epoch, anchor count) its stored results cover
+        self._corpus_runs = []        # the corpus_run calls since the last corpus_upload: what a switch of form sweeps once more
 
     # -- plumbing
     def _check(self, rc: int, what: str):
@@ -343,14 +368,8 @@ class Engine:
 
     # -- weights
     def load_tensor(self, name: str, arr: np.ndarray):
-        if arr.dtype == np.float16:
-            dt = MV_F16
-        elif arr.dtype in (np.int64, np.int32):
-            dt = MV_I64 if arr.dtype == np.int64 else MV_I32
-        else:
-            arr = _as(arr, np.float32)
-            dt = MV_F32
-        arr = np.ascontiguousarray(arr)
+        dt = {np.dtype(np.float16): MV_F16, np.dtype(np.int64): MV_I64, np.dtype(np.int32): MV_I32}.get(arr.dtype, MV_F32)
+        arr = _as(arr, np.float32 if dt == MV_F32 else arr.dtype)  # (every other dtype is loaded as fp32)
         shape = (C.c_int64 * arr.ndim)(*arr.shape)
         self._check(self._lib.mv_load_tensor(self._h, name.encode(), _ptr(arr), dt, shape, arr.ndim), f"mv_load_tensor({name})")
 
@@ -370,8 +389,7 @@ class Engine:
             self.set_form(wanted_form(compute_dtype))
         else:
             self._form = {v: k for k, v in FORMS.items()}.get(self._get_form(), "default")  # (MEMVUL_FORM, read by mv_create)
-        want = getattr(self, "_sink_tokens_wanted", None)
-        src = "sink_tokens"
+        want, src = self._sink_tokens_wanted, "sink_tokens"
         if want is None:
             want, src = sink_tokens_policy(), "MEMVUL_SINK_TOKENS"
         if want is not None:  # (once, after mv_finalize_weights and after the form is known)
@@ -409,17 +427,16 @@ class Engine:
     def last_row_forms(self) -> list:
         """The form ("default" / "safe") that produced each row of the last forward / forward_by_length / forward_by_length_end / encode / anchor_append, in
         that call's row order (mv_last_row_forms)."""
-        n = self._last_rows
-        f = np.empty((n,), np.uint8)
-        self._check(self._lib.mv_last_row_forms(self._h, _ptr(f), n), "mv_last_row_forms")
-        return ["safe" if x == MV_FORM_SAFE else "default" for x in f]
+        f = np.empty((self._last_rows,), np.uint8)
+        self._check(self._lib.mv_last_row_forms(self._h, _ptr(f), len(f)), "mv_last_row_forms")
+        return _row_forms(f)
 
     def corpus_row_forms(self, first: int, count: int) -> list:
         """The same for rows [first, first + count) of the resident corpus, valid after corpus_results (mv_corpus_row_forms).  After bucketed_sweep the rows are
         those of the length-sorted upload: ``np.argsort(lens, kind="stable")``."""
         f = np.empty((count,), np.uint8)
         self._check(self._lib.mv_corpus_row_forms(self._h, first, count, _ptr(f)), "mv_corpus_row_forms")
-        return ["safe" if x == MV_FORM_SAFE else "default" for x in f]
+        return _row_forms(f)
 
     # -- the sink-token list of the guarded form
     def set_sink_tokens(self, ids):
@@ -513,68 +530,79 @@ class Engine:
 
     def _census_note(self) -> str:
         """What the one-time sink warning appends with the census on: the top three tokens ("" with it off — the text then stays as it always was)."""
-        if not getattr(self, "_census", False):
-            return ""
-        rows = self.sink_census(top=3)["tokens"]
+        rows = self.sink_census(top=3)["tokens"] if self._census else []
         if not rows:
             return ""
         return "; sink census, token id (share of the flagged items): " + ", ".join(f"{r['token_id']} ({r['share_of_flagged_items']:.0%})" for r in rows)
 
-    def _check_saturation(self):
-        """Called after the host-synchronous entry points of the precise mode: warn ONCE when the fp8 planes clamped anything, and once when the concentration
-        monitor trips.  Returns True when that trip switched the engine to the safe form (MEMVUL_ON_SINK=safe): the caller redoes its call."""
-        switched = False
-        if getattr(self, "_precise", False) and not getattr(self, "_conc_warned", False) and self._form == "default":  # (the safe form keeps counting, trips nothing; the guarded form answers per sequence)
-            m, n, t = self.attention_concentration()
-            if t >= 100 and n > 0.02 * t and self._on_sink == "safe":
-                self._conc_warned = True
-                self._on_sink_trip(m, n, t)
-                switched = True
-            elif t >= 100 and n > 0.02 * t:  # systematic, not the odd head of the odd sequence
-                self._conc_warned = True
-                warnings.warn(f"MV_F16X8: in {n} of {t} (sequence, head, layer) items the [CLS] row puts more than half of a head's attention on ONE ordinary token "
-                              f"(collision mass up to {m:.2f}): the 1e-3 logit tolerance of the default form is backed by measurement for diffuse attention and "
-                              "for attention sinks on [CLS] / [SEP] only (profiles/r06_n_sink_envelope.txt: 0.8 - 2.7e-3 for such a sink); "
-                              "MEMVUL_CLS_ASIDE=0 MEMVUL_QKV_ASIDE=qkv is the most conservative form (include/memvul_hip.h mv_attention_concentration)"
-                              + self._census_note(), RuntimeWarning, stacklevel=3)
-        if getattr(self, "_precise", False) and self._form == "guarded" and not self._guard_warned:
-            seqs, resc = self.form_stats()
-            if seqs >= 100 and resc > GUARDED_WARN_SHARE * seqs:
-                self._guard_warned = True
-                warnings.warn(f"MV_F16X8, guarded form: {resc} of {seqs} sequences were encoded again in the safe form — above a share of {GUARDED_WARN_SHARE} the safe "
-                              "form (compute dtype \"safe\" / set_form(\"safe\") / MEMVUL_FORM=safe) scores the same corpus faster: a guarded sequence costs "
-                              "1 + 1.34 x that share of a default-form one, a safe-form one 1.34 (include/memvul_hip.h mv_set_form).  If the sinks sit on a few tokens "
-                              "(sink_census() names them), set_sink_tokens / MEMVUL_SINK_TOKENS sends the sequences that carry them straight to the safe form "
-                              "instead of encoding them twice", RuntimeWarning, stacklevel=3)
-        if getattr(self, "_precise", False) and not self._sat_warned:
-            n = self.x8_saturation()
-            if n:
-                self._sat_warned = True
-                warnings.warn(f"MV_F16X8: {n} activation element(s) exceeded the +-112 range of the fp8 correction planes and were "
-                              "computed at fp16 accuracy; the 1e-3 logit tolerance is not backed by measurement for this model "
-                              "(include/memvul_hip.h mv_x8_saturation; Engine.x8_saturation())", RuntimeWarning, stacklevel=3)
-        return switched
+    def _monitors(self, level: int = 3) -> bool:
+        """Called after the host-synchronous entry points of the precise mode: the three monitors below in this order, each saying its piece ONCE.  Returns True
+        when the first of them switched the engine to the safe form (MEMVUL_ON_SINK=safe): the caller redoes its call.  level: the stacklevel that attributes a
+        warning to whoever called the public method: 3 when that method calls this itself, 4 through _redo_on_switch."""
+        if not self._precise:
+            return False
+        form = self._form
+        for monitor in (self._sink_monitor, self._guard_monitor, self._saturation_monitor):
+            text = monitor()
+            if text:
+                warnings.warn(text, RuntimeWarning, stacklevel=level)
+        return self._form != form
 
-    def _on_sink_trip(self, m: float, n: int, t: int):
+    def _sink_monitor(self) -> Optional[str]:
+        """The concentration monitor in the default form (the safe form keeps counting, trips nothing; the guarded form answers per sequence): attention sinks
+        on ordinary tokens, systematic, not the odd head of the odd sequence, warn or, under MEMVUL_ON_SINK=safe, switch the form (_on_sink_trip)."""
+        m, n, t = (0.0, 0, 0) if self._conc_warned or self._form != "default" else self.attention_concentration()
+        if t < 100 or n <= 0.02 * t:
+            return None
+        self._conc_warned = True
+        seen = (f"MV_F16X8: in {n} of {t} (sequence, head, layer) items the [CLS] row puts more than half of a head's attention on ONE ordinary token "
+                f"(collision mass up to {m:.2f})")
+        if self._on_sink == "safe":
+            return seen + self._on_sink_trip()
+        return (seen + ": the 1e-3 logit tolerance of the default form is backed by measurement for diffuse attention and "
+                "for attention sinks on [CLS] / [SEP] only (profiles/r06_n_sink_envelope.txt: 0.8 - 2.7e-3 for such a sink); "
+                "MEMVUL_CLS_ASIDE=0 MEMVUL_QKV_ASIDE=qkv is the most conservative form (include/memvul_hip.h mv_attention_concentration)"
+                + self._census_note())
+
+    def _guard_monitor(self) -> Optional[str]:
+        """The guarded form's rescored share: above GUARDED_WARN_SHARE the safe form is the cheaper one."""
+        seqs, resc = (0, 0) if self._form != "guarded" or self._guard_warned else self.form_stats()
+        if seqs < 100 or resc <= GUARDED_WARN_SHARE * seqs:
+            return None
+        self._guard_warned = True
+        return (f"MV_F16X8, guarded form: {resc} of {seqs} sequences were encoded again in the safe form — above a share of {GUARDED_WARN_SHARE} the safe "
+                "form (compute dtype \"safe\" / set_form(\"safe\") / MEMVUL_FORM=safe) scores the same corpus faster: a guarded sequence costs "
+                "1 + 1.34 x that share of a default-form one, a safe-form one 1.34 (include/memvul_hip.h mv_set_form).  If the sinks sit on a few tokens "
+                "(sink_census() names them), set_sink_tokens / MEMVUL_SINK_TOKENS sends the sequences that carry them straight to the safe form "
+                "instead of encoding them twice")
+
+    def _saturation_monitor(self) -> Optional[str]:
+        """The fp8 correction planes clamped something."""
+        n = 0 if self._sat_warned else self.x8_saturation()
+        if not n:
+            return None
+        self._sat_warned = True
+        return (f"MV_F16X8: {n} activation element(s) exceeded the +-112 range of the fp8 correction planes and were "
+                "computed at fp16 accuracy; the 1e-3 logit tolerance is not backed by measurement for this model "
+                "(include/memvul_hip.h mv_x8_saturation; Engine.x8_saturation())")
+
+    def _on_sink_trip(self) -> str:
         """MEMVUL_ON_SINK=safe, the monitor has tripped: the safe form for the rest of the engine's life, the counters reset, the anchor bank encoded again in
-        that form from the ids anchor_append was given (a bank installed with anchor_set is kept: there is nothing to encode it from), one warning."""
+        that form from the ids anchor_append was given (a bank installed with anchor_set is kept: there is nothing to encode it from); returns what the one warning goes on to say."""
         self.set_form("safe")
         self.attention_concentration(reset=True)
-        self._bump_epoch()  # (the bank is encoded again below: results stored against it are stale row for row)
+        self._bank_epoch += 1  # (the bank is encoded again below: results stored against it are stale row for row)
         n_bank = self.n_anchors
         if self._bank_replayable:
-            log = self._anchor_log
             self._anchor_reset()
-            for ids, lens in log:
+            for ids, lens in self._anchor_log:
                 self._anchor_append(ids, lens)
             bank = f"the anchor bank ({n_bank} anchors) was encoded again in the safe form"
         else:
             bank = (f"the anchor bank ({n_bank} anchors) holds embeddings installed with anchor_set and was KEPT as it is: install a bank encoded in the safe form "
                     "to have both sides of the match in it") if n_bank else "the anchor bank is empty"
-        warnings.warn(f"MV_F16X8: in {n} of {t} (sequence, head, layer) items the [CLS] row puts more than half of a head's attention on ONE ordinary token "
-                      f"(collision mass up to {m:.2f}), outside the measured envelope of the default form: MEMVUL_ON_SINK=safe switched this engine to the SAFE form "
-                      f"(include/memvul_hip.h mv_set_form) for the rest of its life; {bank}; the call that tripped is redone in the safe form",
-                      RuntimeWarning, stacklevel=4)
+        return (", outside the measured envelope of the default form: MEMVUL_ON_SINK=safe switched this engine to the SAFE form "
+                f"(include/memvul_hip.h mv_set_form) for the rest of its life; {bank}; the call that tripped is redone in the safe form")
 
     # -- anchors
     def _anchor_reset(self):
@@ -583,21 +611,18 @@ class Engine:
     def _anchor_append(self, ids: np.ndarray, lens: np.ndarray):
         self._check(self._lib.mv_anchor_append(self._h, _ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1]), "mv_anchor_append")
 
-    def _bump_epoch(self):
-        self._bank_epoch = getattr(self, "_bank_epoch", 0) + 1
-
     def anchor_reset(self):
         self._anchor_reset()
         self._anchor_log, self._bank_replayable = [], True
-        self._bump_epoch()
+        self._bank_epoch += 1
 
     def anchor_append(self, ids: np.ndarray, lens: np.ndarray):
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         self._anchor_append(ids, lens)
         self._last_rows = ids.shape[0]
-        if self._on_sink == "safe" and not getattr(self, "_conc_warned", False):  # (kept only while a switch of form may still need them)
+        if self._on_sink == "safe" and not self._conc_warned:  # (kept only while a switch of form may still need them)
             self._anchor_log.append((ids.copy(), lens.copy()))
-        self._check_saturation()  # (a trip here encodes the whole bank again, these anchors included)
+        self._monitors()  # (a trip here encodes the whole bank again, these anchors included)
 
     @property
     def n_anchors(self) -> int:
@@ -617,19 +642,30 @@ class Engine:
         self._check_width(v, "anchor_set")
         self._check(self._lib.mv_anchor_set(self._h, _ptr(v), v.shape[0]), "mv_anchor_set")
         self._anchor_log, self._bank_replayable = [], False
-        self._bump_epoch()
+        self._bank_epoch += 1
 
     # -- hot loop
+    def _redo_on_switch(self, rows: int, call):
+        """One host-synchronous scoring call, `call` (it allocates its results and hands them back), of `rows` rows, and the monitors after it; when they
+        switched the engine to the safe form (MEMVUL_ON_SINK=safe) the call once more, in that form."""
+        out = call()
+        self._last_rows = rows
+        if self._monitors(level=4):
+            out = call()
+            self._monitors(level=4)  # (the safe form trips nothing: what is left to read is the saturation count)
+        return out
+
+    def _scoring(self, entry: str, ids: np.ndarray, lens: np.ndarray, want, *extra):
+        """The `call` of forward / forward_by_length: the library's `entry` (mv_forward, or mv_forward_ragged with its min_tokens) on one batch."""
+        def call():
+            out = _outputs(ids.shape[0], self.n_anchors, self.P, *want)
+            self._check(getattr(self._lib, entry)(self._h, _ptr(ids), _ptr(lens), *ids.shape, *extra, *map(_ptr, out.values())), entry)
+            return out
+        return call
+
     def forward(self, ids: np.ndarray, lens: np.ndarray, want_logits=True, want_probs=True, want_embed=False):
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
-        B, S = ids.shape
-        out = _outputs(B, self.n_anchors, self.P, want_logits, want_probs, want_embed)
-        self._check(self._lib.mv_forward(self._h, _ptr(ids), _ptr(lens), B, S, _ptr(out["logits"]), _ptr(out["probs"]), _ptr(out["best"]),
-                                         _ptr(out["best_idx"]), _ptr(out["embed"])), "mv_forward")
-        self._last_rows = B
-        if self._check_saturation():
-            return self.forward(ids, lens, want_logits, want_probs, want_embed)
-        return out
+        return self._redo_on_switch(ids.shape[0], self._scoring("mv_forward", ids, lens, (want_logits, want_probs, want_embed)))
 
     # tokens below which one pad-to-longest pass is kept as it is (a pass of a few thousand tokens leaves most of the 256 persistent workgroups idle)
     BY_LENGTH_MIN_TOKENS = 16384
@@ -643,17 +679,10 @@ class Engine:
         length is bit for bit ``forward`` at that length."""
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         B, S = ids.shape
-        if min_tokens is None:
-            min_tokens = self.BY_LENGTH_MIN_TOKENS
+        min_tokens = self.BY_LENGTH_MIN_TOKENS if min_tokens is None else min_tokens
         if B == 0 or B * S < 2 * min_tokens:
             return self.forward(ids, lens, want_logits, want_probs, want_embed)
-        out = _outputs(B, self.n_anchors, self.P, want_logits, want_probs, want_embed)
-        self._check(self._lib.mv_forward_ragged(self._h, _ptr(ids), _ptr(lens), B, S, int(min_tokens), _ptr(out["logits"]), _ptr(out["probs"]),
-                                                _ptr(out["best"]), _ptr(out["best_idx"]), _ptr(out["embed"])), "mv_forward_ragged")
-        self._last_rows = B
-        if self._check_saturation():
-            return self.forward_by_length(ids, lens, want_logits, want_probs, want_embed, min_tokens)
-        return out
+        return self._redo_on_switch(B, self._scoring("mv_forward_ragged", ids, lens, (want_logits, want_probs, want_embed), int(min_tokens)))
 
     def forward_by_length_begin(self, ids: np.ndarray, lens: np.ndarray, want_logits=True, want_probs=True, want_embed=False, min_tokens: Optional[int] = None):
         """``forward_by_length`` handed over without waiting for it (mv_forward_ragged_begin): returns a ticket for ``forward_by_length_end``.  One batch per
@@ -664,67 +693,63 @@ class Engine:
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         B, S = ids.shape
         mt = self.BY_LENGTH_MIN_TOKENS if min_tokens is None else min_tokens
-        redo = (self._form, ids, lens, bool(want_logits), bool(want_probs), bool(want_embed), min_tokens) if self._on_sink == "safe" and self._form == "default" else None
+        want = (bool(want_logits), bool(want_probs), bool(want_embed))
+        redo = _Redo(ids, lens, min_tokens) if self._on_sink == "safe" and self._form == "default" else None
         if B > 0 and B * S >= 2 * mt:
             t = C.c_int(-1)
             rc = self._lib.mv_forward_ragged_begin(self._h, _ptr(ids), _ptr(lens), B, S, int(mt), int(want_logits), int(want_probs), int(want_embed), C.byref(t))
             if rc == 0:
                 self._tickets.append(t.value)
-                return ("pending", t.value, B, self.n_anchors, bool(want_logits), bool(want_probs), bool(want_embed), redo)
+                return Ticket("pending", t.value, B, self.n_anchors, want, redo)
             if rc != -5:  # (MV_ERR_CAPACITY: below)
                 self._check(rc, "mv_forward_ragged_begin")
         out = self.forward_by_length(ids, lens, want_logits, want_probs, want_embed, min_tokens)
-        return ("done", out, None if self._form == "safe" else redo)  # (a trip inside that call: the results are the safe form's already)
+        return Ticket("done", out, B, 0, want, None if self._form == "safe" else redo)  # (a trip inside that call: the results are the safe form's already)
 
-    def _rescore(self, redo):
+    def _rescore(self, ticket: Ticket):
         """A ticket begun in the default form, collected after the switch: its batch once more, synchronously, in the safe form."""
-        _, ids, lens, want_logits, want_probs, want_embed, min_tokens = redo
-        return self.forward_by_length(ids, lens, want_logits, want_probs, want_embed, min_tokens)
+        return self.forward_by_length(ticket.redo.ids, ticket.redo.lens, *ticket.want, ticket.redo.min_tokens)
 
-    def forward_by_length_end(self, ticket):
+    def forward_by_length_end(self, ticket: Ticket):
         """The results of a ``forward_by_length_begin`` ticket.  Collecting consumes the ticket, also when this call raises.  MEMVUL_ON_SINK=safe: the monitor is
         read at EVERY collection while the engine is in the default form (that read waits for the batch in flight behind this one: the price of the guarantee
         that no result handed out after the trip comes from the default form), and a ticket begun in the default form is scored again after the switch."""
-        if ticket[0] == "done":
-            return self._rescore(ticket[2]) if ticket[2] is not None and self._form == "safe" else ticket[1]
-        _, t, B, G, want_logits, want_probs, want_embed, redo = ticket  # (G: the anchors the batch began with, what the library scatters)
+        redo = ticket.redo
+        if ticket.state == "done":
+            return self._rescore(ticket) if redo is not None and self._form == "safe" else ticket.held
+        t = ticket.held
         if not self._tickets or self._tickets[0] != t:
             raise RuntimeError("forward_by_length_end: tickets are collected in the order they were issued")
-        out = _outputs(B, G, self.P, want_logits, want_probs, want_embed)
+        out = _outputs(ticket.B, ticket.G, self.P, *ticket.want)
         self._tickets.pop(0)
-        self._check(self._lib.mv_forward_ragged_end(self._h, t, _ptr(out["logits"]), _ptr(out["probs"]), _ptr(out["best"]), _ptr(out["best_idx"]), _ptr(out["embed"])),
-                    "mv_forward_ragged_end")
-        self._last_rows = B
+        self._check(self._lib.mv_forward_ragged_end(self._h, t, *map(_ptr, out.values())), "mv_forward_ragged_end")
+        self._last_rows = ticket.B
         stale = redo is not None and self._form == "safe"  # begun before the switch: its results are the default form's
         if not self._tickets or (redo is not None and not stale):  # (the counters are read after a synchronisation of EVERY stream: with the next batch in flight that would wait for it — holding the lock)
-            stale = self._check_saturation() or stale
-        return self._rescore(redo) if stale and redo is not None else out
+            stale = self._monitors() or stale
+        return self._rescore(ticket) if stale and redo is not None else out
 
     def encode(self, ids: np.ndarray, lens: np.ndarray) -> np.ndarray:
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
-        out = np.empty((ids.shape[0], self.P), np.float32)
-        self._check(self._lib.mv_encode(self._h, _ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1], _ptr(out)), "mv_encode")
-        self._last_rows = ids.shape[0]
-        if self._check_saturation():
-            return self.encode(ids, lens)
-        return out
+
+        def call():
+            out = np.empty((ids.shape[0], self.P), np.float32)
+            self._check(self._lib.mv_encode(self._h, _ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1], _ptr(out)), "mv_encode")
+            return out
+        return self._redo_on_switch(ids.shape[0], call)
 
     def match(self, u: np.ndarray):
         u = _as(u, np.float32)
         self._check_width(u, "match")
-        B, G = u.shape[0], self.n_anchors
-        logits = np.empty((B, G, 2), np.float32)
-        probs = np.empty((B, G, 2), np.float32)
-        best = np.empty((B, 2), np.float32)
-        idx = np.empty((B,), np.int32)
-        self._check(self._lib.mv_match(self._h, _ptr(u), B, _ptr(logits), _ptr(probs), _ptr(best), _ptr(idx)), "mv_match")
-        return {"logits": logits, "probs": probs, "best": best, "best_idx": idx}
+        out = _outputs(u.shape[0], self.n_anchors, self.P, True, True, False)
+        del out["embed"]  # (the matcher has none to hand back)
+        self._check(self._lib.mv_match(self._h, _ptr(u), u.shape[0], *map(_ptr, out.values())), "mv_match")
+        return out
 
     def topk(self, u: np.ndarray, k: int):
         u = _as(u, np.float32)
         self._check_width(u, "topk")
-        p = np.empty((u.shape[0], k), np.float32)
-        i = np.empty((u.shape[0], k), np.int32)
+        p, i = np.empty((u.shape[0], k), np.float32), np.empty((u.shape[0], k), np.int32)
         self._check(self._lib.mv_topk(self._h, _ptr(u), u.shape[0], k, _ptr(p), _ptr(i)), "mv_topk")
         return p, i
 
@@ -732,10 +757,7 @@ class Engine:
     def corpus_upload(self, ids: np.ndarray, lens: np.ndarray):
         ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         self._check(self._lib.mv_corpus_upload(self._h, _ptr(ids), _ptr(lens), ids.shape[0], ids.shape[1]), "mv_corpus_upload")
-        self._corpus_n = ids.shape[0]
-        self._corpus_runs = []
-        self._corpus_k = 0        # (an upload resets mv_corpus_keep)
-        self._sweep_kept = None
+        self._corpus_runs, self._corpus_k, self._sweep_kept = [], 0, None  # (an upload resets mv_corpus_keep)
 
     def corpus_run(self, first: int, count: int, batch: int, keep_probs: bool = False, s_eff: int = 0):
         """Enqueue IRs [first, first+count) of the resident corpus in batches of `batch` (asynchronous).  s_eff > 0:
@@ -764,9 +786,7 @@ class Engine:
 
     def corpus_topk(self, first: int, count: int):
         """(P(same) fp32 [count, k], anchor index int32 [count, k]) of rows [first, first + count), k as given to corpus_keep (mv_corpus_topk)."""
-        k = getattr(self, "_corpus_k", 0)
-        p = np.empty((count, k), np.float32)
-        i = np.empty((count, k), np.int32)
+        p, i = np.empty((count, self._corpus_k), np.float32), np.empty((count, self._corpus_k), np.int32)
         self._check(self._lib.mv_corpus_topk(self._h, first, count, _ptr(p), _ptr(i)), "mv_corpus_topk")
         return p, i
 
@@ -776,8 +796,7 @@ class Engine:
         batch at that batch's length (rounded up to 64 tokens), and the results are returned in the ORIGINAL order.
         keep / topk: the corpus keeps its embeddings / the k best anchors of every row (corpus_keep), and the engine remembers the order of the upload:
         rematch_sweep() then scores the same rows against a changed bank without encoding them again, sweep_topk() returns the top-k lists."""
-        ids = np.ascontiguousarray(ids, np.int32)
-        lens = np.ascontiguousarray(lens, np.int32)
+        ids, lens = _as(ids, np.int32), _as(lens, np.int32)
         n = ids.shape[0]
         order = np.argsort(lens, kind="stable")
         self.corpus_upload(ids[order], lens[order])
@@ -791,38 +810,37 @@ class Engine:
         inv = np.empty(n, np.int64)
         inv[order] = np.arange(n)
         if keep or topk:  # (after corpus_results: a MEMVUL_ON_SINK=safe trip in there swept again, against the bank it encoded again)
-            self._sweep_kept = {"n": n, "inv": inv, "embed": bool(keep), "epoch": getattr(self, "_bank_epoch", 0), "covered": self.n_anchors}
+            self._sweep_kept = _KeptSweep(n, inv, bool(keep), self._bank_epoch, self.n_anchors)
         return best[inv], idx[inv], (ps[inv] if ps is not None else None)
 
     def rematch_sweep(self, with_probs: bool = False):
         """The rows of the last ``bucketed_sweep(..., keep=True)`` against the anchor bank as it is NOW, by the matcher alone: ``(best, idx, p_same | None)`` in
         the ORIGINAL row order, the bytes sweeping again would give.  When the bank has only been appended to since the stored results were computed (no
         anchor_reset, anchor_set or switch of form in between) and P(same) is not asked for, only the new anchors are matched and merged in."""
-        st = getattr(self, "_sweep_kept", None)
-        if st is None or not st["embed"]:
+        st = self._sweep_kept
+        if st is None or not st.embed:
             raise RuntimeError("rematch_sweep: the resident corpus keeps no embeddings — sweep it with bucketed_sweep(..., keep=True) first")
         G = self.n_anchors
-        appended = st["epoch"] == getattr(self, "_bank_epoch", 0) and G >= st["covered"] and not with_probs
-        self.corpus_rematch(0, st["n"], st["covered"] if appended else 0, keep_probs=with_probs)
-        best, idx, ps = self.corpus_results(0, st["n"], with_probs=with_probs)
-        st["epoch"], st["covered"] = getattr(self, "_bank_epoch", 0), self.n_anchors
-        inv = st["inv"]
-        return best[inv], idx[inv], (ps[inv] if ps is not None else None)
+        appended = st.epoch == self._bank_epoch and G >= st.covered and not with_probs
+        self.corpus_rematch(0, st.n, st.covered if appended else 0, keep_probs=with_probs)
+        best, idx, ps = self.corpus_results(0, st.n, with_probs=with_probs)
+        st.epoch, st.covered = self._bank_epoch, self.n_anchors
+        return best[st.inv], idx[st.inv], (ps[st.inv] if ps is not None else None)
 
     def sweep_topk(self):
         """(P(same) [n, k], anchor index [n, k]) of the last ``bucketed_sweep(..., topk=k)``, in the ORIGINAL row order."""
-        st = getattr(self, "_sweep_kept", None)
-        if st is None or not getattr(self, "_corpus_k", 0):
+        st = self._sweep_kept
+        if st is None or not self._corpus_k:
             raise RuntimeError("sweep_topk: the resident corpus keeps no top-k lists — sweep it with bucketed_sweep(..., topk=k) first")
-        p, i = self.corpus_topk(0, st["n"])
-        return p[st["inv"]], i[st["inv"]]
+        p, i = self.corpus_topk(0, st.n)
+        return p[st.inv], i[st.inv]
 
     def corpus_results(self, first: int, count: int, with_probs: bool = False):
         best = np.empty((count, 2), np.float32)
         idx = np.empty((count,), np.int32)
         ps = np.empty((count, self.n_anchors), np.float32) if with_probs else None
         self._check(self._lib.mv_corpus_results(self._h, first, count, _ptr(best), _ptr(idx), _ptr(ps)), "mv_corpus_results")
-        if self._check_saturation():  # MEMVUL_ON_SINK=safe tripped: the sweeps over the resident corpus once more, in the safe form
+        if self._monitors():  # MEMVUL_ON_SINK=safe tripped: the sweeps over the resident corpus once more, in the safe form
             runs, self._corpus_runs = self._corpus_runs, []
             for r in runs:
                 self.corpus_run(*r)
@@ -843,17 +861,14 @@ class Engine:
         return buf.raw[:n]
 
     def comm_init(self, rank: int, world: int, unique_id: Optional[bytes] = None):
-        if unique_id is None:
-            self._check(self._lib.mv_comm_init(self._h, int(rank), int(world), None, 0), "mv_comm_init")
-        else:
-            self._check(self._lib.mv_comm_init(self._h, int(rank), int(world), C.c_char_p(bytes(unique_id)), len(unique_id)), "mv_comm_init")
+        uid = None if unique_id is None else C.c_char_p(bytes(unique_id))
+        self._check(self._lib.mv_comm_init(self._h, int(rank), int(world), uid, 0 if unique_id is None else len(unique_id)), "mv_comm_init")
         self.comm_world = int(world)
 
     def comm_allgather(self, block: np.ndarray) -> np.ndarray:
         """Every rank contributes a same-shape array; returns ``[world, *block.shape]`` in rank order."""
         block = np.ascontiguousarray(block)
-        world = getattr(self, "comm_world", 1)
-        out = np.empty((world,) + block.shape, block.dtype)
+        out = np.empty((self.comm_world,) + block.shape, block.dtype)
         if block.nbytes:
             self._check(self._lib.mv_comm_allgather(self._h, _ptr(block), _ptr(out), block.nbytes), "mv_comm_allgather")
         return out
@@ -879,13 +894,8 @@ class Engine:
 
     def profile_select(self, names=None):
         """Restrict HIP-event recording to the named kernel classes (None = all)."""
-        if names is None:
-            mask = 0xFFFFFFFF
-        else:
-            all_names = [self._lib.mv_kernel_class_name(i).decode() for i in range(NUM_KERNEL_CLASSES)]
-            mask = 0
-            for nm in names:
-                mask |= 1 << all_names.index(nm)
+        all_names = names and [self._lib.mv_kernel_class_name(i).decode() for i in range(NUM_KERNEL_CLASSES)]
+        mask = 0xFFFFFFFF if names is None else sum({1 << all_names.index(nm) for nm in names})
         self._check(self._lib.mv_profile_select(self._h, mask), "mv_profile_select")
 
     def profile_read(self) -> Dict[str, Tuple[float, int]]:
@@ -911,23 +921,24 @@ class Engine:
         shape, dt = shapes[buffer]
         out = np.empty(shape, dt)
         self._check(self._lib.mv_debug_read(self._h, buffer, _ptr(out), out.nbytes), "mv_debug_read")
-        if getattr(self, "_precise", False) and buffer in self._TOKEN_AXIS:
+        if self._precise and buffer in self._TOKEN_AXIS:
             # MV_F16X8 keeps the LAST token of every sequence in row 1 and token 1 in the last token's row (the "special rows" of
             # misc_kernels.h embed_ln_kernel; only the [CLS] row's result leaves the encoder): hand the taps back in token order
             ax = self._TOKEN_AXIS[buffer]
             for b in range(B):
                 n = int(lens[b])
                 if n >= 3:
-                    idx = [slice(None)] * out.ndim
-                    idx[0] = b
-                    i1, i2 = list(idx), list(idx)
-                    i1[ax], i2[ax] = 1, n - 1
-                    t = out[tuple(i1)].copy()
-                    out[tuple(i1)] = out[tuple(i2)]
-                    out[tuple(i2)] = t
+                    rows = np.moveaxis(out[b], ax - 1, 0)  # (a view: the token axis of sequence b first)
+                    rows[[1, n - 1]] = rows[[n - 1, 1]]
         return out
 
     _TOKEN_AXIS = {0: 1, 1: 1, 2: 2, 3: 2, 4: 3, 5: 1, 6: 1, 7: 2, 8: 2, 9: 3}  # debug buffer -> its token axis (7 - 9: the lo planes of 2 - 4)
+
+    def _timed(self, entry: str, *args) -> float:
+        """A mv_test_gemm* entry: it runs its kernel `iters` times and says what one run took, in milliseconds."""
+        ms = C.c_float(0)
+        self._check(getattr(self._lib, entry)(self._h, *args, C.byref(ms)), entry)
+        return float(ms.value)
 
     def test_gemm(self, A16: np.ndarray, W16: np.ndarray, bias: Optional[np.ndarray], variant: int = 0, iters: int = 1):
         A16, W16 = _as(A16, np.float16), _as(W16, np.float16)
@@ -935,10 +946,7 @@ class Engine:
         N = W16.shape[0]
         bias = None if bias is None else _as(bias, np.float32)
         out = np.empty((M, N), np.float32)
-        ms = C.c_float(0)
-        self._check(self._lib.mv_test_gemm(self._h, variant, M, N, K, _ptr(A16), _ptr(W16), _ptr(bias), _ptr(out), iters,
-                                           C.byref(ms)), "mv_test_gemm")
-        return out, float(ms.value)
+        return out, self._timed("mv_test_gemm", variant, M, N, K, _ptr(A16), _ptr(W16), _ptr(bias), _ptr(out), iters)
 
     def test_gemm_pp(self, A: np.ndarray, W: np.ndarray, bias: np.ndarray, x8=False, iters: int = 1):
         """The persistent FFN-1 kernel on fp32 operands (unit row statistics): fp16 gelu(A W^T + bias) [M][N]; x8: the MV_F16X8
@@ -949,10 +957,7 @@ class Engine:
         N = W.shape[0]
         out = np.empty((M, N), np.float16)
         out8 = np.empty((M, 2 * N), np.uint8) if x8 else None
-        ms = C.c_float(0)
-        self._check(self._lib.mv_test_gemm_pp(self._h, int(x8), M, N, K, _ptr(A), _ptr(W), _ptr(bias), _ptr(out), _ptr(out8), iters,
-                                              C.byref(ms)), "mv_test_gemm_pp")
-        return out, out8, float(ms.value)
+        return out, out8, self._timed("mv_test_gemm_pp", int(x8), M, N, K, _ptr(A), _ptr(W), _ptr(bias), _ptr(out), _ptr(out8), iters)
 
     GEMM_F32_ACTS = {"bias": 0, "gelu": 1, "res": 2}
 
@@ -964,10 +969,7 @@ class Engine:
         bias = None if bias is None else _as(bias, np.float32)
         res = None if res is None else _as(res, np.float32)
         out = np.empty((M, N), np.float32)
-        ms = C.c_float(0)
-        self._check(self._lib.mv_test_gemm_f32(self._h, self.GEMM_F32_ACTS[act], M, N, K, _ptr(A), _ptr(W), _ptr(bias), _ptr(res), _ptr(out), iters,
-                                               C.byref(ms)), "mv_test_gemm_f32")
-        return out, float(ms.value)
+        return out, self._timed("mv_test_gemm_f32", self.GEMM_F32_ACTS[act], M, N, K, _ptr(A), _ptr(W), _ptr(bias), _ptr(res), _ptr(out), iters)
 
 
 def _token_string(vocab, token_id: int) -> str:
@@ -987,11 +989,9 @@ def device_count() -> int:
 
 def e4m3_bits(x: np.ndarray) -> np.ndarray:
     """OCP e4m3fn bits of fp32 values through the library's host-side encoder (the one that builds the MV_F16X8 weight planes)."""
-    lib = load_library()
     x = _as(x, np.float32)
     out = np.empty(x.shape, np.uint8)
-    rc = lib.mv_test_e4m3(_ptr(x), _ptr(out), x.size)
-    if rc != 0:
+    if load_library().mv_test_e4m3(_ptr(x), _ptr(out), x.size) != 0:
         raise RuntimeError("mv_test_e4m3 failed")
     return out
 
@@ -1034,12 +1034,14 @@ class DeviceWordPiece:
         lb, lo = _packed(list(literals))
         t = C.c_void_p()
         self.device = -1 if device is None else int(device)
-        rc = self._lib.mv_tok_create(self.device, vb, _ptr(vo), len(vo) - 1, lb, _ptr(lo), len(lo) - 1, int(unk_id), int(cls_id), int(sep_id),
-                                     int(max_chars_per_word), 1 if lowercase else 0, C.byref(t))
-        if rc != 0:
-            msg = self._lib.mv_tok_last_error(None)
-            raise RuntimeError(f"mv_tok_create failed ({rc}): {msg.decode() if msg else ''}")
+        self._check(self._lib.mv_tok_create(self.device, vb, _ptr(vo), len(vo) - 1, lb, _ptr(lo), len(lo) - 1, int(unk_id), int(cls_id), int(sep_id),
+                                            int(max_chars_per_word), 1 if lowercase else 0, C.byref(t)), "mv_tok_create")
         self._t = t
+
+    def _check(self, rc: int, what: str):
+        if rc != 0:
+            msg = self._lib.mv_tok_last_error(self._t)  # (None while mv_tok_create runs: the library's own last error)
+            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
 
     def close(self):
         if getattr(self, "_t", None):
@@ -1058,10 +1060,7 @@ class DeviceWordPiece:
         if n < 0:
             raise ValueError(f"{name}: offsets must hold n + 1 values")
         ids, lens, status = np.zeros((n, int(max_length)), np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
-        rc = fn(self._t, packed, _ptr(off), n, int(max_length), 1 if add_special else 0, _ptr(ids), _ptr(lens), _ptr(status))
-        if rc != 0:
-            msg = self._lib.mv_tok_last_error(self._t)
-            raise RuntimeError(f"{name} failed ({rc}): {msg.decode() if msg else ''}")
+        self._check(fn(self._t, packed, _ptr(off), n, int(max_length), 1 if add_special else 0, _ptr(ids), _ptr(lens), _ptr(status)), name)
         return ids, lens, status
 
     def encode(self, packed: bytes, offsets, max_length: int, add_special: bool = True):
@@ -1088,10 +1087,7 @@ class DeviceWordPiece:
             e = e.view(np.uint8).reshape(-1, 16)
         if e.dtype != np.uint8 or e.ndim != 2 or e.shape[1] != 16:
             raise ValueError("set_unicode: entries must be uint8 [n, 16] or CODE_POINT_DTYPE [n]")
-        rc = self._lib.mv_tok_set_unicode(self._t, _ptr(e), len(e))
-        if rc != 0:
-            msg = self._lib.mv_tok_last_error(self._t)
-            raise RuntimeError(f"mv_tok_set_unicode failed ({rc}): {msg.decode() if msg else ''}")
+        self._check(self._lib.mv_tok_set_unicode(self._t, _ptr(e), len(e)), "mv_tok_set_unicode")
 
     def encode_u8(self, packed: bytes, offsets, max_length: int, add_special: bool = True):
         """The UTF-8 kernel (mv_tok_encode_u8): as ``encode`` for text in UTF-8; status 0 tokenised, 1 an added-token literal, 2 malformed or not covered."""

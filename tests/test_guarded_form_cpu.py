@@ -64,6 +64,19 @@ class _Lib(sf._Lib):
             self.seqs += self.rows
             self.rescored += int(self.rows * self.flag_share)
 
+    def _row_forms(self, out, n):
+        for r in range(n):  # (every third row "safe": the decoding is visible)
+            C.cast(out, C.POINTER(C.c_uint8))[r] = binding.MV_FORM_SAFE if r % 3 == 1 else binding.MV_FORM_DEFAULT
+        return 0
+
+    def mv_last_row_forms(self, h, out, n):
+        self.log.append(("last_row_forms", n))
+        return self._row_forms(out, n)
+
+    def mv_corpus_row_forms(self, h, first, count, out):
+        self.log.append(("corpus_row_forms", first, count))
+        return self._row_forms(out, count)
+
 
 def _guarded_engine(lib):
     eng = sf.StandInEngine(lib)

@@ -38,7 +38,7 @@ class _Quick:
         return self.lib.n_anchors
 
     def mv_x8_saturation(self, h, n, reset):
-        n._obj.value = 0
+        n._obj.value = self.lib.saturated
         return 0
 
     def mv_attention_concentration(self, h, m, n, t, reset):
@@ -51,11 +51,12 @@ class _Quick:
 
 class _Lib:
     """What binding.Engine calls of libmemvul_hip.so, as a recorder: every pass-like call adds `items` (sequence, head, layer) items to the monitor, `sink_share`
-    of them over the threshold, and writes the form it ran in into its first output value."""
+    of them over the threshold, and writes the form it ran in into its first output value.  `saturated`: what mv_x8_saturation counts; `begin_rc`: what
+    mv_forward_ragged_begin answers instead of taking the batch (-5: MV_ERR_CAPACITY)."""
 
-    def __init__(self, items=200, sink_share=0.5):
+    def __init__(self, items=200, sink_share=0.5, saturated=0, begin_rc=0):
         self.form, self.log, self.n_anchors, self.over, self.total = 0, [], 0, 0, 0
-        self.items, self.sink_share = items, sink_share
+        self.items, self.sink_share, self.saturated, self.begin_rc = items, sink_share, saturated, begin_rc
         self.quick = _Quick(self)
         self.next_ticket, self.in_flight = 0, {}
 
@@ -103,6 +104,9 @@ class _Lib:
         return 0
 
     def mv_forward_ragged_begin(self, h, ids, lens, B, S, mt, wl, wp, we, ticket):
+        if self.begin_rc:
+            self.log.append(("begin_refused", self.begin_rc))
+            return self.begin_rc
         t = self.next_ticket
         self.next_ticket += 1
         self.in_flight[t] = self.form
@@ -135,6 +139,11 @@ class _Lib:
         self.log.append(("encode", self.form))
         self._pass()
         self._stamp(out)
+        return 0
+
+    def mv_match(self, h, u, B, logits, probs, best, idx):
+        self.log.append(("match", B))
+        self._stamp(best)
         return 0
 
 
