@@ -835,6 +835,30 @@ class Engine:
         p, i = self.corpus_topk(0, st.n)
         return p[st.inv], i[st.inv]
 
+    def sweep_embeddings(self, first: int = 0, count: Optional[int] = None, chunk: int = 65536) -> np.ndarray:
+        """fp32 [count, P]: the kept embeddings of rows [first, first + count) of the last ``bucketed_sweep(..., keep=True)``, in the ORIGINAL row order.  The
+        upload is sorted by length, so the rows asked for lie scattered over it: the span that holds them is downloaded ``chunk`` rows at a time (corpus_embeddings)
+        and the wanted rows are picked out — one pass over the corpus when all rows are asked for."""
+        st = self._sweep_kept
+        if st is None or not st.embed:
+            raise RuntimeError("sweep_embeddings: the resident corpus keeps no embeddings — sweep it with bucketed_sweep(..., keep=True) first")
+        count = st.n - first if count is None else count
+        if first < 0 or count < 0 or first + count > st.n or chunk < 1:
+            raise ValueError(f"sweep_embeddings: rows [{first}, {first} + {count}) of {st.n}, chunk {chunk}")
+        out = np.empty((count, self.P), np.float32)
+        if count == 0:
+            return out
+        pos = st.inv[first:first + count]
+        lo, hi = int(pos.min()), int(pos.max()) + 1
+        where = np.full(hi - lo, -1, np.int64)  # row of the upload -> row of `out`
+        where[pos - lo] = np.arange(count)
+        for s0 in range(lo, hi, chunk):
+            w = where[s0 - lo:s0 - lo + chunk]
+            take = w >= 0
+            if take.any():
+                out[w[take]] = self.corpus_embeddings(s0, len(w))[take]
+        return out
+
     def corpus_results(self, first: int, count: int, with_probs: bool = False):
         best = np.empty((count, 2), np.float32)
         idx = np.empty((count,), np.int32)

@@ -1,4 +1,4 @@
-"""Build libmemvul_hip.so and libmemvul_tok_u8.so (gfx950) in-tree with hipcc.  No torch involved."""
+"""Build libmemvul_hip.so, libmemvul_tok_u8.so and libmemvul_retrieve.so (gfx950) in-tree with hipcc.  No torch involved."""
 from __future__ import annotations
 
 import os
@@ -22,6 +22,12 @@ TOK_LIB_NAME = "libmemvul_tok_u8.so"
 LIB_PATH_TOK = os.path.join(LIB_DIR, TOK_LIB_NAME)
 TOK_SOURCES = ["wordpiece_u8.hip"]
 TOK_HEADERS = ["wordpiece.h"]
+# per-anchor retrieval over a kept corpus (csrc/retrieve.hip, csrc/report_topk.h, include/memvul_retrieve.h): a stand-alone library — nothing links against it and it
+# links against nothing of this tree, so neither the source fingerprint nor the kernel map of the libraries above moves with it
+RETRIEVE_LIB_NAME = "libmemvul_retrieve.so"
+LIB_PATH_RETRIEVE = os.path.join(LIB_DIR, RETRIEVE_LIB_NAME)
+RETRIEVE_SOURCES = ["retrieve.hip"]
+RETRIEVE_HEADERS = ["report_topk.h", os.path.join(ROOT, "include", "memvul_retrieve.h")]
 SOURCES = ["engine.hip"]
 KERNEL_HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", "wordpiece.h"]
 # the host code of the library: engine.hip includes each of these parts once, in this order
@@ -211,38 +217,59 @@ def is_stale(extra_flags=(), dev: bool = False) -> bool:
     return want["cc"] != "unknown" and have.get("cc") != want["cc"]
 
 
-def tok_is_stale() -> bool:
-    """is_stale for libmemvul_tok_u8.so (its own stamp: its sources are wordpiece_u8.hip and wordpiece.h)."""
-    stamp_path = LIB_PATH_TOK + ".stamp"
-    if not os.path.exists(LIB_PATH_TOK) or not os.path.exists(stamp_path):
+def _side_is_stale(lib_path: str, sources, headers) -> bool:
+    """is_stale for a library with sources and a stamp of its own."""
+    stamp_path = lib_path + ".stamp"
+    if not os.path.exists(lib_path) or not os.path.exists(stamp_path):
         return True
     with open(stamp_path) as f:
         have = dict(line.split(" ", 1) for line in f.read().strip().splitlines() if " " in line)
     cc = _compiler_id()
     import hashlib
 
-    if have.get("src") != source_fingerprint((), TOK_SOURCES, TOK_HEADERS):
+    if have.get("src") != source_fingerprint((), sources, headers):
         return True
     return cc is not None and have.get("cc") != hashlib.sha256(cc).hexdigest()
+
+
+def tok_is_stale() -> bool:
+    """is_stale for libmemvul_tok_u8.so (its own stamp: its sources are wordpiece_u8.hip and wordpiece.h)."""
+    return _side_is_stale(LIB_PATH_TOK, TOK_SOURCES, TOK_HEADERS)
+
+
+def retrieve_is_stale() -> bool:
+    """is_stale for libmemvul_retrieve.so (its own stamp: retrieve.hip, report_topk.h, include/memvul_retrieve.h)."""
+    return _side_is_stale(LIB_PATH_RETRIEVE, RETRIEVE_SOURCES, RETRIEVE_HEADERS)
+
+
+def _build_side(lib_path: str, lib_name: str, sources, headers, verbose: bool) -> str:
+    import hashlib
+
+    os.makedirs(LIB_DIR, exist_ok=True)
+    cmd = [hipcc_path(), f"--offload-arch={ARCH}", *FLAGS, f"-Wl,-soname,{lib_name}", *[os.path.join(CSRC, s) for s in sources], "-o", lib_path + ".tmp"]
+    if verbose:
+        print("[memvul_amd.build]", " ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    cc = _compiler_id()
+    with open(lib_path + ".stamp.tmp", "w") as f:
+        f.write("src %s\ncc %s\n" % (source_fingerprint((), sources, headers), hashlib.sha256(cc).hexdigest() if cc is not None else "unknown"))
+    os.replace(lib_path + ".tmp", lib_path)
+    os.replace(lib_path + ".stamp.tmp", lib_path + ".stamp")
+    return lib_path
 
 
 def build_tok(force: bool = False, verbose: bool = True) -> str:
     """Compile libmemvul_tok_u8.so for gfx950; returns its path."""
     if not force and not tok_is_stale():
         return LIB_PATH_TOK
-    import hashlib
+    return _build_side(LIB_PATH_TOK, TOK_LIB_NAME, TOK_SOURCES, TOK_HEADERS, verbose)
 
-    os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [hipcc_path(), f"--offload-arch={ARCH}", *FLAGS, f"-Wl,-soname,{TOK_LIB_NAME}", *[os.path.join(CSRC, s) for s in TOK_SOURCES], "-o", LIB_PATH_TOK + ".tmp"]
-    if verbose:
-        print("[memvul_amd.build]", " ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    cc = _compiler_id()
-    with open(LIB_PATH_TOK + ".stamp.tmp", "w") as f:
-        f.write("src %s\ncc %s\n" % (source_fingerprint((), TOK_SOURCES, TOK_HEADERS), hashlib.sha256(cc).hexdigest() if cc is not None else "unknown"))
-    os.replace(LIB_PATH_TOK + ".tmp", LIB_PATH_TOK)
-    os.replace(LIB_PATH_TOK + ".stamp.tmp", LIB_PATH_TOK + ".stamp")
-    return LIB_PATH_TOK
+
+def build_retrieve(force: bool = False, verbose: bool = True) -> str:
+    """Compile libmemvul_retrieve.so for gfx950; returns its path."""
+    if not force and not retrieve_is_stale():
+        return LIB_PATH_RETRIEVE
+    return _build_side(LIB_PATH_RETRIEVE, RETRIEVE_LIB_NAME, RETRIEVE_SOURCES, RETRIEVE_HEADERS, verbose)
 
 
 def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool = False) -> str:
@@ -282,14 +309,17 @@ def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool =
 
 
 def build_all(force: bool = False, verbose: bool = True):
-    """Both builds, compiled side by side (two hipcc processes), after the library both link against."""
+    """Both builds, compiled side by side (two hipcc processes), after the library both link against; libmemvul_retrieve.so, which stands alone, beside them.
+    Returns the paths of the two builds of libmemvul_hip.so (LIB_PATH_RETRIEVE is where the third library lies)."""
     from concurrent.futures import ThreadPoolExecutor
 
     build_tok(force, verbose)
-    with ThreadPoolExecutor(2) as ex:
+    with ThreadPoolExecutor(3) as ex:
+        side = ex.submit(build_retrieve, force, verbose)
         futs = [ex.submit(build, force, verbose, (), d) for d in (False, True)]
+        side.result()
         return [f.result() for f in futs]
 
 
 if __name__ == "__main__":
-    print("\n".join(build_all(force="--force" in sys.argv)))
+    print("\n".join(build_all(force="--force" in sys.argv) + [LIB_PATH_RETRIEVE]))

@@ -200,6 +200,8 @@ class ModelMemory(Model):
         self._engine = Engine(self._device_index, vocab_size=vocab_size, layers=layers, max_pos=max_pos, type_vocab=type_vocab,
                               same_idx=self._same_idx, **opts)
         self._engine.load_state_dict(sd, cd)
+        self._matcher_weight = np.ascontiguousarray(sd["_projector.weight"], np.float32) if "_projector.weight" in sd else None  # (anchor_reports hands it to its index)
+        self._drop_report_index()
         # torch's contract (AllenNLP's Model._load unpacks it): every tensor the engine needs was found by mv_load_tensor /
         # mv_finalize_weights (they fail otherwise); keys it has no use for — the BertModel's own pooler copy, position_ids — are
         # not "unexpected" to a model that declares no parameters of its own
@@ -361,6 +363,7 @@ class ModelMemory(Model):
         last = len(arrays["lens"]) if last is None else last
         lens = np.ascontiguousarray(arrays["lens"][first:last], np.int32)
         self._kept_rows = None
+        self._drop_report_index()  # (it indexed the sweep this one replaces)
         if len(lens) == 0:
             return np.zeros((0, 2), np.float32), np.zeros((0,), np.int32), None
         ids = arrays["ids"][first:last, :int(lens.max())]
@@ -389,6 +392,40 @@ class ModelMemory(Model):
         best, best_idx, p_same = self.engine.rematch_sweep(with_probs=with_probs)
         self._score_arrays(arrays, first, last, best)
         return best, best_idx, p_same
+
+    def _drop_report_index(self):
+        index, self._report_index = getattr(self, "_report_index", None), None
+        if index is not None:
+            index.close()
+
+    def anchor_reports(self, arrays: Dict[str, Any], k: int, first: int = 0, last: Optional[int] = None, vectors=None, labels: Optional[List[str]] = None,
+                       index_factory=None) -> List[Dict[str, Any]]:
+        """The other direction of the match, over the rows of the last ``sweep_arrays(..., keep=True)``: for every anchor of the bank as it is NOW — or for every
+        row of ``vectors`` (fp32 [Q, P], e.g. ``engine.encode(...)`` of a fresh CVE description), named by ``labels`` — the k issue reports with the highest
+        P(same): ``[{"anchor": label, "reports": [{"Issue_Url", "row", "prob"}, ...]}, ...]``, ``row`` numbered as in ``arrays``.  The ranking runs on the GPU
+        (retrieve.ReportIndex; ``index_factory(device, proj_dim, matcher_weight, same_idx)`` builds it) over an index that is filled once per kept sweep and
+        dropped when another sweep replaces it; P(same) is bit for bit the matcher's."""
+        from . import retrieve
+
+        last = len(arrays["lens"]) if last is None else last
+        if getattr(self, "_kept_rows", None) != (first, last):
+            raise RuntimeError("anchor_reports(): no kept sweep of these rows — call sweep_arrays(arrays, first, last, keep=True) first (the resident corpus keeps "
+                               "its embeddings only when asked to)")
+        if vectors is None:
+            vectors = self.engine.anchor_get()
+            if labels is None:
+                labels = self._golden_labels
+        vectors = np.ascontiguousarray(vectors, np.float32)
+        if labels is None:
+            labels = [str(g) for g in range(len(vectors))]
+        if len(labels) != len(vectors):
+            raise ValueError(f"anchor_reports(): {len(labels)} labels for {len(vectors)} vectors")
+        if getattr(self, "_report_index", None) is None:
+            if getattr(self, "_matcher_weight", None) is None:
+                raise RuntimeError("anchor_reports(): the state dict held no _projector.weight")
+            self._report_index = retrieve.ReportIndex.from_sweep(self.engine, self._matcher_weight, self._same_idx, index_factory=index_factory)
+        p, rows = self._report_index.query(vectors, k)
+        return retrieve.format_reports(list(labels), arrays["urls"], p, rows, first)
 
     def format_records_json(self, labels: List[str], urls: List[str], p_same: np.ndarray) -> str:
         """``json.dumps(make_output_human_readable(...))`` of one batch, byte for byte, built from arrays: the line
