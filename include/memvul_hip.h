@@ -382,7 +382,20 @@ const char* mv_kernel_class_name(int cls);
  * the folded 1/8.  The pass takes the path its size selects — persistent kernels or the small-pass kernels — with last-layer pruning
  * off and the final LayerNorm applied, so buffer 0 is the normalised output of layer n_layers.  MV_FORM_GUARDED is ignored here: the taps show the default
  * form, nothing is rescored.  An MV_F32 handle has buffers 0 and 10 only: its Q, K, V, context and intermediate are fp32 planes, and mv_debug_read of the
- * fp16 taps 1 - 9 returns MV_ERR_INVALID with a message that says so.) */
+ * fp16 taps 1 - 9 returns MV_ERR_INVALID with a message that says so.)
+ * The raw planes of the persistent path, in the engine's own row order (rows 0 and 1 of a sequence hold its [CLS] and its LAST token; T = B*Sp tokens):
+ * 11 x8, the stream's fp8 planes, bytes [T][2*768] = [lo8 | hi8] per row; 12 st_lo fp16 [2 B][768], 2^11 x the stream's low parts of the special rows, compact
+ * [2 b + row]; 13 lnstats and 14 lnpart fp32 [T][3][2], per row and 256-column tile the (sum, sum of squares) of the stream at the layer's input / after the
+ * output projection; 15 ctx8 bytes [T][2*768]; 16 cls_lo fp16, compact [2 b + row][N], 2^11 x the special rows' low parts of the context (N = 768) or of the GELU
+ * output (N = 3072) — at most 2 B * 3072 elements; 17 h8 bytes [T][2*3072]; 18 vlo_sp fp16 [B*12][64][2], 2^11 x the low parts of V of the special rows; 19 xlo
+ * fp16 [T][768], the stream's lo plane (MV_F16 only); 20 cls_corr fp32, compact [2 b + row][N] with the N of the last launch that took a row term, 2^11 x that
+ * term; 21 tile_both int32 [ceil(T / 256)], the per-row-tile flags of the [CLS]-row form (written only by a pass of padded length 256 / 512 in that form).
+ * The per-token planes 11, 13 - 15, 17 and 19 may be read up to the end of the pass' last 256-row tile (T rounded up to 256 rows: the persistent GEMMs compute
+ * those rows like any other; no token lives there, the embedding kernel leaves them as the pass before left them, and a pass that MEMVUL_DEBUG_STOP ended
+ * between a residual GEMM and the launch that writes the matching vstats leaves them with a stream and statistics that do not belong together).
+ * After an ordinary mv_debug_encode they hold what the last layer and the final LayerNorm left (buffer 1 is then the NORMALISED stream); the development build's
+ * MEMVUL_DEBUG_STOP=k ends the pass after the first k launch groups of its last layer, without the final LayerNorm, so that every plane is what that launch
+ * wrote.  A buffer that does not exist in the handle's compute dtype (11, 12, 15 - 18, 20, 21: MV_F16X8; 19: MV_F16) answers MV_ERR_STATE. */
 int mv_debug_encode(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int n_layers);
 int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes);
 /* Stand-alone GEMM check/bench on caller data: C[M,N] = A[M,K] (fp16 bits) x W[N,K]^T (fp16 bits)

@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmemvul_hip.so")
 LIB_PATH_DEV = os.path.join(_HERE, "lib", "libmemvul_hip_dev.so")  # the -DMEMVUL_DEV_SWITCHES build (memvul_amd/build.py): tests and A/B scripts only
-DEV_SWITCHES = ("MEMVUL_GEMM_TILE", "MEMVUL_SHORT_VLO", "MEMVUL_RASTER", "MEMVUL_GN_MAX", "MEMVUL_NUM_CU")  # read by that build alone
+DEV_SWITCHES = ("MEMVUL_GEMM_TILE", "MEMVUL_SHORT_VLO", "MEMVUL_RASTER", "MEMVUL_GN_MAX", "MEMVUL_NUM_CU", "MEMVUL_DEBUG_STOP")  # read by that build alone
 
 MV_F32, MV_F16, MV_BF16, MV_I32, MV_I64 = 0, 1, 2, 3, 4
 MV_F16X8 = 6  # compute dtype only ("precise"): fp16 MFMA sweep + one fp8 (e4m3) correction sweep per GEMM (include/memvul_hip.h)
@@ -934,13 +934,28 @@ class Engine:
         S = ids.shape[1]
         self._dbg = (ids.shape[0], (S + 63) // 64 * 64 if S <= 256 else (S + 127) // 128 * 128, lens.copy())  # engine.hip padded_len
 
-    def debug_read(self, buffer: int) -> np.ndarray:
+    def debug_read(self, buffer: int, pad_rows: bool = False) -> np.ndarray:
+        """pad_rows (the per-token raw planes 11, 13 - 15, 17, 19 only): the rows PAST the pass' B * Sp tokens, up to the end of its last 256-row tile, as
+        [rows, width] in the engine's order — rows no token lives in, which the persistent GEMMs compute like any other."""
         B, Sp, lens = self._dbg
+        if pad_rows:
+            width, dt = {11: (2 * 768, np.uint8), 13: (6, np.float32), 14: (6, np.float32), 15: (2 * 768, np.uint8), 17: (2 * 3072, np.uint8), 19: (768, np.float16)}[buffer]
+            T = B * Sp
+            full = np.empty(((T + 255) // 256 * 256, width), dt)
+            self._check(self._lib.mv_debug_read(self._h, buffer, _ptr(full), full.nbytes), "mv_debug_read")
+            return full[T:]
         shapes = {
             0: ((B, Sp, 768), np.float32), 1: ((B, Sp, 768), np.float16), 2: ((B, 12, Sp, 64), np.float16),
             3: ((B, 12, Sp, 64), np.float16), 4: ((B, 12, 64, Sp), np.float16), 5: ((B, Sp, 768), np.float16),
             6: ((B, Sp, 3072), np.float16), 7: ((B, 12, Sp, 64), np.float16), 8: ((B, 12, Sp, 64), np.float16), 9: ((B, 12, 64, Sp), np.float16),
             10: ((B, self.P), np.float32),
+            # the raw planes of the persistent path (include/memvul_hip.h; what a pass stopped by MEMVUL_DEBUG_STOP leaves).  Per-token planes come back in token
+            # order like 0 - 9; the COMPACT special-row buffers 12, 16, 18, 20 stay in the engine's [2 b + row] order: row 0 = the [CLS] token, row 1 = the LAST
+            # token of sequence b (token 1 when the sequence has fewer than 3).  16 and 20 are flat: their row pitch is the N of the launch that wrote them
+            # (768 / 2304 / 3072), so rows are x[:2 * B * N].reshape(2 * B, N)
+            11: ((B, Sp, 2 * 768), np.uint8), 12: ((2 * B, 768), np.float16), 13: ((B, Sp, 3, 2), np.float32), 14: ((B, Sp, 3, 2), np.float32),
+            15: ((B, Sp, 2 * 768), np.uint8), 16: ((2 * B * 3072,), np.float16), 17: ((B, Sp, 2 * 3072), np.uint8), 18: ((B, 12, 64, 2), np.float16),
+            19: ((B, Sp, 768), np.float16), 20: ((2 * B * 3072,), np.float32), 21: (((B * Sp + 255) // 256,), np.int32),
         }
         shape, dt = shapes[buffer]
         out = np.empty(shape, dt)
@@ -956,7 +971,8 @@ class Engine:
                     rows[[1, n - 1]] = rows[[n - 1, 1]]
         return out
 
-    _TOKEN_AXIS = {0: 1, 1: 1, 2: 2, 3: 2, 4: 3, 5: 1, 6: 1, 7: 2, 8: 2, 9: 3}  # debug buffer -> its token axis (7 - 9: the lo planes of 2 - 4)
+    # debug buffer -> its token axis (7 - 9: the lo planes of 2 - 4; 11, 13 - 15, 17: the per-token raw planes)
+    _TOKEN_AXIS = {0: 1, 1: 1, 2: 2, 3: 2, 4: 3, 5: 1, 6: 1, 7: 2, 8: 2, 9: 3, 11: 1, 13: 1, 14: 1, 15: 1, 17: 1}
 
     def _timed(self, entry: str, *args) -> float:
         """A mv_test_gemm* entry: it runs its kernel `iters` times and says what one run took, in milliseconds."""

@@ -359,9 +359,13 @@ int final_ln(mv_handle* h, Work& wk, const PassPlan& p, const float* g, const fl
 // A layer of the persistent path: five launches (+ the row terms; + the sink census).  pend_g / pend_b: gamma / beta of the LayerNorm whose statistics are
 // pending in wk.lnstats (the embedding's, or the previous layer's second one) — the output projection applies it; wk.lnstats = vstats of the layer's input
 // rows, wk.lnpart = of the rows after the output projection; no statistics kernel in between (gemm_pp.h)
-int persistent_layer(mv_handle* h, Work& wk, const PassPlan& p, const PassForm& pf, int l, const int32_t* d_ids, const int32_t* d_lens, const float* pend_g, const float* pend_b) {
+// groups: the launch groups to run (5 = the layer; fewer only from mv_debug_encode of the development build, encode_dev: 1 the QKV projection, 2 + attention, 3 + the
+// output projection, 4 + FFN-1)
+int persistent_layer(mv_handle* h, Work& wk, const PassPlan& p, const PassForm& pf, int l, const int32_t* d_ids, const int32_t* d_lens, const float* pend_g, const float* pend_b,
+                     int groups = 5) {
   const LayerW& w = h->L[l];
   if (int rc = launch_qkv(h, wk, p, w, false)) return rc;
+  if (groups < 2) return MV_OK;
   // the sink census: the layers whose attention launch feeds the concentration monitor, and only where it is attached (a rescoring pass counts nothing twice)
   if (h->census && p.x8 && pf.monitor) {
     ProfScope ps(h, wk.stream, KC_ATTENTION);
@@ -371,8 +375,11 @@ int persistent_layer(mv_handle* h, Work& wk, const PassPlan& p, const PassForm& 
   }
   // K3: attention (cls_as: + the context's special rows' low parts for the output projection's row term)
   if (int rc = launch_attention(h, wk, d_lens, p.B, p.Sp, p.x8, p.cls_as, pf)) return rc;
+  if (groups < 3) return MV_OK;
   if (int rc = launch_out_proj(h, wk, p, w, pend_g, pend_b)) return rc;
+  if (groups < 4) return MV_OK;
   if (int rc = launch_ffn1(h, wk, p, w)) return rc;
+  if (groups < 5) return MV_OK;
   return launch_ffn2(h, wk, p, w);
 }
 
@@ -462,6 +469,9 @@ int pruned_last_layer(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w
 int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_lens, int min_len, int B, int S_in, int n_layers, float* u_out,
                const PassForm& pf = PassForm(), bool full = false, int pitch = 0) {  // min_len: the shortest sequence of the pass as the HOST knows it (Pass::min_len; 0 = unknown)
   if (pitch <= 0) pitch = S_in;
+  // mv_debug_encode of the development build with its stop switch set (mv_handle::dbg_stop): the pass ends after that many launch groups of its last layer
+  const int stop = full ? h->dbg_stop : 0;
+  if (stop && h->f32) return fail(h, MV_ERR_STATE, "mv_debug_encode: the stop inside a layer exists on the persistent path of MV_F16 / MV_F16X8 only");
   if (h->f32) return encode_f32_dev(h, wk, d_ids, d_lens, B, S_in, n_layers, u_out, pitch);  // MV_F32: no forms, no monitors, no pruning
   const mv_config& c = h->cfg;
   PassPlan p{};
@@ -473,6 +483,7 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
   h->dbg_B = B;
   h->dbg_Sp = p.Sp;
   p.big = pp_selected(h, p.Mpad);
+  if (stop && !p.big) return fail(h, MV_ERR_STATE, "mv_debug_encode: the stop inside a layer exists on the persistent path only (this pass takes the small-pass kernels)");
   p.x8 = h->precise;
   p.safe = p.x8 && pf.safe;
   p.prune = !full && h->cls_prune && u_out && n_layers == c.layers && n_layers > 0;
@@ -504,11 +515,13 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
   }
   // persistent path: the LayerNorm whose statistics are pending in the vstats buffers — gamma / beta the next residual GEMM applies
   const float *pend_g = h->embg, *pend_b = h->embb;
+  if (stop && n_layers == 0) return MV_OK;  // the embedding kernel's planes as it left them
   if (p.big && n_layers == 0) { if (int rc = final_ln(h, wk, p, pend_g, pend_b)) return rc; }
   for (int l = 0; l < n_layers; ++l) {
     const LayerW& w = h->L[l];
     const bool last = (l == n_layers - 1);
     if (last && p.prune) return pruned_last_layer(h, wk, p, w, d_lens, pend_g, pend_b, u_out);
+    if (last && stop) return persistent_layer(h, wk, p, pf, l, d_ids, d_lens, pend_g, pend_b, stop);  // no final LayerNorm, no pooler: the raw planes stay
     if (int rc = p.big ? persistent_layer(h, wk, p, pf, l, d_ids, d_lens, pend_g, pend_b) : small_layer(h, wk, p, w, d_lens)) return rc;
     if (!p.big) continue;
     pend_g = w.ln2g; pend_b = w.ln2b;

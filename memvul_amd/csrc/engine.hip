@@ -332,6 +332,7 @@ struct mv_handle {
 
   // debug
   int dbg_B = 0, dbg_Sp = 0;
+  int dbg_stop = 0;  // development build only (read_switches): mv_debug_encode ends inside its last layer, after this many launch groups (encode_dev); 0 = off
 
   Comm comm;  // the multi-GPU exchange (comm.h)
 };
@@ -417,6 +418,10 @@ int read_switches(mv_handle* h) {
     if (!env_int("MEMVUL_GN_MAX", 1, 12, &h->pp_gn_max)) return MV_ERR_INVALID;
     if (!env_int("MEMVUL_RASTER", 0, 1, &h->pp_raster)) return MV_ERR_INVALID;
     if (!env_int("MEMVUL_NUM_CU", 1, h->num_cu, &h->num_cu)) return MV_ERR_INVALID;
+    //   MEMVUL_DEBUG_STOP 1 .. 5: mv_debug_encode(ids, lens, n) runs n - 1 whole layers, then only the first k launch groups of layer n - 1 (1 the QKV projection with
+    //                     its row term, 2 + attention, 3 + the output projection, 4 + FFN-1, 5 + FFN-2) and NO final LayerNorm (nor with n = 0): every workspace buffer
+    //                     keeps what the last launch left in it, for mv_debug_read (persistent path, MV_F16 / MV_F16X8)
+    if (!env_int("MEMVUL_DEBUG_STOP", 1, 5, &h->dbg_stop)) return MV_ERR_INVALID;
   }
 #endif
   return MV_OK;
@@ -954,7 +959,7 @@ int mv_debug_encode(mv_handle* h, const int32_t* ids, const int32_t* lens, int B
 int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes) try {
   if (!h || !dst || bytes <= 0) return MV_ERR_INVALID;
   Work& wk = h->work[0];  // (mv_debug_encode's set)
-  const int64_t T = (int64_t)h->dbg_B * h->dbg_Sp;
+  const int64_t T = (int64_t)h->dbg_B * h->dbg_Sp, Tp = round_up(T, 256);
   const void* src = nullptr;
   int64_t avail = 0;
   if (h->f32 && buffer >= 1 && buffer <= 9)
@@ -971,6 +976,19 @@ int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes) try {
     case 8: src = wk.k_lo; avail = T * MV_HIDDEN * 2; break;
     case 9: src = wk.vt_lo; avail = T * MV_HIDDEN * 2; break;
     case 10: src = wk.u; avail = (int64_t)h->dbg_B * h->P * 4; break;
+    // the raw planes of the persistent path (include/memvul_hip.h); the compact special-row buffers hold 2 rows per sequence; the per-token planes can be
+    // read to the end of the pass' last 256-row tile (Tp rows: the persistent GEMMs compute the rows past B*Sp like any other)
+    case 11: src = wk.x8; avail = Tp * 2 * MV_HIDDEN; break;
+    case 12: src = wk.st_lo; avail = (int64_t)2 * h->dbg_B * MV_HIDDEN * 2; break;
+    case 13: src = wk.lnstats; avail = Tp * 6 * 4; break;
+    case 14: src = wk.lnpart; avail = Tp * 6 * 4; break;
+    case 15: src = wk.ctx8; avail = Tp * 2 * MV_HIDDEN; break;
+    case 16: src = wk.cls_lo; avail = (int64_t)2 * h->dbg_B * MV_INTER * 2; break;
+    case 17: src = wk.h8; avail = Tp * 2 * MV_INTER; break;
+    case 18: src = wk.vlo_sp; avail = (int64_t)h->dbg_B * MV_HEADS * MV_HEAD_DIM * 2 * 2; break;
+    case 19: src = wk.xlo; avail = Tp * MV_HIDDEN * 2; break;
+    case 20: src = wk.cls_corr; avail = (int64_t)2 * h->dbg_B * MV_INTER * 4; break;
+    case 21: src = wk.tile_both; avail = (int64_t)((T + 255) / 256) * 4; break;
     default: return fail(h, MV_ERR_INVALID, "mv_debug_read: unknown buffer");
   }
   if (!src) return fail(h, MV_ERR_STATE, "mv_debug_read: this buffer does not exist in this compute dtype");

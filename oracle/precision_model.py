@@ -141,42 +141,54 @@ def _wside_term(ah8, wl8, A):
     raise ValueError(mode)
 
 
+def _mm_planes(afmt, ah, ah8, al8, W, sp_lo=None, rows=None, A=None, q_row_term=True):
+    """The MV_F16X8 product of ``_mm`` from the A operand's PLANES as the engine holds them (tests/gemm_stage_kit.py hands over what a launch was given):
+    ``ah`` the fp16 plane, ``ah8`` / ``al8`` the e4m3 planes de-scaled (hi8 2^-X8_ACT_SHIFT, lo8 2^-(11 + X8_ACT_SHIFT)), all float64 [B, S, K] (or [M, K]
+    without a row term); ``W`` the float64 weight, rounded here (_w_planes).  ``sp_lo`` (float64 [B, R, K]): the fp16 value of 2^11 x the low part of the
+    rows ``rows`` [B, R] of each sequence — the operand of their row term; None = no row term.  ``afmt`` as in _mm.  ``A``: the unrounded operand, read
+    only by the model-side W_SIDE_MODE "tophalf"."""
+    wh, wh8, wl8 = _w_planes(W)
+    out = ah @ wh.T + _wside_term(ah8, wl8, ah + al8 if A is None else A)
+
+    def cls_term(cols):
+        if sp_lo is not None and ah.ndim == 3:
+            bi = np.arange(ah.shape[0])
+            for j in range(rows.shape[1]):
+                r = rows[:, j]
+                if j and (r == rows[:, 0]).all():
+                    continue
+                out[bi, r, cols] += (sp_lo[:, j] @ wh[cols].T) / 2048.0
+
+    if afmt == "f16x8w":  # the weight-side term only (gemm_pp.h x8_terms = 1)
+        cls_term(slice(None))
+        return out
+    if afmt != "f16x8":   # packed QKV weight [3 H][K]: the A-side term only in the Q / K / V block (gemm_pp.h x8_aside_mask)
+        Hb = W.shape[0] // 3
+        b = "qkv".index(afmt[-1])
+        out[..., b * Hb:(b + 1) * Hb] += al8 @ wh8[b * Hb:(b + 1) * Hb].T
+        if b != 0 or q_row_term:  # the engine forms the [CLS] row's term of the QKV projection only when the Q block lacks the A-side term (encoder_pass.h encode_dev:
+            for o in range(3):  # K and V of the [CLS] token are one key among S); the launch skips it in the block that swept both terms
+                if o != b:
+                    cls_term(slice(o * Hb, (o + 1) * Hb))
+        return out
+    return out + al8 @ wh8.T
+
+
 def _mm(afmt, wfmt, A, W, cls_lo=None, rows=None):
     """A @ W^T as the engine forms it.  Both operands "f16x8" (MV_F16X8): ONE fp16 sweep + two fp8 (e4m3) correction sweeps
     into the same fp32 accumulators,  A_hi W_hi + A_lo8 W_hi8 + A_hi8 W_lo8;  otherwise each operand is rounded on its own.
     ``cls_lo`` (the [CLS]-row form, engine.hip cls_aside; A is [B, S, K]): wherever the sweep carried the weight-side term only, row 0 of
     every sequence — its [CLS] token — gets the A-side term from a skinny fp16 GEMM  fp16(2^11 A_lo) fp16(W)^T 2^-11  with A_lo taken from
     the operand's lo fp16 plane ("lo16": the raw stream) or its lo8 plane ("lo8": context, GELU output).  ``rows`` (int [B, R], round 6): the rows of
-    each sequence that get the term instead of row 0 alone (e.g. the [CLS] and the [SEP] token)."""
+    each sequence that get the term instead of row 0 alone (e.g. the [CLS] and the [SEP] token).  The arithmetic on the planes is _mm_planes."""
     if afmt in ("f16x8", "f16x8w", "f16x8q", "f16x8k", "f16x8v") and wfmt == "f16x8":
         ah, ah8, al8 = _x8_planes(A, X8_ACT_SHIFT)
-        wh, wh8, wl8 = _w_planes(W)
-        out = ah @ wh.T + _wside_term(ah8, wl8, A)
-
-        def cls_term(cols):
-            if cls_lo and A.ndim == 3:
-                rr = np.zeros((A.shape[0], 1), np.int64) if rows is None else rows
-                bi = np.arange(A.shape[0])
-                for j in range(rr.shape[1]):
-                    r = rr[:, j]
-                    if j and (r == rr[:, 0]).all():
-                        continue
-                    lo = _f16(A[bi, r] - ah[bi, r]) if cls_lo == "lo16" else al8[bi, r]
-                    out[bi, r, cols] += (_f16(lo * 2048.0) @ wh[cols].T) / 2048.0
-
-        if afmt == "f16x8w":  # the weight-side term only (gemm_pp.h x8_terms = 1)
-            cls_term(slice(None))
-            return out
-        if afmt != "f16x8":   # packed QKV weight [3 H][K]: the A-side term only in the Q / K / V block (gemm_pp.h x8_aside_mask)
-            Hb = W.shape[0] // 3
-            b = "qkv".index(afmt[-1])
-            out[..., b * Hb:(b + 1) * Hb] += al8 @ wh8[b * Hb:(b + 1) * Hb].T
-            if b != 0 or rows is not None:  # the engine forms the [CLS] row's term of the QKV projection only when the Q block lacks the A-side term (encoder_pass.h encode_dev:
-                for o in range(3):  # K and V of the [CLS] token are one key among S); the launch skips it in the block that swept both terms
-                    if o != b:
-                        cls_term(slice(o * Hb, (o + 1) * Hb))
-            return out
-        return out + al8 @ wh8.T
+        sp_lo, rr = None, rows
+        if cls_lo and A.ndim == 3:
+            rr = np.zeros((A.shape[0], 1), np.int64) if rows is None else rows
+            bi = np.arange(A.shape[0])
+            sp_lo = np.stack([_f16((_f16(A[bi, rr[:, j]] - ah[bi, rr[:, j]]) if cls_lo == "lo16" else al8[bi, rr[:, j]]) * 2048.0) for j in range(rr.shape[1])], 1)
+        return _mm_planes(afmt, ah, ah8, al8, W, sp_lo, rr, A, q_row_term=rows is not None)
     return FORMATS[afmt](A) @ FORMATS[wfmt](W).T
 
 
