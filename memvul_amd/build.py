@@ -1,4 +1,4 @@
-"""Build libmemvul_hip.so, libmemvul_tok_u8.so and libmemvul_retrieve.so (gfx950) in-tree with hipcc.  No torch involved."""
+"""Build libmemvul_hip.so (product and development build), libmemvul_tok_u8.so, libmemvul_retrieve.so and libmemvul_claims.so (gfx950) in-tree with hipcc.  No torch involved."""
 from __future__ import annotations
 
 import os
@@ -28,6 +28,11 @@ RETRIEVE_LIB_NAME = "libmemvul_retrieve.so"
 LIB_PATH_RETRIEVE = os.path.join(LIB_DIR, RETRIEVE_LIB_NAME)
 RETRIEVE_SOURCES = ["retrieve.hip"]
 RETRIEVE_HEADERS = ["report_topk.h", os.path.join(ROOT, "include", "memvul_retrieve.h")]
+# per-anchor claims over a kept corpus (csrc/claims.hip, csrc/claim_sweep.h, include/memvul_claims.h): stand-alone in the same way, with sources and a stamp of its own
+CLAIMS_LIB_NAME = "libmemvul_claims.so"
+LIB_PATH_CLAIMS = os.path.join(LIB_DIR, CLAIMS_LIB_NAME)
+CLAIMS_SOURCES = ["claims.hip"]
+CLAIMS_HEADERS = ["claim_sweep.h", os.path.join(ROOT, "include", "memvul_claims.h")]
 SOURCES = ["engine.hip"]
 KERNEL_HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", "wordpiece.h"]
 # the host code of the library: engine.hip includes each of these parts once, in this order
@@ -242,6 +247,11 @@ def retrieve_is_stale() -> bool:
     return _side_is_stale(LIB_PATH_RETRIEVE, RETRIEVE_SOURCES, RETRIEVE_HEADERS)
 
 
+def claims_is_stale() -> bool:
+    """is_stale for libmemvul_claims.so (its own stamp: claims.hip, claim_sweep.h, include/memvul_claims.h)."""
+    return _side_is_stale(LIB_PATH_CLAIMS, CLAIMS_SOURCES, CLAIMS_HEADERS)
+
+
 def _build_side(lib_path: str, lib_name: str, sources, headers, verbose: bool) -> str:
     import hashlib
 
@@ -270,6 +280,13 @@ def build_retrieve(force: bool = False, verbose: bool = True) -> str:
     if not force and not retrieve_is_stale():
         return LIB_PATH_RETRIEVE
     return _build_side(LIB_PATH_RETRIEVE, RETRIEVE_LIB_NAME, RETRIEVE_SOURCES, RETRIEVE_HEADERS, verbose)
+
+
+def build_claims(force: bool = False, verbose: bool = True) -> str:
+    """Compile libmemvul_claims.so for gfx950; returns its path."""
+    if not force and not claims_is_stale():
+        return LIB_PATH_CLAIMS
+    return _build_side(LIB_PATH_CLAIMS, CLAIMS_LIB_NAME, CLAIMS_SOURCES, CLAIMS_HEADERS, verbose)
 
 
 def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool = False) -> str:
@@ -309,17 +326,18 @@ def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool =
 
 
 def build_all(force: bool = False, verbose: bool = True):
-    """Both builds, compiled side by side (two hipcc processes), after the library both link against; libmemvul_retrieve.so, which stands alone, beside them.
-    Returns the paths of the two builds of libmemvul_hip.so (LIB_PATH_RETRIEVE is where the third library lies)."""
+    """Both builds, compiled side by side (two hipcc processes), after the library both link against; libmemvul_retrieve.so and libmemvul_claims.so, which stand
+    alone, beside them.  Returns the paths of the two builds of libmemvul_hip.so (LIB_PATH_RETRIEVE and LIB_PATH_CLAIMS are where the other two lie)."""
     from concurrent.futures import ThreadPoolExecutor
 
     build_tok(force, verbose)
-    with ThreadPoolExecutor(3) as ex:
-        side = ex.submit(build_retrieve, force, verbose)
+    with ThreadPoolExecutor(4) as ex:
+        sides = [ex.submit(build_retrieve, force, verbose), ex.submit(build_claims, force, verbose)]
         futs = [ex.submit(build, force, verbose, (), d) for d in (False, True)]
-        side.result()
+        for side in sides:
+            side.result()
         return [f.result() for f in futs]
 
 
 if __name__ == "__main__":
-    print("\n".join(build_all(force="--force" in sys.argv) + [LIB_PATH_RETRIEVE]))
+    print("\n".join(build_all(force="--force" in sys.argv) + [LIB_PATH_TOK, LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS]))

@@ -394,9 +394,34 @@ class ModelMemory(Model):
         return best, best_idx, p_same
 
     def _drop_report_index(self):
+        """Both indexes over the kept sweep (anchor_reports', anchor_claims') and the host copy of its embeddings they are filled from."""
         index, self._report_index = getattr(self, "_report_index", None), None
         if index is not None:
             index.close()
+        index, self._claim_index = getattr(self, "_claim_index", None), None
+        if index is not None:
+            index.close()
+        self._kept_embed = None
+
+    def _kept_source(self):
+        """What ``from_sweep`` of either index reads the kept embeddings from: the engine, with its download remembered on the host until BOTH indexes are filled or
+        another sweep replaces this one — whichever index is asked for second is filled without a second download (2 KB per row of host memory meanwhile)."""
+        owner, engine = self, self.engine
+
+        class _Kept:
+            device, P = engine.device, engine.P
+
+            def sweep_embeddings(self, first=0, count=None, chunk=65536):
+                if getattr(owner, "_kept_embed", None) is None:
+                    owner._kept_embed = engine.sweep_embeddings(0, None, chunk)
+                e = owner._kept_embed
+                return e[first:None if count is None else first + count]
+
+        return _Kept()
+
+    def _forget_kept_embed(self):
+        if getattr(self, "_report_index", None) is not None and getattr(self, "_claim_index", None) is not None:
+            self._kept_embed = None
 
     def anchor_reports(self, arrays: Dict[str, Any], k: int, first: int = 0, last: Optional[int] = None, vectors=None, labels: Optional[List[str]] = None,
                        index_factory=None) -> List[Dict[str, Any]]:
@@ -423,9 +448,42 @@ class ModelMemory(Model):
         if getattr(self, "_report_index", None) is None:
             if getattr(self, "_matcher_weight", None) is None:
                 raise RuntimeError("anchor_reports(): the state dict held no _projector.weight")
-            self._report_index = retrieve.ReportIndex.from_sweep(self.engine, self._matcher_weight, self._same_idx, index_factory=index_factory)
+            self._report_index = retrieve.ReportIndex.from_sweep(self._kept_source(), self._matcher_weight, self._same_idx, index_factory=index_factory)
+            self._forget_kept_embed()
         p, rows = self._report_index.query(vectors, k)
         return retrieve.format_reports(list(labels), arrays["urls"], p, rows, first)
+
+    def anchor_claims(self, arrays: Dict[str, Any], thres=0.5, first: int = 0, last: Optional[int] = None, vectors=None, labels: Optional[List[str]] = None,
+                      grid=None, index_factory=None) -> List[Dict[str, Any]]:
+        """The reference's decision rule (predict_memory.py:170-177: ``prob >= thres``) per anchor, over the rows of the last ``sweep_arrays(..., keep=True)``: for
+        every anchor of the bank as it is NOW — or for every row of ``vectors`` (fp32 [Q, P]), named by ``labels`` — EVERY issue report with P(same) >= ``thres``
+        (a number, or one per vector): ``[{"anchor", "thres", "claimed", "positives", "reports": [{"Issue_Url", "row", "prob"}, ...]}, ...]``, reports ranked
+        (P descending, row ascending), ``positives`` counted from ``arrays["same"]``.  grid (a list of thresholds, or "reference" = np.arange(0.5, 0.9, 0.01)): also
+        ``"grid": [{"thres", "claimed", "positives"}, ...]`` and ``"best_thres"``, the per-anchor find_best_thres (custom_metric.py:35-52: best F1, ``>=``, the
+        last threshold wins a tie).  Runs on the GPU (claims.ClaimIndex; ``index_factory(device, proj_dim, matcher_weight, same_idx)`` builds it) over an index
+        that is filled once per kept sweep — a further device copy of the embeddings, 2 KB per row — and dropped when another sweep replaces it."""
+        from . import claims
+
+        last = len(arrays["lens"]) if last is None else last
+        if getattr(self, "_kept_rows", None) != (first, last):
+            raise RuntimeError("anchor_claims(): no kept sweep of these rows — call sweep_arrays(arrays, first, last, keep=True) first (the resident corpus keeps "
+                               "its embeddings only when asked to)")
+        if vectors is None:
+            vectors = self.engine.anchor_get()
+            if labels is None:
+                labels = self._golden_labels
+        vectors = np.ascontiguousarray(vectors, np.float32)
+        if labels is None:
+            labels = [str(g) for g in range(len(vectors))]
+        if len(labels) != len(vectors):
+            raise ValueError(f"anchor_claims(): {len(labels)} labels for {len(vectors)} vectors")
+        positive = np.ascontiguousarray(np.asarray(arrays["same"][first:last], bool))
+        if getattr(self, "_claim_index", None) is None:
+            if getattr(self, "_matcher_weight", None) is None:
+                raise RuntimeError("anchor_claims(): the state dict held no _projector.weight")
+            self._claim_index = claims.ClaimIndex.from_sweep(self._kept_source(), self._matcher_weight, self._same_idx, index_factory=index_factory, classes=positive)
+            self._forget_kept_embed()
+        return claims.claims_of(self._claim_index, list(labels), arrays["urls"], vectors, thres, positive, first, grid)
 
     def format_records_json(self, labels: List[str], urls: List[str], p_same: np.ndarray) -> str:
         """``json.dumps(make_output_human_readable(...))`` of one batch, byte for byte, built from arrays: the line
