@@ -1,4 +1,5 @@
-"""Build libmemvul_hip.so (product and development build), libmemvul_tok_u8.so, libmemvul_retrieve.so and libmemvul_claims.so (gfx950) in-tree with hipcc.  No torch involved."""
+"""Build libmemvul_hip.so (product and development build), libmemvul_tok_u8.so, libmemvul_retrieve.so, libmemvul_claims.so and libmemvul_bank.so (gfx950) in-tree with
+hipcc.  No torch involved."""
 from __future__ import annotations
 
 import os
@@ -33,6 +34,11 @@ CLAIMS_LIB_NAME = "libmemvul_claims.so"
 LIB_PATH_CLAIMS = os.path.join(LIB_DIR, CLAIMS_LIB_NAME)
 CLAIMS_SOURCES = ["claims.hip"]
 CLAIMS_HEADERS = ["claim_sweep.h", os.path.join(ROOT, "include", "memvul_claims.h")]
+# the anchor-bank audit over a kept corpus (csrc/bank.hip, csrc/bank_cover.h, include/memvul_bank.h): stand-alone in the same way, with sources and a stamp of its own
+BANK_LIB_NAME = "libmemvul_bank.so"
+LIB_PATH_BANK = os.path.join(LIB_DIR, BANK_LIB_NAME)
+BANK_SOURCES = ["bank.hip"]
+BANK_HEADERS = ["bank_cover.h", os.path.join(ROOT, "include", "memvul_bank.h")]
 SOURCES = ["engine.hip"]
 KERNEL_HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", "wordpiece.h"]
 # the host code of the library: engine.hip includes each of these parts once, in this order
@@ -252,6 +258,11 @@ def claims_is_stale() -> bool:
     return _side_is_stale(LIB_PATH_CLAIMS, CLAIMS_SOURCES, CLAIMS_HEADERS)
 
 
+def bank_is_stale() -> bool:
+    """is_stale for libmemvul_bank.so (its own stamp: bank.hip, bank_cover.h, include/memvul_bank.h)."""
+    return _side_is_stale(LIB_PATH_BANK, BANK_SOURCES, BANK_HEADERS)
+
+
 def _build_side(lib_path: str, lib_name: str, sources, headers, verbose: bool) -> str:
     import hashlib
 
@@ -287,6 +298,13 @@ def build_claims(force: bool = False, verbose: bool = True) -> str:
     if not force and not claims_is_stale():
         return LIB_PATH_CLAIMS
     return _build_side(LIB_PATH_CLAIMS, CLAIMS_LIB_NAME, CLAIMS_SOURCES, CLAIMS_HEADERS, verbose)
+
+
+def build_bank(force: bool = False, verbose: bool = True) -> str:
+    """Compile libmemvul_bank.so for gfx950; returns its path."""
+    if not force and not bank_is_stale():
+        return LIB_PATH_BANK
+    return _build_side(LIB_PATH_BANK, BANK_LIB_NAME, BANK_SOURCES, BANK_HEADERS, verbose)
 
 
 def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool = False) -> str:
@@ -326,13 +344,14 @@ def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool =
 
 
 def build_all(force: bool = False, verbose: bool = True):
-    """Both builds, compiled side by side (two hipcc processes), after the library both link against; libmemvul_retrieve.so and libmemvul_claims.so, which stand
-    alone, beside them.  Returns the paths of the two builds of libmemvul_hip.so (LIB_PATH_RETRIEVE and LIB_PATH_CLAIMS are where the other two lie)."""
+    """Both builds, compiled side by side (two hipcc processes), after the library both link against; libmemvul_retrieve.so, libmemvul_claims.so and
+    libmemvul_bank.so, which stand alone, beside them.  Returns the paths of the two builds of libmemvul_hip.so (LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS and LIB_PATH_BANK
+    are where the other three lie)."""
     from concurrent.futures import ThreadPoolExecutor
 
     build_tok(force, verbose)
-    with ThreadPoolExecutor(4) as ex:
-        sides = [ex.submit(build_retrieve, force, verbose), ex.submit(build_claims, force, verbose)]
+    with ThreadPoolExecutor(5) as ex:
+        sides = [ex.submit(build_retrieve, force, verbose), ex.submit(build_claims, force, verbose), ex.submit(build_bank, force, verbose)]
         futs = [ex.submit(build, force, verbose, (), d) for d in (False, True)]
         for side in sides:
             side.result()
@@ -340,4 +359,4 @@ def build_all(force: bool = False, verbose: bool = True):
 
 
 if __name__ == "__main__":
-    print("\n".join(build_all(force="--force" in sys.argv) + [LIB_PATH_TOK, LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS]))
+    print("\n".join(build_all(force="--force" in sys.argv) + [LIB_PATH_TOK, LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS, LIB_PATH_BANK]))

@@ -394,11 +394,14 @@ class ModelMemory(Model):
         return best, best_idx, p_same
 
     def _drop_report_index(self):
-        """Both indexes over the kept sweep (anchor_reports', anchor_claims') and the host copy of its embeddings they are filled from."""
+        """The indexes over the kept sweep (anchor_reports', anchor_claims', anchor_bank_audit's) and the host copy of its embeddings they are filled from."""
         index, self._report_index = getattr(self, "_report_index", None), None
         if index is not None:
             index.close()
         index, self._claim_index = getattr(self, "_claim_index", None), None
+        if index is not None:
+            index.close()
+        index, self._bank_index = getattr(self, "_bank_index", None), None
         if index is not None:
             index.close()
         self._kept_embed = None
@@ -484,6 +487,38 @@ class ModelMemory(Model):
             self._claim_index = claims.ClaimIndex.from_sweep(self._kept_source(), self._matcher_weight, self._same_idx, index_factory=index_factory, classes=positive)
             self._forget_kept_embed()
         return claims.claims_of(self._claim_index, list(labels), arrays["urls"], vectors, thres, positive, first, grid)
+
+    def anchor_bank_audit(self, arrays: Dict[str, Any], thres=0.5, first: int = 0, last: Optional[int] = None, candidates=None,
+                          candidate_labels: Optional[List[str]] = None, w_pos: int = 1, w_neg: int = 1, max_rounds: Optional[int] = None, candidate_thres=None,
+                          top: int = 20, index_factory=None) -> Dict[str, Any]:
+        """The bank as a whole, over the rows of the last ``sweep_arrays(..., keep=True)`` and the anchors as they are NOW, each at its own threshold (``thres``: a
+        number, or one per anchor — e.g. the ``best_thres`` of ``anchor_claims``): one dict (bank.audit_of) with the union decision ("claimed by at least one
+        anchor") and its confusion matrix, per anchor what it claims, what ONLY it claims and the union's F1 without it, the ``top`` overlapping pairs by Jaccard,
+        and the greedy order (gain = w_pos * new positives - w_neg * new negatives) in which the bank would be rebuilt.  candidates (fp32 [K, P], e.g.
+        ``engine.encode(...)`` of CVE descriptions; thresholds ``candidate_thres``, default the first anchor's): the bank's anchors are fixed and "greedy" ranks the
+        candidates by what each adds beyond the bank.  Runs on the GPU (bank.BankAudit; ``index_factory(device, proj_dim, matcher_weight, same_idx)`` builds it)
+        over an index that is filled once per kept sweep — from the same download as the other two indexes while that is still held — and dropped with them."""
+        from . import bank
+
+        last = len(arrays["lens"]) if last is None else last
+        if getattr(self, "_kept_rows", None) != (first, last):
+            raise RuntimeError("anchor_bank_audit(): no kept sweep of these rows — call sweep_arrays(arrays, first, last, keep=True) first (the resident corpus keeps "
+                               "its embeddings only when asked to)")
+        vectors = np.ascontiguousarray(self.engine.anchor_get(), np.float32)
+        labels = list(self._golden_labels)
+        if len(labels) != len(vectors):
+            raise ValueError(f"anchor_bank_audit(): {len(labels)} labels for {len(vectors)} anchors")
+        if np.ndim(thres) != 0 and np.shape(thres) != (len(vectors),):
+            raise ValueError(f"anchor_bank_audit(): thres: a number, or one per anchor ({len(vectors)}), not shape {list(np.shape(thres))}")
+        if not np.isfinite(np.asarray(thres, np.float64)).all():
+            raise ValueError("anchor_bank_audit(): a threshold is not finite")
+        positive = np.ascontiguousarray(np.asarray(arrays["same"][first:last], bool))
+        if getattr(self, "_bank_index", None) is None:
+            if getattr(self, "_matcher_weight", None) is None:
+                raise RuntimeError("anchor_bank_audit(): the state dict held no _projector.weight")
+            self._bank_index = bank.BankAudit.from_sweep(self._kept_source(), self._matcher_weight, self._same_idx, index_factory=index_factory, classes=positive)
+            self._forget_kept_embed()
+        return bank.run_audit(self._bank_index, labels, vectors, thres, positive, candidates, candidate_labels, candidate_thres, w_pos, w_neg, max_rounds, top)
 
     def format_records_json(self, labels: List[str], urls: List[str], p_same: np.ndarray) -> str:
         """``json.dumps(make_output_human_readable(...))`` of one batch, byte for byte, built from arrays: the line
