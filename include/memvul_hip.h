@@ -395,7 +395,15 @@ const char* mv_kernel_class_name(int cls);
  * between a residual GEMM and the launch that writes the matching vstats leaves them with a stream and statistics that do not belong together).
  * After an ordinary mv_debug_encode they hold what the last layer and the final LayerNorm left (buffer 1 is then the NORMALISED stream); the development build's
  * MEMVUL_DEBUG_STOP=k ends the pass after the first k launch groups of its last layer, without the final LayerNorm, so that every plane is what that launch
- * wrote.  A buffer that does not exist in the handle's compute dtype (11, 12, 15 - 18, 20, 21: MV_F16X8; 19: MV_F16) answers MV_ERR_STATE. */
+ * wrote.  A buffer that does not exist in the handle's compute dtype (11, 12, 15 - 18, 20, 21: MV_F16X8; 19: MV_F16) answers MV_ERR_STATE.
+ * The tail taps, development build with MEMVUL_DEBUG_TAIL=1 only (the product library answers "unknown buffer"): mv_debug_encode never prunes its last layer, so these
+ * are filled by an ORDINARY pruned pass on workspace set 0 (mv_encode, mv_forward), which then copies the B real rows each launch of the pruned last layer's
+ * [CLS] tail wrote into an arena of its own — the tail overwrites c32 and pooled in place.  22 c32 fp32 [B][768] and 23 c16 fp16 [B][768] as cls_gather_kernel
+ * left them; 24 cq fp32 [B][768], the [CLS] query (1/8 folded); 25 the single-query attention's context [B][768], fp32 in MV_F16X8, fp16 in MV_F16; 26 c32 after the
+ * output projection + residual; 27 c32 and 28 c16 after LayerNorm 1; 29 the FFN intermediate [B][3072], fp32 in MV_F16X8 (ch32), fp16 in MV_F16 (ch16); 30 c32 after
+ * FFN-2 + residual; 31 c32 after LayerNorm 2; 32 the pooler output fp32 [B][768]; 33 the embedding u fp32 [B][proj_dim]; 34 int32 [3]: the pruned passes tapped since
+ * mv_create, and B and Sp of the last pass (a batch that ran as one pass adds 1).  After such a call buffers 0, 1, 12, 13, 19 (the stream the tail gathers from) and
+ * 3, 4, 8, 9, 18 (K, V^T, their lo planes, vlo_sp) still hold the tail's inputs: the pruned layer overwrites none of them. */
 int mv_debug_encode(mv_handle* h, const int32_t* ids, const int32_t* lens, int B, int S, int n_layers);
 int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes);
 /* Stand-alone GEMM check/bench on caller data: C[M,N] = A[M,K] (fp16 bits) x W[N,K]^T (fp16 bits)

@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmemvul_hip.so")
 LIB_PATH_DEV = os.path.join(_HERE, "lib", "libmemvul_hip_dev.so")  # the -DMEMVUL_DEV_SWITCHES build (memvul_amd/build.py): tests and A/B scripts only
-DEV_SWITCHES = ("MEMVUL_GEMM_TILE", "MEMVUL_SHORT_VLO", "MEMVUL_RASTER", "MEMVUL_GN_MAX", "MEMVUL_NUM_CU", "MEMVUL_DEBUG_STOP")  # read by that build alone
+DEV_SWITCHES = ("MEMVUL_GEMM_TILE", "MEMVUL_SHORT_VLO", "MEMVUL_RASTER", "MEMVUL_GN_MAX", "MEMVUL_NUM_CU", "MEMVUL_DEBUG_STOP", "MEMVUL_DEBUG_TAIL")  # read by that build alone
 
 MV_F32, MV_F16, MV_BF16, MV_I32, MV_I64 = 0, 1, 2, 3, 4
 MV_F16X8 = 6  # compute dtype only ("precise"): fp16 MFMA sweep + one fp8 (e4m3) correction sweep per GEMM (include/memvul_hip.h)
@@ -236,7 +236,8 @@ def load_library(path: Optional[str] = None, dev: bool = False):
         raise RuntimeError(f"libmemvul_hip.so not found at {path}: build it with `python -m memvul_amd.build` "
                            "(hipcc --offload-arch=gfx950); the MemVul hot path has no CPU fallback")
     try:
-        # the product library as always (RTLD_GLOBAL); the development build, which a test process may load NEXT TO it, privately
+        # the product library as always (RTLD_GLOBAL); the development build, which a test process may load NEXT TO it, privately — RTLD_LOCAL keeps its
+        # symbols from others, and its -Bsymbolic link (build.DEV_FLAGS) keeps the product's from it
         lib = C.CDLL(path, mode=C.RTLD_LOCAL if path == LIB_PATH_DEV else C.RTLD_GLOBAL)
     except OSError as e:  # pragma: no cover
         raise RuntimeError(f"cannot load {path}: {e}") from e
@@ -934,6 +935,15 @@ class Engine:
         S = ids.shape[1]
         self._dbg = (ids.shape[0], (S + 63) // 64 * 64 if S <= 256 else (S + 127) // 128 * 128, lens.copy())  # engine.hip padded_len
 
+    def tail_encode(self, ids, lens) -> np.ndarray:
+        """encode(ids, lens) — the ordinary, pruned forward — on a development-build engine created with MEMVUL_DEBUG_TAIL=1: the embeddings, and debug_read then
+        hands back the tail taps 22 - 34 of that pass beside the taps of the tail's inputs (0, 1, 3, 4, 8, 9, 12, 13, 18, 19: the pruned layer overwrites none)."""
+        ids, lens = _as(ids, np.int32), _as(lens, np.int32)
+        u = self.encode(ids, lens)
+        S = ids.shape[1]
+        self._dbg = (ids.shape[0], (S + 63) // 64 * 64 if S <= 256 else (S + 127) // 128 * 128, lens.copy())  # engine.hip padded_len
+        return u
+
     def debug_read(self, buffer: int, pad_rows: bool = False) -> np.ndarray:
         """pad_rows (the per-token raw planes 11, 13 - 15, 17, 19 only): the rows PAST the pass' B * Sp tokens, up to the end of its last 256-row tile, as
         [rows, width] in the engine's order — rows no token lives in, which the persistent GEMMs compute like any other."""
@@ -956,6 +966,13 @@ class Engine:
             11: ((B, Sp, 2 * 768), np.uint8), 12: ((2 * B, 768), np.float16), 13: ((B, Sp, 3, 2), np.float32), 14: ((B, Sp, 3, 2), np.float32),
             15: ((B, Sp, 2 * 768), np.uint8), 16: ((2 * B * 3072,), np.float16), 17: ((B, Sp, 2 * 3072), np.uint8), 18: ((B, 12, 64, 2), np.float16),
             19: ((B, Sp, 768), np.float16), 20: ((2 * B * 3072,), np.float32), 21: (((B * Sp + 255) // 256,), np.int32),
+            # the tail taps (development build, MEMVUL_DEBUG_TAIL=1; tail_encode): what each launch of the pruned last layer's [CLS] tail wrote, B rows each —
+            # 22 / 23 the gathered c32 / c16, 24 the [CLS] query, 25 the context (fp32 in MV_F16X8, fp16 in MV_F16), 26 c32 after the output projection, 27 / 28
+            # c32 / c16 after LayerNorm 1, 29 the FFN intermediate (fp32 / fp16 likewise), 30 c32 after FFN-2, 31 c32 after LayerNorm 2, 32 the pooler output,
+            # 33 the embedding u; 34 int32 [3] = (pruned passes tapped since the engine was created, rows and padded length of the last pass)
+            22: ((B, 768), np.float32), 23: ((B, 768), np.float16), 24: ((B, 768), np.float32), 25: ((B, 768), np.float32 if self._precise else np.float16),
+            26: ((B, 768), np.float32), 27: ((B, 768), np.float32), 28: ((B, 768), np.float16), 29: ((B, 3072), np.float32 if self._precise else np.float16),
+            30: ((B, 768), np.float32), 31: ((B, 768), np.float32), 32: ((B, 768), np.float32), 33: ((B, self.P), np.float32), 34: ((3,), np.int32),
         }
         shape, dt = shapes[buffer]
         out = np.empty(shape, dt)

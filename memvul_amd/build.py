@@ -16,7 +16,11 @@ LIB_PATH = os.path.join(LIB_DIR, "libmemvul_hip.so")
 # the same sources with -DMEMVUL_DEV_SWITCHES: the development A/B knobs (MEMVUL_GEMM_TILE, MEMVUL_SHORT_VLO, MEMVUL_RASTER, MEMVUL_GN_MAX,
 # MEMVUL_NUM_CU; engine.hip read_switches) exist only in this build — GPU tests that force a kernel path at test sizes and the A/B scripts load it
 LIB_PATH_DEV = os.path.join(LIB_DIR, "libmemvul_hip_dev.so")
-DEV_FLAGS = ("-DMEMVUL_DEV_SWITCHES",)
+# -Bsymbolic: a test process loads this build NEXT TO the product library, which binding.load_library opens RTLD_GLOBAL.  Both define the same interposable
+# symbols (mv_destroy, mv_comm_destroy, mv_handle's implicit constructor and destructor, the kernels' host handles), and without it the dynamic linker binds this
+# build's own references to them to the product's definitions when that was loaded first — host code compiled for ANOTHER mv_handle layout (the development
+# members of the struct).  With it every reference of this build is bound to its own definition at link time; the product's link line is untouched
+DEV_FLAGS = ("-DMEMVUL_DEV_SWITCHES", "-Wl,-Bsymbolic")
 # the UTF-8 tokenise kernel and its launch function, a library and a code object of its own (csrc/wordpiece_u8.hip says why); the two libraries above link
 # against it and find it beside themselves ($ORIGIN), so it is built before them
 TOK_LIB_NAME = "libmemvul_tok_u8.so"

@@ -90,16 +90,46 @@ int launch_small(mv_handle* h, hipStream_t stream, int cls, const GemmArgs& a) {
   return launch_gemm128<EPI>(h, stream, cls, a);
 }
 
+// The tail taps of the development build (MEMVUL_DEBUG_TAIL=1, engine.hip read_switches): after a launch of the pruned last layer's [CLS] tail, its B output
+// rows copied into slot `stage` of the handle's tap arena — on the pass's stream, so the copy sees what that launch wrote and the next launch (which may
+// overwrite it in place: c32 four times, pooled as the fp32 context and then as the pooler output) waits for it.  Workspace set 0 only (what mv_debug_read
+// reads).  The product build compiles MV_TAIL_TAP to nothing.
+#if defined(MEMVUL_DEV_SWITCHES)
+enum TailTap { TT_GATHER32, TT_GATHER16, TT_Q, TT_CTX, TT_OUT, TT_LN1_32, TT_LN1_16, TT_FFN1, TT_FFN2, TT_LN2, TT_POOLED, TT_U, TT_COUNT };
+// bytes per row of a slot (the widest form of the stage: fp32; MV_F16 stores fp16 in TT_CTX / TT_FFN1) and the slots' offsets in row units
+constexpr int64_t TT_ROW[TT_COUNT] = {3072, 1536, 3072, 3072, 3072, 3072, 1536, 12288, 3072, 3072, 3072, 3072};
+constexpr int64_t tt_off(int s) { return s == 0 ? 0 : tt_off(s - 1) + TT_ROW[s - 1]; }
+int tail_tap(mv_handle* h, Work& wk, int stage, const void* src, size_t row_bytes, int B) {
+  if (!h->dbg_tail || &wk != &h->work[0]) return MV_OK;
+  if (!h->tail_arena)
+    if (int rc = dev_alloc(h, wk.stream, &h->tail_arena, tt_off(TT_COUNT) * h->cfg.max_batch)) return rc;
+  if (B > h->cfg.max_batch || (int64_t)row_bytes > TT_ROW[stage]) return fail(h, MV_ERR_STATE, "internal: tail tap larger than its slot");
+  if (stage == TT_GATHER32) ++h->tail_passes;  // (the first tap of a pruned pass: a batch cut into several passes shows here, and only the last one's rows stay)
+  HIPCHK(h, hipMemcpyAsync(h->tail_arena + tt_off(stage) * h->cfg.max_batch, src, row_bytes * (size_t)B, hipMemcpyDeviceToDevice, wk.stream));
+  return MV_OK;
+}
+#define MV_TAIL_TAP(stage, src, row_bytes, B) \
+  if (int rc_tap = tail_tap(h, wk, stage, src, row_bytes, B)) return rc_tap
+#else
+#define MV_TAIL_TAP(stage, src, row_bytes, B)
+#endif
+
 // K7 + K8: pooler on the [CLS] rows (row_stride floats apart), then the header
 int pool_head(mv_handle* h, Work& wk, const float* x, size_t row_stride, int B, float* u_out) {
   const unsigned gx = (unsigned)((B + 31) / 32);
   hipLaunchKernelGGL(dense768_kernel<0>, dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, x, row_stride, B, h->WpT, h->bp,
                      MV_HIDDEN, h->P == MV_HIDDEN ? u_out : wk.pooled);
   if (int rc = launch_check(h, "pooler")) return rc;
-  if (h->P == MV_HIDDEN) return MV_OK;  // use_header = False: the pooler output is the embedding
+  MV_TAIL_TAP(TT_POOLED, h->P == MV_HIDDEN ? u_out : wk.pooled, MV_HIDDEN * 4, B);
+  if (h->P == MV_HIDDEN) {  // use_header = False: the pooler output is the embedding
+    MV_TAIL_TAP(TT_U, u_out, MV_HIDDEN * 4, B);
+    return MV_OK;
+  }
   hipLaunchKernelGGL(dense768_kernel<1>, dim3(gx, MV_PROJ / 32), dim3(512), 0, wk.stream, wk.pooled, (size_t)MV_HIDDEN, B, h->WhT,
                      h->bh, MV_PROJ, u_out);
-  return launch_check(h, "header");
+  if (int rc = launch_check(h, "header")) return rc;
+  MV_TAIL_TAP(TT_U, u_out, MV_PROJ * 4, B);
+  return MV_OK;
 }
 
 // padded sequence length of a pass: attention_v2 runs 64-key blocks up to 256 and 128-key chunks above
@@ -402,6 +432,7 @@ int cls_tail_f32(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w, con
   hipLaunchKernelGGL((dense768_kernel<2, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.c32,
                      (size_t)MV_HIDDEN, B, (const float*)w.wqT32, (const float*)w.bqkv, MV_HIDDEN, wk.cq, (const float*)nullptr);
   if (int rc = launch_check(h, "cls q")) return rc;
+  MV_TAIL_TAP(TT_Q, wk.cq, MV_HIDDEN * 4, B);
   const half_t* vlo_sp = special_v_lo(wk, p);
   if (p.safe)
     hipLaunchKernelGGL(attention_cls_kernel<true>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt, d_lens, wk.cctx, p.Sp,
@@ -410,17 +441,24 @@ int cls_tail_f32(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w, con
     hipLaunchKernelGGL(attention_cls_kernel<false>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt, d_lens, wk.cctx, p.Sp,
                        B * MV_HEADS, wk.pooled, vlo_sp, (const half_t*)nullptr, (const half_t*)nullptr);
   if (int rc = launch_check(h, "attention_cls")) return rc;
+  MV_TAIL_TAP(TT_CTX, wk.pooled, MV_HIDDEN * 4, B);
   hipLaunchKernelGGL((dense768_kernel<4, MV_HIDDEN>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.pooled,
                      (size_t)MV_HIDDEN, B, (const float*)w.woT32, (const float*)w.bo, MV_HIDDEN, wk.c32, (const float*)wk.c32);
   if (int rc = launch_check(h, "cls out")) return rc;
+  MV_TAIL_TAP(TT_OUT, wk.c32, MV_HIDDEN * 4, B);
   if (int rc = run_ln(h, wk, wk.c32, wk.c16, B, w.ln1g, w.ln1b)) return rc;
+  MV_TAIL_TAP(TT_LN1_32, wk.c32, MV_HIDDEN * 4, B);
+  MV_TAIL_TAP(TT_LN1_16, wk.c16, MV_HIDDEN * 2, B);
   hipLaunchKernelGGL((dense768_kernel<3, MV_HIDDEN>), dim3(gx, MV_INTER / 32), dim3(512), 0, wk.stream, (const float*)wk.c32,
                      (size_t)MV_HIDDEN, B, (const float*)w.w1T32, (const float*)w.b1, MV_INTER, wk.ch32, (const float*)nullptr);
   if (int rc = launch_check(h, "cls ffn1")) return rc;
+  MV_TAIL_TAP(TT_FFN1, wk.ch32, MV_INTER * 4, B);
   hipLaunchKernelGGL((dense768_kernel<4, MV_INTER>), dim3(gx, MV_HIDDEN / 32), dim3(512), 0, wk.stream, (const float*)wk.ch32,
                      (size_t)MV_INTER, B, (const float*)w.w2T32, (const float*)w.b2, MV_HIDDEN, wk.c32, (const float*)wk.c32);
   if (int rc = launch_check(h, "cls ffn2")) return rc;
+  MV_TAIL_TAP(TT_FFN2, wk.c32, MV_HIDDEN * 4, B);
   if (int rc = run_ln(h, wk, wk.c32, wk.c16, B, w.ln2g, w.ln2b)) return rc;
+  MV_TAIL_TAP(TT_LN2, wk.c32, MV_HIDDEN * 4, B);
   return pool_head(h, wk, wk.c32, MV_HIDDEN, B, u_out);
 }
 
@@ -435,20 +473,28 @@ int cls_tail_f16(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w, con
   GemmArgs q = skinny(wk.c16, w.wqkv, w.bqkv, MV_HIDDEN, MV_HIDDEN);
   q.outf = wk.cq;
   if (int rc = launch_small<EPI_F32>(h, wk.stream, KC_CLS_TAIL, q)) return rc;
+  MV_TAIL_TAP(TT_Q, wk.cq, MV_HIDDEN * 4, B);
   hipLaunchKernelGGL(attention_cls_kernel<false>, dim3((B * MV_HEADS + 3) / 4), dim3(256), 0, wk.stream, wk.cq, wk.k, wk.vt,
                      d_lens, wk.cctx, p.Sp, B * MV_HEADS, (float*)nullptr, (const half_t*)nullptr, (const half_t*)nullptr, (const half_t*)nullptr);
   if (int rc = launch_check(h, "attention_cls")) return rc;
+  MV_TAIL_TAP(TT_CTX, wk.cctx, MV_HIDDEN * 2, B);
   GemmArgs o = skinny(wk.cctx, w.wo, w.bo, MV_HIDDEN, MV_HIDDEN);
   o.xres = wk.c32;
   if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_CLS_TAIL, o)) return rc;
+  MV_TAIL_TAP(TT_OUT, wk.c32, MV_HIDDEN * 4, B);
   if (int rc = run_ln(h, wk, wk.c32, wk.c16, B, w.ln1g, w.ln1b)) return rc;
+  MV_TAIL_TAP(TT_LN1_32, wk.c32, MV_HIDDEN * 4, B);
+  MV_TAIL_TAP(TT_LN1_16, wk.c16, MV_HIDDEN * 2, B);
   GemmArgs f1 = skinny(wk.c16, w.w1, w.b1, MV_INTER, MV_HIDDEN);
   f1.out16 = wk.ch16;
   if (int rc = launch_small<EPI_GELU>(h, wk.stream, KC_CLS_TAIL, f1)) return rc;
+  MV_TAIL_TAP(TT_FFN1, wk.ch16, MV_INTER * 2, B);
   GemmArgs f2 = skinny(wk.ch16, w.w2, w.b2, MV_HIDDEN, MV_INTER);
   f2.xres = wk.c32;
   if (int rc = launch_small<EPI_RES>(h, wk.stream, KC_CLS_TAIL, f2)) return rc;
+  MV_TAIL_TAP(TT_FFN2, wk.c32, MV_HIDDEN * 4, B);
   if (int rc = run_ln(h, wk, wk.c32, wk.c16, B, w.ln2g, w.ln2b)) return rc;
+  MV_TAIL_TAP(TT_LN2, wk.c32, MV_HIDDEN * 4, B);
   return pool_head(h, wk, wk.c32, MV_HIDDEN, B, u_out);
 }
 
@@ -463,6 +509,8 @@ int pruned_last_layer(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w
                      (p.big && !p.x8) ? wk.xlo : (const half_t*)nullptr, p.big ? 1 : 0, h->cfg.ln_eps,
                      p.special ? (const half_t*)wk.st_lo : (const half_t*)nullptr);
   if (int rc = launch_check(h, "cls_gather")) return rc;
+  MV_TAIL_TAP(TT_GATHER32, wk.c32, MV_HIDDEN * 4, p.B);
+  MV_TAIL_TAP(TT_GATHER16, wk.c16, MV_HIDDEN * 2, p.B);
   return p.x8 ? cls_tail_f32(h, wk, p, w, d_lens, u_out) : cls_tail_f16(h, wk, p, w, d_lens, u_out);
 }
 

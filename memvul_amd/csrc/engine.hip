@@ -333,6 +333,13 @@ struct mv_handle {
   // debug
   int dbg_B = 0, dbg_Sp = 0;
   int dbg_stop = 0;  // development build only (read_switches): mv_debug_encode ends inside its last layer, after this many launch groups (encode_dev); 0 = off
+#if defined(MEMVUL_DEV_SWITCHES)
+  // development build only, MEMVUL_DEBUG_TAIL=1 (read_switches; encoder_pass.h tail_tap): every launch of the pruned last layer's [CLS] tail on workspace set 0
+  // is followed by a device-to-device copy of its B output rows into this arena, for mv_debug_read 22 - 33 (the tail overwrites c32 and pooled in place)
+  bool dbg_tail = false;
+  uint8_t* tail_arena = nullptr;  // [TT_COUNT slots], slot s at TT_OFF[s] x max_batch bytes (allocated at the first tapped pass)
+  int tail_passes = 0;            // pruned passes tapped so far: a batch that ran as ONE pass adds 1 (mv_debug_read 34)
+#endif
 
   Comm comm;  // the multi-GPU exchange (comm.h)
 };
@@ -422,6 +429,10 @@ int read_switches(mv_handle* h) {
     //                     its row term, 2 + attention, 3 + the output projection, 4 + FFN-1, 5 + FFN-2) and NO final LayerNorm (nor with n = 0): every workspace buffer
     //                     keeps what the last launch left in it, for mv_debug_read (persistent path, MV_F16 / MV_F16X8)
     if (!env_int("MEMVUL_DEBUG_STOP", 1, 5, &h->dbg_stop)) return MV_ERR_INVALID;
+    //   MEMVUL_DEBUG_TAIL 1: a pruned pass on workspace set 0 (mv_encode, mv_forward, ...) copies what each launch of its [CLS] tail wrote — the B real rows — into a
+    //                     tap arena, device to device on the pass's own stream, for mv_debug_read 22 - 34 (encoder_pass.h tail_tap).  Copies only: no launch, argument or
+    //                     order changes, so the embedding is the product library's bit for bit
+    if (!env_flag("MEMVUL_DEBUG_TAIL", &h->dbg_tail)) return MV_ERR_INVALID;
   }
 #endif
   return MV_OK;
@@ -989,6 +1000,26 @@ int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes) try {
     case 19: src = wk.xlo; avail = Tp * MV_HIDDEN * 2; break;
     case 20: src = wk.cls_corr; avail = (int64_t)2 * h->dbg_B * MV_INTER * 4; break;
     case 21: src = wk.tile_both; avail = (int64_t)((T + 255) / 256) * 4; break;
+#if defined(MEMVUL_DEV_SWITCHES)
+    // the tail taps (include/memvul_hip.h 22 - 34; encoder_pass.h tail_tap): B rows each, of the last pruned pass on workspace set 0
+    case 22: case 23: case 24: case 25: case 26: case 27: case 28: case 29: case 30: case 31: case 32: case 33: {
+      const int s = buffer - 22;
+      if (!h->dbg_tail) return fail(h, MV_ERR_STATE, "mv_debug_read: the tail taps 22 - 34 exist with MEMVUL_DEBUG_TAIL=1 only");
+      if (h->f32 || !h->tail_arena) return fail(h, MV_ERR_STATE, "mv_debug_read: no pruned pass has filled the tail taps");
+      int64_t row = TT_ROW[s];
+      if (!h->precise && (s == TT_CTX || s == TT_FFN1)) row /= 2;  // MV_F16: cctx / ch16 are fp16
+      if (s == TT_U) row = (int64_t)h->P * 4;
+      src = h->tail_arena + tt_off(s) * h->cfg.max_batch; avail = (int64_t)h->dbg_B * row;
+      break;
+    }
+    case 34: {  // int32 [3]: pruned passes tapped since mv_create, and the rows and the padded length of the last pass (host state: no copy from the device)
+      if (bytes > 12) return fail(h, MV_ERR_INVALID, "mv_debug_read: more bytes requested than the buffer holds");
+      const int32_t info[3] = {h->tail_passes, h->dbg_B, h->dbg_Sp};
+      HIPCHK(h, hipStreamSynchronize(wk.stream));
+      std::memcpy(dst, info, (size_t)bytes);
+      return MV_OK;
+    }
+#endif
     default: return fail(h, MV_ERR_INVALID, "mv_debug_read: unknown buffer");
   }
   if (!src) return fail(h, MV_ERR_STATE, "mv_debug_read: this buffer does not exist in this compute dtype");

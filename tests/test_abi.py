@@ -94,6 +94,39 @@ def test_kernel_fingerprints_do_not_depend_on_the_build_or_the_layout(lib):
     assert sum(k.endswith(".kd") for k in fp) == len(kernels)
 
 
+def _dynamic_entries(path):
+    """The (tag, value) pairs of the .dynamic section of an ELF64 little-endian shared library."""
+    import struct
+
+    data = open(path, "rb").read()
+    assert data[:6] == b"\x7fELF\x02\x01"
+    (shoff,) = struct.unpack_from("<Q", data, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", data, 0x3A)
+    for i in range(shnum):
+        typ, off, size = struct.unpack_from("<4xI16xQQ", data, shoff + i * shentsize)
+        if typ == 6:  # SHT_DYNAMIC
+            return [struct.unpack_from("<qQ", data, off + 16 * j) for j in range(size // 16)]
+    raise AssertionError(f"{path}: no .dynamic section")
+
+
+def test_development_build_binds_its_own_symbols(lib):
+    """A test process loads the development build next to the product library (opened RTLD_GLOBAL), and the two define the same interposable symbols —
+    mv_destroy, mv_comm_destroy, mv_handle's implicit constructor and destructor, the kernels' host handles — while their mv_handle layouts differ (the
+    development members).  Unless the development build is linked -Bsymbolic, the dynamic linker binds its references to those symbols to the PRODUCT's
+    definitions whenever that library was loaded first: `delete h` in its mv_destroy then runs a destructor compiled for another layout.  The product library
+    is linked as ever."""
+    from memvul_amd import build
+
+    build.build(verbose=False, dev=True)
+    DT_SYMBOLIC, DT_FLAGS, DF_SYMBOLIC = 16, 30, 2
+
+    def symbolic(path):
+        return any(tag == DT_SYMBOLIC or (tag == DT_FLAGS and val & DF_SYMBOLIC) for tag, val in _dynamic_entries(path))
+
+    assert symbolic(build.LIB_PATH_DEV)
+    assert not symbolic(build.LIB_PATH)
+
+
 def test_stamp_carries_the_device_code_fingerprint(lib):
     """bench.py keys the counter figures of profiles/pmc_current.json on the stamp's `dev` line = sha256 of the gfx950 code
     object inside the .so: it must describe the binary next to it, and the committed counter file must be readable.  (A host-only edit of engine.hip leaves
