@@ -1,7 +1,8 @@
-"""Build libmemvul_hip.so (product and development build), libmemvul_tok_u8.so, libmemvul_retrieve.so, libmemvul_claims.so and libmemvul_bank.so (gfx950) in-tree with
-hipcc.  No torch involved."""
+"""Build libmemvul_hip.so (product and development build) and the side libraries of SIDE_LIBS — libmemvul_tok_u8.so, libmemvul_retrieve.so, libmemvul_claims.so and
+libmemvul_bank.so — for gfx950, in-tree with hipcc.  The last three share csrc/kept_index.h and csrc/kept_terms.h, which no other library includes.  No torch involved."""
 from __future__ import annotations
 
+from functools import partial
 import os
 import shutil
 import subprocess
@@ -21,28 +22,27 @@ LIB_PATH_DEV = os.path.join(LIB_DIR, "libmemvul_hip_dev.so")
 # build's own references to them to the product's definitions when that was loaded first — host code compiled for ANOTHER mv_handle layout (the development
 # members of the struct).  With it every reference of this build is bound to its own definition at link time; the product's link line is untouched
 DEV_FLAGS = ("-DMEMVUL_DEV_SWITCHES", "-Wl,-Bsymbolic")
-# the UTF-8 tokenise kernel and its launch function, a library and a code object of its own (csrc/wordpiece_u8.hip says why); the two libraries above link
-# against it and find it beside themselves ($ORIGIN), so it is built before them
-TOK_LIB_NAME = "libmemvul_tok_u8.so"
-LIB_PATH_TOK = os.path.join(LIB_DIR, TOK_LIB_NAME)
-TOK_SOURCES = ["wordpiece_u8.hip"]
-TOK_HEADERS = ["wordpiece.h"]
-# per-anchor retrieval over a kept corpus (csrc/retrieve.hip, csrc/report_topk.h, include/memvul_retrieve.h): a stand-alone library — nothing links against it and it
-# links against nothing of this tree, so neither the source fingerprint nor the kernel map of the libraries above moves with it
-RETRIEVE_LIB_NAME = "libmemvul_retrieve.so"
-LIB_PATH_RETRIEVE = os.path.join(LIB_DIR, RETRIEVE_LIB_NAME)
-RETRIEVE_SOURCES = ["retrieve.hip"]
-RETRIEVE_HEADERS = ["report_topk.h", os.path.join(ROOT, "include", "memvul_retrieve.h")]
-# per-anchor claims over a kept corpus (csrc/claims.hip, csrc/claim_sweep.h, include/memvul_claims.h): stand-alone in the same way, with sources and a stamp of its own
-CLAIMS_LIB_NAME = "libmemvul_claims.so"
-LIB_PATH_CLAIMS = os.path.join(LIB_DIR, CLAIMS_LIB_NAME)
-CLAIMS_SOURCES = ["claims.hip"]
-CLAIMS_HEADERS = ["claim_sweep.h", os.path.join(ROOT, "include", "memvul_claims.h")]
-# the anchor-bank audit over a kept corpus (csrc/bank.hip, csrc/bank_cover.h, include/memvul_bank.h): stand-alone in the same way, with sources and a stamp of its own
-BANK_LIB_NAME = "libmemvul_bank.so"
-LIB_PATH_BANK = os.path.join(LIB_DIR, BANK_LIB_NAME)
-BANK_SOURCES = ["bank.hip"]
-BANK_HEADERS = ["bank_cover.h", os.path.join(ROOT, "include", "memvul_bank.h")]
+# the side libraries, each with sources, headers and a stamp of its own: key -> (library name, sources, headers).
+#   tok       the UTF-8 tokenise kernel and its launch function, a library and a code object of its own (csrc/wordpiece_u8.hip says why); the two libraries above link
+#             against it and find it beside themselves ($ORIGIN), so it is built before them
+#   retrieve  per-anchor retrieval over a kept corpus (csrc/retrieve.hip, csrc/report_topk.h, include/memvul_retrieve.h)
+#   claims    per-anchor claims over a kept corpus (csrc/claims.hip, csrc/claim_sweep.h, include/memvul_claims.h)
+#   bank      the anchor-bank audit over a kept corpus (csrc/bank.hip, csrc/bank_cover.h, include/memvul_bank.h)
+# The three kept-corpus libraries stand alone — nothing links against them and they link against nothing of this tree, so neither the source fingerprint nor the
+# kernel map of the libraries above moves with them — and share two headers, which only they include: csrc/kept_index.h (the host side of an index over a kept corpus)
+# and csrc/kept_terms.h (the device functions of the row and vector terms)
+KEPT_HEADERS = ["kept_index.h", "kept_terms.h"]
+SIDE_LIBS = {
+    "tok": ("libmemvul_tok_u8.so", ["wordpiece_u8.hip"], ["wordpiece.h"]),
+    "retrieve": ("libmemvul_retrieve.so", ["retrieve.hip"], ["report_topk.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_retrieve.h")]),
+    "claims": ("libmemvul_claims.so", ["claims.hip"], ["claim_sweep.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_claims.h")]),
+    "bank": ("libmemvul_bank.so", ["bank.hip"], ["bank_cover.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_bank.h")]),
+}
+TOK_LIB_NAME, TOK_SOURCES, TOK_HEADERS = SIDE_LIBS["tok"]
+RETRIEVE_LIB_NAME, RETRIEVE_SOURCES, RETRIEVE_HEADERS = SIDE_LIBS["retrieve"]
+CLAIMS_LIB_NAME, CLAIMS_SOURCES, CLAIMS_HEADERS = SIDE_LIBS["claims"]
+BANK_LIB_NAME, BANK_SOURCES, BANK_HEADERS = SIDE_LIBS["bank"]
+LIB_PATH_TOK, LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS, LIB_PATH_BANK = (os.path.join(LIB_DIR, SIDE_LIBS[k][0]) for k in ("tok", "retrieve", "claims", "bank"))
 SOURCES = ["engine.hip"]
 KERNEL_HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", "wordpiece.h"]
 # the host code of the library: engine.hip includes each of these parts once, in this order
@@ -232,83 +232,51 @@ def is_stale(extra_flags=(), dev: bool = False) -> bool:
     return want["cc"] != "unknown" and have.get("cc") != want["cc"]
 
 
-def _side_is_stale(lib_path: str, sources, headers) -> bool:
-    """is_stale for a library with sources and a stamp of its own."""
-    stamp_path = lib_path + ".stamp"
-    if not os.path.exists(lib_path) or not os.path.exists(stamp_path):
-        return True
-    with open(stamp_path) as f:
-        have = dict(line.split(" ", 1) for line in f.read().strip().splitlines() if " " in line)
+def side_lib_path(key: str) -> str:
+    return os.path.join(LIB_DIR, SIDE_LIBS[key][0])
+
+
+def _side_stamp(key: str) -> str:
+    import hashlib
+
+    _, sources, headers = SIDE_LIBS[key]
     cc = _compiler_id()
-    import hashlib
+    return "src %s\ncc %s\n" % (source_fingerprint((), sources, headers), hashlib.sha256(cc).hexdigest() if cc is not None else "unknown")
 
-    if have.get("src") != source_fingerprint((), sources, headers):
+
+def side_is_stale(key: str) -> bool:
+    """is_stale for a side library (SIDE_LIBS[key]): its own stamp, over its own sources and headers."""
+    lib_path = side_lib_path(key)
+    if not os.path.exists(lib_path) or not os.path.exists(lib_path + ".stamp"):
         return True
-    return cc is not None and have.get("cc") != hashlib.sha256(cc).hexdigest()
+    with open(lib_path + ".stamp") as f:
+        have = dict(line.split(" ", 1) for line in f.read().strip().splitlines() if " " in line)
+    want = dict(line.split(" ", 1) for line in _side_stamp(key).splitlines())
+    if have.get("src") != want["src"]:
+        return True
+    return want["cc"] != "unknown" and have.get("cc") != want["cc"]
 
 
-def tok_is_stale() -> bool:
-    """is_stale for libmemvul_tok_u8.so (its own stamp: its sources are wordpiece_u8.hip and wordpiece.h)."""
-    return _side_is_stale(LIB_PATH_TOK, TOK_SOURCES, TOK_HEADERS)
-
-
-def retrieve_is_stale() -> bool:
-    """is_stale for libmemvul_retrieve.so (its own stamp: retrieve.hip, report_topk.h, include/memvul_retrieve.h)."""
-    return _side_is_stale(LIB_PATH_RETRIEVE, RETRIEVE_SOURCES, RETRIEVE_HEADERS)
-
-
-def claims_is_stale() -> bool:
-    """is_stale for libmemvul_claims.so (its own stamp: claims.hip, claim_sweep.h, include/memvul_claims.h)."""
-    return _side_is_stale(LIB_PATH_CLAIMS, CLAIMS_SOURCES, CLAIMS_HEADERS)
-
-
-def bank_is_stale() -> bool:
-    """is_stale for libmemvul_bank.so (its own stamp: bank.hip, bank_cover.h, include/memvul_bank.h)."""
-    return _side_is_stale(LIB_PATH_BANK, BANK_SOURCES, BANK_HEADERS)
-
-
-def _build_side(lib_path: str, lib_name: str, sources, headers, verbose: bool) -> str:
-    import hashlib
-
+def build_side(key: str, force: bool = False, verbose: bool = True) -> str:
+    """Compile a side library (SIDE_LIBS[key]) for gfx950; returns its path."""
+    lib_name, sources, _ = SIDE_LIBS[key]
+    lib_path = side_lib_path(key)
+    if not force and not side_is_stale(key):
+        return lib_path
     os.makedirs(LIB_DIR, exist_ok=True)
     cmd = [hipcc_path(), f"--offload-arch={ARCH}", *FLAGS, f"-Wl,-soname,{lib_name}", *[os.path.join(CSRC, s) for s in sources], "-o", lib_path + ".tmp"]
     if verbose:
         print("[memvul_amd.build]", " ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)
-    cc = _compiler_id()
     with open(lib_path + ".stamp.tmp", "w") as f:
-        f.write("src %s\ncc %s\n" % (source_fingerprint((), sources, headers), hashlib.sha256(cc).hexdigest() if cc is not None else "unknown"))
+        f.write(_side_stamp(key))
     os.replace(lib_path + ".tmp", lib_path)
     os.replace(lib_path + ".stamp.tmp", lib_path + ".stamp")
     return lib_path
 
 
-def build_tok(force: bool = False, verbose: bool = True) -> str:
-    """Compile libmemvul_tok_u8.so for gfx950; returns its path."""
-    if not force and not tok_is_stale():
-        return LIB_PATH_TOK
-    return _build_side(LIB_PATH_TOK, TOK_LIB_NAME, TOK_SOURCES, TOK_HEADERS, verbose)
-
-
-def build_retrieve(force: bool = False, verbose: bool = True) -> str:
-    """Compile libmemvul_retrieve.so for gfx950; returns its path."""
-    if not force and not retrieve_is_stale():
-        return LIB_PATH_RETRIEVE
-    return _build_side(LIB_PATH_RETRIEVE, RETRIEVE_LIB_NAME, RETRIEVE_SOURCES, RETRIEVE_HEADERS, verbose)
-
-
-def build_claims(force: bool = False, verbose: bool = True) -> str:
-    """Compile libmemvul_claims.so for gfx950; returns its path."""
-    if not force and not claims_is_stale():
-        return LIB_PATH_CLAIMS
-    return _build_side(LIB_PATH_CLAIMS, CLAIMS_LIB_NAME, CLAIMS_SOURCES, CLAIMS_HEADERS, verbose)
-
-
-def build_bank(force: bool = False, verbose: bool = True) -> str:
-    """Compile libmemvul_bank.so for gfx950; returns its path."""
-    if not force and not bank_is_stale():
-        return LIB_PATH_BANK
-    return _build_side(LIB_PATH_BANK, BANK_LIB_NAME, BANK_SOURCES, BANK_HEADERS, verbose)
+tok_is_stale, retrieve_is_stale, claims_is_stale, bank_is_stale = (partial(side_is_stale, k) for k in ("tok", "retrieve", "claims", "bank"))
+build_tok, build_retrieve, build_claims, build_bank = (partial(build_side, k) for k in ("tok", "retrieve", "claims", "bank"))
 
 
 def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool = False) -> str:
@@ -355,7 +323,7 @@ def build_all(force: bool = False, verbose: bool = True):
 
     build_tok(force, verbose)
     with ThreadPoolExecutor(5) as ex:
-        sides = [ex.submit(build_retrieve, force, verbose), ex.submit(build_claims, force, verbose), ex.submit(build_bank, force, verbose)]
+        sides = [ex.submit(build_side, key, force, verbose) for key in ("retrieve", "claims", "bank")]
         futs = [ex.submit(build, force, verbose, (), d) for d in (False, True)]
         for side in sides:
             side.result()

@@ -23,7 +23,7 @@ from typing import Optional
 
 import numpy as np
 
-from .retrieve import _check_array, _int, _ptr  # (the same rule for arrays: checked, never converted)
+from .kept_index import ClassedKeptIndex, _check_array, _int, _ptr, load_side_library  # noqa: F401  (the kept-corpus index the three libraries share)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmemvul_claims.so")
@@ -49,26 +49,10 @@ _SIGNATURES = {
 }
 CLAIMS_SYMBOLS = list(_SIGNATURES)
 
-_libs = {}
-
 
 def load_library(path: Optional[str] = None):
     """dlopen libmemvul_claims.so and declare the prototypes.  Raises RuntimeError if it is missing: there is no other implementation to fall back to."""
-    path = path or LIB_PATH
-    if path in _libs:
-        return _libs[path]
-    if not os.path.exists(path):
-        raise RuntimeError(f"libmemvul_claims.so not found at {path}: build it with `python -m memvul_amd.build` (hipcc --offload-arch=gfx950); "
-                           "per-anchor claims have no CPU fallback")
-    try:
-        lib = C.CDLL(path, mode=C.RTLD_LOCAL)
-    except OSError as e:  # pragma: no cover
-        raise RuntimeError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
-        fn.restype, fn.argtypes = res, args
-    _libs[path] = lib
-    return lib
+    return load_side_library(path or LIB_PATH, "libmemvul_claims.so", _SIGNATURES, "per-anchor claims have no CPU fallback")
 
 
 # ---- thresholds ---------------------------------------------------------------------------------------------------------------------------------------------------
@@ -122,106 +106,11 @@ def order_by_prob(offsets: np.ndarray, rows: np.ndarray, p: np.ndarray):
     return rows[order], p[order]
 
 
-class ClaimIndex:
+class ClaimIndex(ClassedKeptIndex):
     """One index <-> one GPU <-> one stream; one thread uses it at a time.  ``matcher_weight``: ``_projector.weight`` of the state dict, fp32 [2, 3 * proj_dim]."""
 
-    def __init__(self, device: int, proj_dim: int, matcher_weight, same_idx: int, lib=None):
-        self._h = None
-        device, proj_dim, same_idx = _int(device, "device"), _int(proj_dim, "proj_dim"), _int(same_idx, "same_idx")
-        if proj_dim not in (512, 768):
-            raise ValueError(f"proj_dim = {proj_dim}: the matcher runs on 512 or 768 features")
-        if same_idx not in (0, 1):
-            raise ValueError(f"same_idx = {same_idx}: 0 or 1")
-        if device < 0:
-            raise ValueError(f"device = {device}")
-        w = np.asarray(matcher_weight)
-        if w.dtype != np.float32 or w.shape != (2, 3 * proj_dim):
-            raise ValueError(f"matcher_weight: float32 [2, {3 * proj_dim}], not {w.dtype} {list(w.shape)}")
-        w = np.ascontiguousarray(w)
-        self._lib = lib if lib is not None else load_library()
-        self.P, self.same_idx, self.device = proj_dim, same_idx, device
-        h = C.c_void_p()
-        rc = self._lib.mvc_create(device, proj_dim, _ptr(w), same_idx, C.byref(h))
-        if rc != 0:
-            msg = self._lib.mvc_last_error(None)
-            raise RuntimeError(f"mvc_create failed ({rc}): {msg.decode() if msg else ''}")
-        self._h = h
-
-    # -- plumbing
-    def _check(self, rc: int, what: str):
-        if rc != 0:
-            msg = self._lib.mvc_last_error(self._h)
-            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
-
-    def _handle(self):
-        if self._h is None:
-            raise RuntimeError("the ClaimIndex is closed")
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mvc_destroy(self._h)
-        self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    # -- the rows
-    def add(self, embed: np.ndarray):
-        """Append rows: float32 [n, proj_dim], C-contiguous.  Rows are numbered in order of arrival; their class is 0 until set_classes says otherwise."""
-        h = self._handle()
-        embed = _check_array(embed, "embed", self.P)
-        if len(self) + embed.shape[0] > MAX_ROWS:
-            raise ValueError("the index would hold more than 2^31 - 2 rows")
-        self._check(self._lib.mvc_add(h, _ptr(embed), embed.shape[0]), "mvc_add")
-
-    def reset(self):
-        """Forget the rows and their classes, keep the weights."""
-        self._check(self._lib.mvc_reset(self._handle()), "mvc_reset")
-
-    def __len__(self) -> int:
-        return int(self._lib.mvc_count(self._handle()))
-
-    def set_classes(self, cls, first: int = 0):
-        """The class (0 or 1; bool or uint8, one per row) of rows [first, first + len(cls))."""
-        h = self._handle()
-        if not isinstance(cls, np.ndarray):
-            raise TypeError(f"cls: a numpy array, not {type(cls).__name__}")
-        if cls.dtype not in (np.dtype(np.uint8), np.dtype(bool)):
-            raise TypeError(f"cls: uint8 or bool, not {cls.dtype}")
-        if cls.ndim != 1 or not cls.flags["C_CONTIGUOUS"]:
-            raise ValueError(f"cls: one C-contiguous dimension, not shape {list(cls.shape)}")
-        first = _int(first, "first")
-        if first < 0 or first + cls.shape[0] > len(self):
-            raise ValueError(f"rows [{first}, {first} + {cls.shape[0]}) are not within the {len(self)} rows of the index")
-        cls = cls.view(np.uint8)
-        if cls.size and int(cls.max()) > 1:
-            raise ValueError("cls: a class is 0 or 1")
-        self._check(self._lib.mvc_set_classes(h, _ptr(cls), first, cls.shape[0]), "mvc_set_classes")
-
-    def _range(self, first, count):
-        n = len(self)
-        first = _int(first, "first")
-        count = n - first if count is None else _int(count, "count")
-        if first < 0 or count < 0 or first + count > n:
-            raise ValueError(f"rows [{first}, {first} + {count}) are not within the {n} rows of the index")
-        return first, count
-
-    def _vectors(self, vectors) -> np.ndarray:
-        vectors = _check_array(vectors, "vectors", self.P)
-        if not 1 <= vectors.shape[0] <= MAX_VECTORS:
-            raise ValueError(f"{vectors.shape[0]} vectors: 1 <= Q <= {MAX_VECTORS}")
-        return vectors
+    PREFIX, MAX_VECTORS, MAX_ROWS = "mvc_", MAX_VECTORS, MAX_ROWS
+    _load = staticmethod(lambda: load_library())
 
     # -- the questions
     def counts(self, vectors: np.ndarray, thresholds, first: int = 0, count: Optional[int] = None) -> np.ndarray:
@@ -269,34 +158,9 @@ class ClaimIndex:
         self._check(self._lib.mvc_fetch(self._handle(), _ptr(rows), _ptr(p)), "mvc_fetch")
         return rows, p
 
-    def kernel_ms(self) -> float:
-        """HIP-event time of the last call's launches, in milliseconds."""
-        ms = C.c_float()
-        self._check(self._lib.mvc_kernel_ms(self._handle(), C.byref(ms)), "mvc_kernel_ms")
-        return float(ms.value)
-
     def test_plan(self, block_rows: int = 0, vector_group: int = 0):
         """Tests only: rows per block, vectors per group (0 = the library's own choice).  No result depends on them."""
         self._check(self._lib.mvc_test_plan(self._handle(), int(block_rows), int(vector_group)), "mvc_test_plan")
-
-    @classmethod
-    def from_sweep(cls, engine, matcher_weight, same_idx: int, chunk: int = 65536, index_factory=None, classes=None):
-        """An index over the kept embeddings of the engine's last ``bucketed_sweep(..., keep=True)``, in the ORIGINAL row order, downloaded ``chunk`` rows at a time
-        (one download and one upload per kept sweep; a further device copy of the embeddings, 2 KB per row at 512 features).  classes: one class per row."""
-        chunk = _int(chunk, "chunk")
-        if chunk < 1:
-            raise ValueError(f"chunk = {chunk}")
-        embed = engine.sweep_embeddings(0, None, chunk)  # (raises unless the last sweep kept its embeddings; host memory: the whole corpus once, n * P * 4 bytes)
-        index = (index_factory or cls)(engine.device, engine.P, matcher_weight, same_idx)
-        try:
-            for s0 in range(0, embed.shape[0], chunk):
-                index.add(np.ascontiguousarray(embed[s0:s0 + chunk], dtype=np.float32))
-            if classes is not None:
-                index.set_classes(np.ascontiguousarray(classes, dtype=np.uint8))
-        except Exception:
-            index.close()
-            raise
-        return index
 
 
 # ---- the per-anchor threshold rule and the output entries -----------------------------------------------------------------------------------------------------------

@@ -2,29 +2,25 @@
 // library of this tree links against: their kernel sets, their source fingerprints and their lists of entries all stay as they are.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
 #include <cstring>
-#include <new>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
 #include "../../include/memvul_bank.h"
 #include "bank_cover.h"
+#include "kept_index.h"
 
-struct mvb_index {
-  int device = 0, P = 0, same_idx = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};  // bracket the launches of a call
-  bool timed = false;
-  float *U = nullptr, *sa = nullptr;  // rows [cap][P], row terms [cap]
-  uint8_t* cls = nullptr;             // [cap]
-  int64_t n = 0, cap = 0;
-  float* wd = nullptr;                // [3][P] class-difference weights
+KEPT_ASSERT_ABI(MVB, MVB_MAX_VECTORS);
+static_assert(MVB_ERR_STATE == KEPT_ERR_STATE, "the public header and kept_index.h disagree");
+
+namespace {
+const KeptKernels kBankKernels = {bank_weight_delta_kernel, {bank_row_term_kernel<512>, bank_row_term_kernel<768>}, {bank_vector_prep_kernel<512>, bank_vector_prep_kernel<768>}};
+}
+
+struct mvb_index : KeptIndex {
+  mvb_index() : KeptIndex(&kBankKernels, true, 2) {}
   // workspace (grows, never shrinks)
-  float *vdev = nullptr, *vT = nullptr, *bv = nullptr, *thr = nullptr;  // the vectors [Q][P]; one group transposed [P][Qs]; its bv [Qs]; the thresholds [Q]
-  size_t vdev_n = 0, vT_n = 0, bv_n = 0, thr_n = 0;
+  float* thr = nullptr;               // the thresholds [Q]
+  size_t thr_n = 0;
   unsigned long long* out = nullptr;  // the integers of a reading call
   size_t out_n = 0;
   uint16_t* mult = nullptr;           // [count]
@@ -45,101 +41,16 @@ struct mvb_index {
   unsigned long long *bits = nullptr, *pos = nullptr, *covered = nullptr;  // B [Q][W]; class words [W]; covered rows [W]
   size_t bits_n = 0, pos_n = 0, covered_n = 0;
   int plan_block_rows = 0, plan_vector_group = 0, plan_word_chunk = 0;  // mvb_test_plan; 0 = the library's own choice
-  std::string err;
 };
 
 namespace {
 
-thread_local std::string g_err;  // errors with no index to hang them on (mvb_create)
-
-struct Refusal : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-struct StateError : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-int fail(mvb_index* h, int code, const std::string& msg) {
-  (h ? h->err : g_err) = msg;
-  return code;
-}
-
-int on_exception(mvb_index* h) noexcept {
-  try {
-    try {
-      throw;
-    } catch (const Refusal& e) {
-      return fail(h, MVB_ERR_ARG, e.what());
-    } catch (const StateError& e) {
-      return fail(h, MVB_ERR_STATE, e.what());
-    } catch (const std::bad_alloc&) {
-      return fail(h, MVB_ERR_NOMEM, "out of host memory");
-    } catch (const std::exception& e) {
-      return fail(h, MVB_ERR_HIP, e.what());
-    } catch (...) {
-      return fail(h, MVB_ERR_INTERNAL, "unknown C++ exception");
-    }
-  } catch (...) {  // (the message itself could not be stored)
-    return MVB_ERR_INTERNAL;
-  }
-}
-
-void hipchk(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(X) hipchk((X), #X)
-
-void launched(const char* what) { hipchk(hipGetLastError(), what); }
-
-void need(bool ok, const std::string& msg) {
-  if (!ok) throw Refusal(msg);
-}
-
-template <typename T>
-void grow(T*& p, size_t& have, size_t want) {  // (contents are not kept)
-  if (want <= have) return;
-  if (p) HIPCHK(hipFree(p));
-  p = nullptr;
-  have = 0;
-  HIPCHK(hipMalloc((void**)&p, want * sizeof(T)));
-  have = want;
-}
-
-void reserve_rows(mvb_index* h, int64_t want) {
-  if (want <= h->cap) return;
-  const int64_t cap = std::max<int64_t>(want, std::min<int64_t>(h->cap + h->cap / 2, MVB_MAX_ROWS));
-  float *U = nullptr, *sa = nullptr;
-  uint8_t* cls = nullptr;
-  hipError_t e = hipMalloc((void**)&U, (size_t)cap * h->P * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&sa, (size_t)cap * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&cls, (size_t)cap);
-  if (e == hipSuccess && h->n) {
-    e = hipMemcpyAsync(U, h->U, (size_t)h->n * h->P * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sa, h->sa, (size_t)h->n * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cls, h->cls, (size_t)h->n, hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  }
-  if (e != hipSuccess) {
-    for (void* p : {(void*)U, (void*)sa, (void*)cls})
-      if (p) (void)hipFree(p);
-    hipchk(e, "growing the rows' buffers");
-  }
-  for (void* p : {(void*)h->U, (void*)h->sa, (void*)h->cls})
-    if (p) (void)hipFree(p);
-  h->U = U;
-  h->sa = sa;
-  h->cls = cls;
-  h->cap = cap;
-}
-
 template <int P>
 void launch_mark(mvb_index* h, int block_rows, dim3 grid, const BankMarkArgs& a) {
-  switch (block_rows) {
-    case 64: hipLaunchKernelGGL((bank_mark_kernel<P, 64>), grid, dim3(64), 0, h->stream, h->U, h->sa, h->vT, h->bv, h->wd, a); break;
-    case 128: hipLaunchKernelGGL((bank_mark_kernel<P, 128>), grid, dim3(128), 0, h->stream, h->U, h->sa, h->vT, h->bv, h->wd, a); break;
-    case 256: hipLaunchKernelGGL((bank_mark_kernel<P, 256>), grid, dim3(256), 0, h->stream, h->U, h->sa, h->vT, h->bv, h->wd, a); break;
-    default: hipLaunchKernelGGL((bank_mark_kernel<P, 512>), grid, dim3(512), 0, h->stream, h->U, h->sa, h->vT, h->bv, h->wd, a); break;
-  }
+  by_block_rows(block_rows, [&](auto br) {
+    constexpr int BR = decltype(br)::value;
+    hipLaunchKernelGGL((bank_mark_kernel<P, BR>), grid, dim3(BR), 0, h->stream, h->U, h->sa, h->vT, h->bv, h->wd, a);
+  });
   launched("bank_mark_kernel");
 }
 
@@ -162,13 +73,13 @@ int word_chunk(const mvb_index* h, int64_t own) {
 struct Timed {  // the events around a call's launches
   mvb_index* h;
   explicit Timed(mvb_index* h_) : h(h_) {
-    h->timed = false;
+    h->timed = 0;
     HIPCHK(hipEventRecord(h->ev[0], h->stream));
   }
   void done() {
     HIPCHK(hipEventRecord(h->ev[1], h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->timed = true;
+    h->timed = 1;
   }
 };
 
@@ -179,71 +90,20 @@ extern "C" {
 const char* mvb_last_error(mvb_index* h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 int mvb_create(int device, int proj_dim, const float* Wm, int same_idx, mvb_index** out) try {
-  need(out != nullptr, "out is NULL");
-  *out = nullptr;
-  need(proj_dim == 512 || proj_dim == 768, "proj_dim = " + std::to_string(proj_dim) + ": the matcher runs on 512 or 768 features");
-  need(same_idx == 0 || same_idx == 1, "same_idx = " + std::to_string(same_idx) + ": 0 or 1");
-  need(Wm != nullptr, "the matcher weight is NULL");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, MVB_ERR_HIP, "no HIP device: the bank audit has no CPU fallback");
-  need(device >= 0 && device < ndev, "device " + std::to_string(device) + " of " + std::to_string(ndev));
-  HIPCHK(hipSetDevice(device));
-  mvb_index* h = new mvb_index();
-  h->device = device; h->P = proj_dim; h->same_idx = same_idx;
-  try {
-    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : h->ev) HIPCHK(hipEventCreate(&e));
-    float* wm = nullptr;
-    HIPCHK(hipMalloc((void**)&h->wd, (size_t)3 * h->P * sizeof(float)));
-    HIPCHK(hipMalloc((void**)&h->gstate, sizeof(BankGreedyState)));
-    HIPCHK(hipMalloc((void**)&wm, (size_t)6 * h->P * sizeof(float)));
-    hipError_t e = hipMemcpyAsync(wm, Wm, (size_t)6 * h->P * sizeof(float), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(bank_weight_delta_kernel, dim3((3 * h->P + 255) / 256), dim3(256), 0, h->stream, wm, h->wd, h->P);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(wm);
-    hipchk(e, "uploading the matcher weight");
-  } catch (...) {
-    mvb_destroy(h);
-    throw;
-  }
-  *out = h;
+  kept_create("bank audit", mvb_destroy, device, proj_dim, Wm, same_idx, out, [](mvb_index* h) { HIPCHK(hipMalloc((void**)&h->gstate, sizeof(BankGreedyState))); });
   return MVB_OK;
 } catch (...) { return on_exception(nullptr); }
 
 void mvb_destroy(mvb_index* h) {
   if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->U, (void*)h->sa, (void*)h->cls, (void*)h->wd, (void*)h->vdev, (void*)h->vT, (void*)h->bv, (void*)h->thr, (void*)h->out, (void*)h->mult,
-                  (void*)h->sole_of, (void*)h->tiles, (void*)h->taken, (void*)h->part, (void*)h->order, (void*)h->gained, (void*)h->gstate, (void*)h->bits,
-                  (void*)h->pos, (void*)h->covered})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  kept_destroy_common(h, {h->thr, h->out, h->mult, h->sole_of, h->tiles, h->taken, h->part, h->order, h->gained, h->gstate, h->bits, h->pos, h->covered});
   delete h;
 }
 
 int mvb_add(mvb_index* h, const float* embed, int64_t n) try {
   if (!h) return fail(nullptr, MVB_ERR_ARG, "index is NULL");
   drop_marking(h);
-  need(n >= 0, "n = " + std::to_string(n) + " rows");
-  need(n <= MVB_MAX_ROWS - h->n, "the index would hold more than 2^31 - 2 rows");
-  if (n == 0) return MVB_OK;
-  need(embed != nullptr, "the embeddings are NULL");
-  HIPCHK(hipSetDevice(h->device));
-  reserve_rows(h, h->n + n);
-  HIPCHK(hipMemcpyAsync(h->U + (size_t)h->n * h->P, embed, (size_t)n * h->P * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemsetAsync(h->cls + h->n, 0, (size_t)n, h->stream));
-  const dim3 grid((unsigned)((n + 3) / 4)), block(256);
-  if (h->P == 512) hipLaunchKernelGGL(bank_row_term_kernel<512>, grid, block, 0, h->stream, h->U, h->wd, h->sa, (long long)h->n, (long long)n);
-  else hipLaunchKernelGGL(bank_row_term_kernel<768>, grid, block, 0, h->stream, h->U, h->wd, h->sa, (long long)h->n, (long long)n);
-  launched("bank_row_term_kernel");
-  HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's buffer is free again, and the rows count only once they are there)
-  h->n += n;
+  kept_add(h, embed, n);
   return MVB_OK;
 } catch (...) { return on_exception(h); }
 
@@ -259,27 +119,16 @@ int64_t mvb_count(mvb_index* h) { return h ? h->n : 0; }
 int mvb_set_classes(mvb_index* h, const uint8_t* cls, int64_t first, int64_t n) try {
   if (!h) return fail(nullptr, MVB_ERR_ARG, "index is NULL");
   drop_marking(h);
-  need(first >= 0 && n >= 0 && first <= h->n && n <= h->n - first,
-       "rows [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are not within the " + std::to_string(h->n) + " rows of the index");
-  if (n == 0) return MVB_OK;
-  need(cls != nullptr, "the classes are NULL");
-  for (int64_t i = 0; i < n; ++i) need(cls[i] <= 1, "cls[" + std::to_string(i) + "] = " + std::to_string((int)cls[i]) + ": a class is 0 or 1");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemcpyAsync(h->cls + first, cls, (size_t)n, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  kept_set_classes(h, cls, first, n);
   return MVB_OK;
 } catch (...) { return on_exception(h); }
 
 int mvb_mark(mvb_index* h, const float* v, int Q, const float* thres, int64_t first, int64_t count) try {
   if (!h) return fail(nullptr, MVB_ERR_ARG, "index is NULL");
   drop_marking(h);
-  h->timed = false;
-  need(v != nullptr, "the vectors are NULL");
-  need(Q >= 1 && Q <= MVB_MAX_VECTORS, "Q = " + std::to_string(Q) + ": 1 <= Q <= 4096");
-  need(first >= 0 && count >= 0 && first <= h->n && count <= h->n - first,
-       "rows [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) + ") are not within the " + std::to_string(h->n) + " rows of the index");
-  need(thres != nullptr, "the thresholds are NULL");
-  for (int i = 0; i < Q; ++i) need(std::isfinite(thres[i]), "thres[" + std::to_string(i) + "] is not finite");
+  h->timed = 0;
+  check_range(h, "vectors", v, Q, first, count);
+  check_thresholds(thres, Q);
   const int64_t W = (count + 63) / 64;
   const int64_t bytes = 8 * (int64_t)Q * W;
   need(bytes <= MVB_MAX_MARK_BYTES, "the marking of " + std::to_string(Q) + " vectors over " + std::to_string(count) + " rows takes " + std::to_string(bytes) +
@@ -294,23 +143,19 @@ int mvb_mark(mvb_index* h, const float* v, int Q, const float* thres, int64_t fi
   const int64_t nblocks = (count + block_rows - 1) / block_rows;
   const int group = std::min(h->plan_vector_group ? h->plan_vector_group : Q, Q);  // (vT of 4096 vectors is 8 MB at 512 features: one group unless the test plan says otherwise)
   const int Qs_max = (group + BK_QT - 1) / BK_QT * BK_QT;
-  grow(h->vdev, h->vdev_n, (size_t)Q * h->P);
   grow(h->thr, h->thr_n, (size_t)Q);
   grow(h->vT, h->vT_n, (size_t)h->P * Qs_max);
   grow(h->bv, h->bv_n, (size_t)Qs_max);
   grow(h->bits, h->bits_n, (size_t)Q * W);
   grow(h->pos, h->pos_n, (size_t)W);
   grow(h->covered, h->covered_n, (size_t)W);
-  HIPCHK(hipMemcpyAsync(h->vdev, v, (size_t)Q * h->P * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  kept_upload_vectors(h, v, Q);
   HIPCHK(hipMemcpyAsync(h->thr, thres, (size_t)Q * sizeof(float), hipMemcpyHostToDevice, h->stream));
   Timed t(h);
   for (int q0 = 0; q0 < Q; q0 += group) {
     const int nq = std::min(group, Q - q0);
     const int Qs = (nq + BK_QT - 1) / BK_QT * BK_QT;
-    const float* vg = h->vdev + (size_t)q0 * h->P;
-    if (h->P == 512) hipLaunchKernelGGL(bank_vector_prep_kernel<512>, dim3((Qs + 63) / 64), dim3(64), 0, h->stream, vg, h->wd, h->vT, h->bv, nq, Qs);
-    else hipLaunchKernelGGL(bank_vector_prep_kernel<768>, dim3((Qs + 63) / 64), dim3(64), 0, h->stream, vg, h->wd, h->vT, h->bv, nq, Qs);
-    launched("bank_vector_prep_kernel");
+    kept_vector_prep(h, q0, nq, Qs);
     BankMarkArgs a{};
     a.first = first; a.count = count; a.nblocks = nblocks; a.W = W; a.nq = nq; a.Qs = Qs; a.q0 = q0; a.same_idx = h->same_idx; a.thr = h->thr;
     a.bits = h->bits + (size_t)q0 * W;  // the group's slice of the full matrix
@@ -332,7 +177,7 @@ int mvb_totals(mvb_index* h, int64_t* claimed) try {
   need(claimed != nullptr, "the output buffer is NULL");
   const size_t n = (size_t)h->Q * 2;
   if (h->count == 0) {
-    h->timed = false;
+    h->timed = 0;
     std::fill(claimed, claimed + n, (int64_t)0);
     return MVB_OK;
   }
@@ -353,7 +198,7 @@ int mvb_multiplicity(mvb_index* h, int64_t* hist, int64_t* sole, uint16_t* mult,
   need(hist != nullptr && sole != nullptr, "an output buffer is NULL");
   const size_t nh = (size_t)2 * (h->Q + 1), ns = (size_t)2 * h->Q;
   if (h->count == 0) {
-    h->timed = false;
+    h->timed = 0;
     std::fill(hist, hist + nh, (int64_t)0);
     std::fill(sole, sole + ns, (int64_t)0);
     return MVB_OK;
@@ -390,7 +235,7 @@ int mvb_overlap(mvb_index* h, int64_t* overlap) try {
   const int Q = h->Q;
   const size_t n = (size_t)Q * Q * 2;
   if (h->count == 0) {
-    h->timed = false;
+    h->timed = 0;
     std::fill(overlap, overlap + n, (int64_t)0);
     return MVB_OK;
   }
@@ -434,7 +279,7 @@ int mvb_greedy(mvb_index* h, int64_t w_pos, int64_t w_neg, const uint8_t* fixed,
   const int limit = std::min(max_rounds, free_vectors);
   need(limit == 0 || (order != nullptr && gained != nullptr), "an output buffer is NULL");
   if (h->count == 0 || limit == 0 || w_pos == 0) {  // (no gain can be positive)
-    h->timed = false;
+    h->timed = 0;
     *rounds = 0;
     return MVB_OK;
   }
@@ -482,19 +327,14 @@ int mvb_greedy(mvb_index* h, int64_t w_pos, int64_t w_neg, const uint8_t* fixed,
 
 int mvb_kernel_ms(mvb_index* h, float* ms) try {
   if (!h) return fail(nullptr, MVB_ERR_ARG, "index is NULL");
-  need(ms != nullptr, "ms is NULL");
-  need(h->timed, "the last call launched no kernel");
-  float a = 0.f;
-  HIPCHK(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-  *ms = a;
+  kept_kernel_ms(h, ms, "the last call launched no kernel");
   return MVB_OK;
 } catch (...) { return on_exception(h); }
 
 int mvb_test_plan(mvb_index* h, int block_rows, int vector_group, int word_chunk) try {
   if (!h) return fail(nullptr, MVB_ERR_ARG, "index is NULL");
   drop_marking(h);
-  need(block_rows == 0 || block_rows == 64 || block_rows == 128 || block_rows == 256 || block_rows == 512,
-       "block_rows = " + std::to_string(block_rows) + ": 0, 64, 128, 256 or 512");
+  check_block_rows(block_rows);
   need(vector_group >= 0 && vector_group <= MVB_MAX_VECTORS, "vector_group = " + std::to_string(vector_group) + ": 0 .. 4096");
   need(word_chunk >= 0 && word_chunk <= (1 << 24), "word_chunk = " + std::to_string(word_chunk) + ": 0 .. 2^24");
   h->plan_block_rows = block_rows; h->plan_vector_group = vector_group; h->plan_word_chunk = word_chunk;

@@ -2,12 +2,8 @@
 // a population count over ANDs of rows and columns of one bit matrix, the marking B [Q][W] (W = ceil(count / 64) words per vector, rows numbered from the range's
 // first row): B[q][n] = P(same)[n, q] >= thres[q] in IEEE fp32 (a NaN claims nothing).  Only integers leave the device.
 //
-// P(same)[n, g] is, bit for bit, the fp32 value the engine's matcher produces for the pair.  That value depends on the pair alone, so its arithmetic is restated here
-// (deliberately: this library includes no header of another library of this tree, whose kernels it would otherwise instantiate):
-//   sa_n    = sum (W_a[0] - W_a[1]) . u_n   lane l takes features l + 64 j by fmaf, j ascending from 0; then the six-step DPP ladder of bk_wave_sum
-//   bv_g    = fma chain of (W_b[0] - W_b[1])[i] * v_g[i],           i ascending, from 0
-//   dd_{n,g} = fma chain of (W_c[0] - W_c[1])[i] * |u_n[i] - v_g[i]|, i ascending, from 0      (the weight differences are formed in fp32 first)
-//   delta = (sa_n + bv_g) + dd;  e = expf(-|delta|);  inv = 1 / (1 + e);  P_0 = delta >= 0 ? inv : e inv;  P_1 the other;  P(same) = P_{same_idx}
+// P(same)[n, g] is, bit for bit, the fp32 value the engine's matcher produces for the pair: kept_terms.h states its arithmetic, sa_n and bv_g included, once for the
+// three kept-corpus libraries (this library includes no header of another library of this tree, whose kernels it would otherwise instantiate).
 //
 // Plan (bank.hip drives it):
 //   bank_row_term_kernel      sa_n, once per row when the row is added: one wave per row
@@ -33,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kept_terms.h"
+
 #define BK_QT 16          // vectors per workgroup tile of the mark kernel = chains per lane
 #define BK_MI 32          // features staged per step
 #define BK_GRID_Y 1024    // row blocks per z-slice of the mark kernel's grid
@@ -44,19 +42,6 @@
 typedef float bk_f4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long bk_u64;
 
-// Wave-wide sum, the matcher's ladder: row_shr 1, 2, 4, 8, row_bcast 15, row_bcast 31, lane 63 read
-__device__ __forceinline__ float bk_wave_sum(float x) {
-#define BK_SUM_STEP(CTRL, ROWS) x += __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), CTRL, ROWS, 0xf, false));
-  BK_SUM_STEP(0x111, 0xf)
-  BK_SUM_STEP(0x112, 0xf)
-  BK_SUM_STEP(0x114, 0xf)
-  BK_SUM_STEP(0x118, 0xf)
-  BK_SUM_STEP(0x142, 0xa)
-  BK_SUM_STEP(0x143, 0xc)
-#undef BK_SUM_STEP
-  return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(x), 63));
-}
-
 // ---- the weight differences, formed in fp32 on the device: wd [3][P] = W_m[0] - W_m[1] for the W_a, W_b and W_c thirds
 __global__ __launch_bounds__(256) void bank_weight_delta_kernel(const float* __restrict__ Wm, float* __restrict__ wd, int P) {
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -66,29 +51,13 @@ __global__ __launch_bounds__(256) void bank_weight_delta_kernel(const float* __r
 // ---- sa_n for rows [first, first + n): one wave per row
 template <int P>
 __global__ __launch_bounds__(256) void bank_row_term_kernel(const float* __restrict__ U, const float* __restrict__ wd, float* __restrict__ sa, long long first, long long n) {
-  const int lane = threadIdx.x & 63;
-  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= n) return;
-  const float* u = U + (size_t)(first + r) * P;
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < P / 64; ++j) s = fmaf(wd[lane + 64 * j], u[lane + 64 * j], s);
-  s = bk_wave_sum(s);
-  if (lane == 0) sa[first + r] = s;
+  ks_row_term<P>(U, wd, sa, first, n);
 }
 
 // ---- one group of nq vectors v [nq][P] -> vT [P][Qs] (zeros behind nq) and bv [Qs]; one thread per slot
 template <int P>
 __global__ __launch_bounds__(64) void bank_vector_prep_kernel(const float* __restrict__ v, const float* __restrict__ wd, float* __restrict__ vT, float* __restrict__ bv, int nq, int Qs) {
-  const int q = blockIdx.x * 64 + threadIdx.x;
-  if (q >= Qs) return;
-  float s = 0.f;
-  for (int i = 0; i < P; ++i) {
-    const float x = q < nq ? v[(size_t)q * P + i] : 0.f;
-    s = fmaf(wd[P + i], x, s);
-    vT[(size_t)i * Qs + q] = x;
-  }
-  bv[q] = s;
+  ks_vector_prep<P>(v, wd, vT, bv, nq, Qs);
 }
 
 struct BankMarkArgs {

@@ -1,12 +1,8 @@
 // Per-anchor retrieval: for every query vector g (an anchor of the bank, or the embedding of a fresh CVE description) the k best-matching rows of a kept
 // corpus — the TRANSPOSE of match_topk.h, which ranks anchors per row.  Here N (rows) >> Q (query vectors).
 //
-// The result is defined bit for bit: P(same)[n, g] is the fp32 value the engine's matcher (match_topk.h) produces for that pair.  That value depends on
-// the pair alone, so its arithmetic is restated here (NOT included: match_topk.h's inline launchers would instantiate the engine's kernels into this library):
-//   sa_n    = sum (W_a[0] - W_a[1]) . u_n   lane l takes features l + 64 j by fmaf, j ascending from 0; then the six-step DPP ladder of rt_wave_sum
-//   bv_g    = fma chain of (W_b[0] - W_b[1])[i] * v_g[i],           i ascending, from 0
-//   dd_{n,g} = fma chain of (W_c[0] - W_c[1])[i] * |u_n[i] - v_g[i]|, i ascending, from 0      (the weight differences are formed in fp32 first)
-//   delta = (sa_n + bv_g) + dd;  e = expf(-|delta|);  inv = 1 / (1 + e);  P_0 = delta >= 0 ? inv : e inv;  P_1 the other;  P(same) = P_{same_idx}
+// The result is defined bit for bit: P(same)[n, g] is the fp32 value the engine's matcher (match_topk.h) produces for that pair.  kept_terms.h states its arithmetic,
+// sa_n and bv_g included, once for the three kept-corpus libraries.
 // ranking per g: (rt_key(P) descending, row ascending), rt_key(NaN) = 2.0.
 //
 // Plan (retrieve.hip drives it):
@@ -27,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kept_terms.h"
+
 #define RT_KMAX 64
 #define RT_QT 16          // query vectors per workgroup tile = chains per lane
 #define RT_MI 32          // features staged per step
@@ -40,19 +38,6 @@ typedef float rt_f4 __attribute__((ext_vector_type(4)));
 
 // rank key: NaN ranks above every probability (match_topk.h mk_key)
 __device__ __forceinline__ float rt_key(float x) { return x != x ? 2.0f : x; }
-
-// Wave-wide sum, the ladder of match_topk.h mk_wave_sum: row_shr 1, 2, 4, 8, row_bcast 15, row_bcast 31, lane 63 read
-__device__ __forceinline__ float rt_wave_sum(float x) {
-#define RT_SUM_STEP(CTRL, ROWS) x += __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), CTRL, ROWS, 0xf, false));
-  RT_SUM_STEP(0x111, 0xf)
-  RT_SUM_STEP(0x112, 0xf)
-  RT_SUM_STEP(0x114, 0xf)
-  RT_SUM_STEP(0x118, 0xf)
-  RT_SUM_STEP(0x142, 0xa)
-  RT_SUM_STEP(0x143, 0xc)
-#undef RT_SUM_STEP
-  return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(x), 63));
-}
 
 // Wave-wide maximum of one 64-bit word per lane, every lane gets it (the same ladder)
 __device__ __forceinline__ unsigned long long rt_wave_max64(unsigned long long x) {
@@ -115,29 +100,13 @@ __global__ __launch_bounds__(256) void report_weight_delta_kernel(const float* _
 // ---- sa_n for rows [first, first + n): one wave per row
 template <int P>
 __global__ __launch_bounds__(256) void report_row_term_kernel(const float* __restrict__ U, const float* __restrict__ wd, float* __restrict__ sa, long long first, long long n) {
-  const int lane = threadIdx.x & 63;
-  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= n) return;
-  const float* u = U + (size_t)(first + r) * P;
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < P / 64; ++j) s = fmaf(wd[lane + 64 * j], u[lane + 64 * j], s);
-  s = rt_wave_sum(s);
-  if (lane == 0) sa[first + r] = s;
+  ks_row_term<P>(U, wd, sa, first, n);
 }
 
 // ---- one group of nq query vectors v [nq][P] -> vT [P][Qs] (zeros behind nq) and bv [Qs]; one thread per slot
 template <int P>
 __global__ __launch_bounds__(64) void report_query_prep_kernel(const float* __restrict__ v, const float* __restrict__ wd, float* __restrict__ vT, float* __restrict__ bv, int nq, int Qs) {
-  const int q = blockIdx.x * 64 + threadIdx.x;
-  if (q >= Qs) return;
-  float s = 0.f;
-  for (int i = 0; i < P; ++i) {
-    const float x = q < nq ? v[(size_t)q * P + i] : 0.f;
-    s = fmaf(wd[P + i], x, s);
-    vT[(size_t)i * Qs + q] = x;
-  }
-  bv[q] = s;
+  ks_vector_prep<P>(v, wd, vT, bv, nq, Qs);
 }
 
 struct ReportScoreArgs {

@@ -19,6 +19,8 @@ from typing import Optional
 
 import numpy as np
 
+from .kept_index import KeptIndex, _check_array, _int, _ptr, load_side_library  # noqa: F401  (the kept-corpus index the three libraries share)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmemvul_retrieve.so")
 
@@ -40,134 +42,17 @@ _SIGNATURES = {
 }
 RETRIEVE_SYMBOLS = list(_SIGNATURES)
 
-_libs = {}
-
 
 def load_library(path: Optional[str] = None):
     """dlopen libmemvul_retrieve.so and declare the prototypes.  Raises RuntimeError if it is missing: there is no other implementation to fall back to."""
-    path = path or LIB_PATH
-    if path in _libs:
-        return _libs[path]
-    if not os.path.exists(path):
-        raise RuntimeError(f"libmemvul_retrieve.so not found at {path}: build it with `python -m memvul_amd.build` (hipcc --offload-arch=gfx950); "
-                           "per-anchor retrieval has no CPU fallback")
-    try:
-        lib = C.CDLL(path, mode=C.RTLD_LOCAL)
-    except OSError as e:  # pragma: no cover
-        raise RuntimeError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
-        fn.restype, fn.argtypes = res, args
-    _libs[path] = lib
-    return lib
+    return load_side_library(path or LIB_PATH, "libmemvul_retrieve.so", _SIGNATURES, "per-anchor retrieval has no CPU fallback")
 
 
-def _ptr(a: np.ndarray):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _check_array(a, what: str, width: int) -> np.ndarray:
-    """float32, C-contiguous, [n, width]: checked, never converted (a silent copy of a 2.5 GB corpus is not a service)."""
-    if not isinstance(a, np.ndarray):
-        raise TypeError(f"{what}: a numpy array, not {type(a).__name__}")
-    if a.dtype != np.float32:
-        raise TypeError(f"{what}: float32, not {a.dtype}")
-    if a.ndim != 2 or a.shape[1] != width:
-        raise ValueError(f"{what}: shape [n, {width}], not {list(a.shape)}")
-    if not a.flags["C_CONTIGUOUS"]:
-        raise ValueError(f"{what}: must be C-contiguous")
-    return a
-
-
-def _int(x, what: str) -> int:
-    if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-        raise TypeError(f"{what}: an integer, not {type(x).__name__}")
-    return int(x)
-
-
-class ReportIndex:
+class ReportIndex(KeptIndex):
     """One index <-> one GPU <-> one stream; one thread uses it at a time.  ``matcher_weight``: ``_projector.weight`` of the state dict, fp32 [2, 3 * proj_dim]."""
 
-    def __init__(self, device: int, proj_dim: int, matcher_weight, same_idx: int, lib=None):
-        self._h = None
-        device, proj_dim, same_idx = _int(device, "device"), _int(proj_dim, "proj_dim"), _int(same_idx, "same_idx")
-        if proj_dim not in (512, 768):
-            raise ValueError(f"proj_dim = {proj_dim}: the matcher runs on 512 or 768 features")
-        if same_idx not in (0, 1):
-            raise ValueError(f"same_idx = {same_idx}: 0 or 1")
-        if device < 0:
-            raise ValueError(f"device = {device}")
-        w = np.asarray(matcher_weight)
-        if w.dtype != np.float32 or w.shape != (2, 3 * proj_dim):
-            raise ValueError(f"matcher_weight: float32 [2, {3 * proj_dim}], not {w.dtype} {list(w.shape)}")
-        w = np.ascontiguousarray(w)
-        self._lib = lib if lib is not None else load_library()
-        self.P, self.same_idx, self.device = proj_dim, same_idx, device
-        h = C.c_void_p()
-        rc = self._lib.mvr_create(device, proj_dim, _ptr(w), same_idx, C.byref(h))
-        if rc != 0:
-            msg = self._lib.mvr_last_error(None)
-            raise RuntimeError(f"mvr_create failed ({rc}): {msg.decode() if msg else ''}")
-        self._h = h
-
-    # -- plumbing
-    def _check(self, rc: int, what: str):
-        if rc != 0:
-            msg = self._lib.mvr_last_error(self._h)
-            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
-
-    def _handle(self):
-        if self._h is None:
-            raise RuntimeError("the ReportIndex is closed")
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mvr_destroy(self._h)
-        self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    # -- the rows
-    def add(self, embed: np.ndarray):
-        """Append rows: float32 [n, proj_dim], C-contiguous.  Rows are numbered in order of arrival."""
-        h = self._handle()
-        embed = _check_array(embed, "embed", self.P)
-        if len(self) + embed.shape[0] > MAX_ROWS:
-            raise ValueError("the index would hold more than 2^31 - 2 rows")
-        self._check(self._lib.mvr_add(h, _ptr(embed), embed.shape[0]), "mvr_add")
-
-    def reset(self):
-        """Forget the rows, keep the weights."""
-        self._check(self._lib.mvr_reset(self._handle()), "mvr_reset")
-
-    def __len__(self) -> int:
-        return int(self._lib.mvr_count(self._handle()))
-
-    def _range(self, first, count):
-        n = len(self)
-        first = _int(first, "first")
-        count = n - first if count is None else _int(count, "count")
-        if first < 0 or count < 0 or first + count > n:
-            raise ValueError(f"rows [{first}, {first} + {count}) are not within the {n} rows of the index")
-        return first, count
-
-    def _vectors(self, vectors) -> np.ndarray:
-        vectors = _check_array(vectors, "vectors", self.P)
-        if not 1 <= vectors.shape[0] <= MAX_QUERIES:
-            raise ValueError(f"{vectors.shape[0]} query vectors: 1 <= Q <= {MAX_QUERIES}")
-        return vectors
+    PREFIX, VECTORS, MAX_VECTORS, MAX_ROWS = "mvr_", "query vectors", MAX_QUERIES, MAX_ROWS
+    _load = staticmethod(lambda: load_library())
 
     # -- the questions
     def query(self, vectors: np.ndarray, k: int, first: int = 0, count: Optional[int] = None):
@@ -196,33 +81,9 @@ class ReportIndex:
         self._check(self._lib.mvr_psame(h, _ptr(vectors), Q, first, count, _ptr(p)), "mvr_psame")
         return p
 
-    def kernel_ms(self) -> float:
-        """HIP-event time of the last query's launches, in milliseconds."""
-        ms = C.c_float()
-        self._check(self._lib.mvr_kernel_ms(self._handle(), C.byref(ms)), "mvr_kernel_ms")
-        return float(ms.value)
-
     def test_plan(self, block_rows: int = 0, fan_in: int = 0, anchor_group: int = 0):
         """Tests only: rows per block, lists per merge launch, query vectors per group (0 = the library's own choice).  No result depends on them."""
         self._check(self._lib.mvr_test_plan(self._handle(), int(block_rows), int(fan_in), int(anchor_group)), "mvr_test_plan")
-
-    @classmethod
-    def from_sweep(cls, engine, matcher_weight, same_idx: int, chunk: int = 65536, index_factory=None):
-        """An index over the kept embeddings of the engine's last ``bucketed_sweep(..., keep=True)``, in the ORIGINAL row order, downloaded ``chunk`` rows at a time
-        (one download and one upload per kept sweep: the engine's ABI has no entry that hands its resident embeddings over on the device)."""
-        chunk = _int(chunk, "chunk")
-        if chunk < 1:
-            raise ValueError(f"chunk = {chunk}")
-        embed = engine.sweep_embeddings(0, None, chunk)  # (raises unless the last sweep kept its embeddings; host memory: the whole corpus once, n * P * 4 bytes)
-        index = (index_factory or cls)(engine.device, engine.P, matcher_weight, same_idx)
-        try:
-            for s0 in range(0, embed.shape[0], chunk):
-                index.add(np.ascontiguousarray(embed[s0:s0 + chunk], dtype=np.float32))
-        except Exception:
-            index.close()
-            raise
-        return index
-
 
 def format_reports(labels, urls, p: np.ndarray, rows: np.ndarray, first: int = 0) -> list:
     """One entry per query vector: {"anchor": label, "reports": [{"Issue_Url", "row", "prob"}, ...]} (exhausted slots left out).  rows: row numbers of the index;

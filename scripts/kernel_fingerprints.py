@@ -35,7 +35,8 @@ def main(argv=None) -> int:
     ap.add_argument("--against", help="a map written by --out: compare, exit 1 on any difference")
     ap.add_argument("--out", help="write the map here instead of printing it")
     a = ap.parse_args(argv)
-    fp = build.kernel_fingerprints(a.lib or (build.LIB_PATH_BANK if a.bank else build.LIB_PATH_CLAIMS if a.claims else build.LIB_PATH_RETRIEVE if a.retrieve else build.LIB_PATH_TOK if a.tok else build.LIB_PATH_DEV if a.dev else build.LIB_PATH))
+    side = [key for key in reversed(list(build.SIDE_LIBS)) if getattr(a, key)]  # (several flags: the last of the table wins, as before)
+    fp = build.kernel_fingerprints(a.lib or (build.side_lib_path(side[0]) if side else build.LIB_PATH_DEV if a.dev else build.LIB_PATH))
     if a.out:
         with open(a.out, "w") as f:
             json.dump(fp, f, indent=0, sort_keys=True)

@@ -77,13 +77,19 @@ def test_build_all_leaves_five_fresh_libraries_and_returns_two_paths(libs):
         assert "libmemvul_bank" not in needed, other
 
 
+def test_the_kernels_are_the_recorded_ones(libs):
+    ri.check_kernels_are_the_recorded_ones(build.LIB_PATH_BANK, "bank")
+
+
 def test_the_module_prints_the_new_path_too():
     src = open(os.path.join(ROOT, "memvul_amd", "build.py")).read()
     assert re.search(r'__name__ == "__main__":\n\s+print\(.*LIB_PATH_BANK', src)
 
 
 def test_the_other_libraries_do_not_know_the_new_files(libs, monkeypatch):
-    new = [os.path.join(CSRC, s) for s in build.BANK_SOURCES] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in build.BANK_HEADERS]
+    new, _ = ri.own_and_shared("bank")
+    assert build.SIDE_LIBS["bank"] == (build.BANK_LIB_NAME, build.BANK_SOURCES, build.BANK_HEADERS)
+    ri.check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
     assert sorted(os.path.basename(p) for p in new) == ["bank.hip", "bank_cover.h", "memvul_bank.h"]
     opened = []
     real_open = open
@@ -104,7 +110,7 @@ def test_the_other_libraries_do_not_know_the_new_files(libs, monkeypatch):
         if name not in ("bank.hip", "bank_cover.h"):
             assert "bank_cover.h" not in text and "memvul_bank.h" not in text, name
     src = open(os.path.join(CSRC, "bank.hip")).read() + open(os.path.join(CSRC, "bank_cover.h")).read()
-    assert re.findall(r'#include\s+"([^"]+)"', src) == ["../../include/memvul_bank.h", "bank_cover.h"]
+    assert re.findall(r'#include\s+"([^"]+)"', src) == ["../../include/memvul_bank.h", "bank_cover.h", "kept_index.h", "kept_terms.h"]
     new_map = build.kernel_fingerprints(build.LIB_PATH_BANK)
     for n in NEW_KERNELS:
         assert any(n in k and k.endswith(".kd") for k in new_map), n

@@ -68,8 +68,14 @@ def test_build_all_still_returns_two_paths_and_leaves_the_new_library_fresh(libs
     assert "libmemvul" not in "".join(ln for ln in needed.splitlines() if "NEEDED" in ln)  # it links against nothing of this tree
 
 
+def test_the_kernels_are_the_recorded_ones(libs):
+    ri.check_kernels_are_the_recorded_ones(build.LIB_PATH_CLAIMS, "claims")
+
+
 def test_the_other_libraries_do_not_know_the_new_files(libs, monkeypatch):
-    new = [os.path.join(CSRC, s) for s in build.CLAIMS_SOURCES] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in build.CLAIMS_HEADERS]
+    new, _ = ri.own_and_shared("claims")
+    assert build.SIDE_LIBS["claims"] == (build.CLAIMS_LIB_NAME, build.CLAIMS_SOURCES, build.CLAIMS_HEADERS)
+    ri.check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
     assert sorted(os.path.basename(p) for p in new) == ["claim_sweep.h", "claims.hip", "memvul_claims.h"]
     opened = []
     real_open = open
@@ -82,6 +88,7 @@ def test_the_other_libraries_do_not_know_the_new_files(libs, monkeypatch):
     build.source_fingerprint()
     build.source_fingerprint((), build.RETRIEVE_SOURCES, build.RETRIEVE_HEADERS)
     build.source_fingerprint((), build.TOK_SOURCES, build.TOK_HEADERS)
+    build.source_fingerprint((), build.BANK_SOURCES, build.BANK_HEADERS)
     monkeypatch.undo()
     assert opened and not set(opened) & set(new)
     for name in os.listdir(CSRC):  # nothing any other library is built from includes the new header

@@ -51,6 +51,71 @@ def test_no_cpp_exception_can_cross_the_boundary():
     assert src.count("catch (...) { return on_exception(") == len(heads)
 
 
+# ---- the two headers the three kept-corpus libraries share (csrc/kept_index.h, csrc/kept_terms.h) ------------------------------------------------------------------
+
+KEPT_SHARED = ("kept_index.h", "kept_terms.h")
+KEPT_OWN = {"retrieve": ("retrieve.hip", "report_topk.h"), "claims": ("claims.hip", "claim_sweep.h"), "bank": ("bank.hip", "bank_cover.h")}  # (source, kernel header)
+
+
+def opened_by_fingerprint(monkeypatch, sources=None, headers=None) -> set:
+    """The files build.source_fingerprint opens for a library (default: libmemvul_hip.so, either build)."""
+    opened = []
+    real_open = open
+
+    def spy(path, *a, **kw):
+        opened.append(os.path.abspath(path) if isinstance(path, str) else path)
+        return real_open(path, *a, **kw)
+
+    monkeypatch.setattr("builtins.open", spy)
+    build.source_fingerprint((), sources, headers)
+    monkeypatch.undo()
+    assert opened
+    return set(opened)
+
+
+def own_and_shared(key: str):
+    """The files of a kept-corpus library as build.py lists them: (its own, the two it shares), as paths."""
+    _, sources, headers = build.SIDE_LIBS[key]
+    files = [os.path.join(CSRC, s) for s in sources] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in headers]
+    shared = [p for p in files if os.path.basename(p) in KEPT_SHARED]
+    assert sorted(os.path.basename(p) for p in shared) == sorted(KEPT_SHARED), key
+    return [p for p in files if p not in shared], shared
+
+
+def check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch):
+    """Opened by exactly the three kept-corpus libraries' fingerprints — never by libmemvul_hip.so's or the tokeniser library's, whose stamps bench.py keys on — and
+    included by no file under csrc/ outside those libraries' own sources."""
+    shared = {os.path.join(CSRC, h) for h in KEPT_SHARED}
+    assert sorted(k for k, (_, _, headers) in build.SIDE_LIBS.items() if set(KEPT_SHARED) & set(headers)) == sorted(KEPT_OWN)
+    for key in KEPT_OWN:
+        assert shared <= opened_by_fingerprint(monkeypatch, *build.SIDE_LIBS[key][1:]), key
+    assert not shared & opened_by_fingerprint(monkeypatch)
+    assert not shared & opened_by_fingerprint(monkeypatch, build.TOK_SOURCES, build.TOK_HEADERS)
+    assert not set(KEPT_SHARED) & set(build.HEADERS + build.KERNEL_HEADERS + build.TOK_HEADERS + build.SOURCES + build.TOK_SOURCES)
+    theirs = {f for pair in KEPT_OWN.values() for f in pair} | set(KEPT_SHARED)
+    includes = {}
+    for name in os.listdir(CSRC):
+        text = open(os.path.join(CSRC, name)).read()
+        includes[name] = re.findall(r'#include\s+"([^"]+)"', text)
+        if name not in theirs:
+            assert not any(h in text for h in KEPT_SHARED), name
+    for source, header in KEPT_OWN.values():  # the host side goes into the .hip file, the device side into its kernel header, and neither shared header includes anything of this tree
+        assert "kept_index.h" in includes[source] and "kept_terms.h" not in includes[source], source
+        assert "kept_terms.h" in includes[header] and "kept_index.h" not in includes[header], header
+    assert includes["kept_index.h"] == [] and includes["kept_terms.h"] == []
+
+
+def check_kernels_are_the_recorded_ones(lib_path: str, flag: str):
+    """build.kernel_fingerprints of a side library against the map recorded under profiles/: a refactor of the shared headers must leave every kernel's bytes alone."""
+    recorded = os.path.join(ROOT, "profiles", f"kernel_fingerprints_{flag}.json")
+    with open(recorded) as f:
+        want = json.load(f)
+    got = build.kernel_fingerprints(lib_path)
+    changed = sorted(set(want) ^ set(got)) + sorted(k for k in set(want) & set(got) if want[k] != got[k])
+    assert not changed, (f"{len(changed)} symbols of {os.path.basename(lib_path)} differ from {recorded}: {changed[:4]}; if the kernels were meant to change, re-record with "
+                         f"`python scripts/kernel_fingerprints.py --{flag} --out profiles/kernel_fingerprints_{flag}.json`")
+
+
 # ---- 3, 4: the build --------------------------------------------------------------------------------------------------------------------------------------------
 
 def test_build_all_returns_two_paths_and_leaves_three_fresh_libraries(libs):
@@ -59,9 +124,15 @@ def test_build_all_returns_two_paths_and_leaves_three_fresh_libraries(libs):
     assert os.path.exists(build.LIB_PATH_RETRIEVE) and os.path.basename(build.LIB_PATH_RETRIEVE) == build.RETRIEVE_LIB_NAME == "libmemvul_retrieve.so"
 
 
+def test_the_kernels_are_the_recorded_ones(libs):
+    check_kernels_are_the_recorded_ones(build.LIB_PATH_RETRIEVE, "retrieve")
+
+
 def test_the_main_library_does_not_know_the_new_files(libs, monkeypatch):
-    new = [os.path.join(CSRC, s) for s in build.RETRIEVE_SOURCES] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in build.RETRIEVE_HEADERS]
+    new, _ = own_and_shared("retrieve")
     assert sorted(os.path.basename(p) for p in new) == ["memvul_retrieve.h", "report_topk.h", "retrieve.hip"]
+    assert build.SIDE_LIBS["retrieve"] == (build.RETRIEVE_LIB_NAME, build.RETRIEVE_SOURCES, build.RETRIEVE_HEADERS)
+    check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
     opened = []
     real_open = open
 
@@ -71,6 +142,8 @@ def test_the_main_library_does_not_know_the_new_files(libs, monkeypatch):
 
     monkeypatch.setattr("builtins.open", spy)
     build.source_fingerprint()
+    for other in ("tok", "claims", "bank"):
+        build.source_fingerprint((), *build.SIDE_LIBS[other][1:])
     monkeypatch.undo()
     assert opened and not set(opened) & set(new)
     for name in os.listdir(CSRC):  # nothing the main library is built from includes the new header
