@@ -18,7 +18,6 @@ As everywhere in this package there is no CPU fallback.
 writes ONE JSON document: the dict of ``audit_of``."""
 from __future__ import annotations
 
-import argparse
 import ctypes as C
 import json
 import os
@@ -35,7 +34,6 @@ LIB_PATH = os.path.join(_HERE, "lib", "libmemvul_bank.so")
 
 MAX_VECTORS, MAX_ROWS, MAX_WEIGHT, MAX_MARK_BYTES = 4096, 2 ** 31 - 2, 1 << 20, 4 << 30  # include/memvul_bank.h
 ERR_STATE = -5
-KEY_MATCH_W = "_projector.weight"
 
 _f32p, _vp = C.POINTER(C.c_float), C.c_void_p
 _SIGNATURES = {
@@ -248,22 +246,16 @@ def run_audit(index, labels, vectors, thres, positive, candidates=None, candidat
 # ---- the command line -------------------------------------------------------------------------------------------------------------------------------------------------
 
 def main(argv=None, engine_factory=None, index_factory=None) -> int:
-    from . import audit as _audit
-    from . import binding
+    from . import kept_sweep as front
 
-    ap = argparse.ArgumentParser(prog="python -m memvul_amd.bank", description="The anchor bank of the golden file as a whole: union decision, sole claims, overlaps, greedy order.")
-    ap.add_argument("--archive", required=True, help="model.tar.gz or its extracted directory")
-    ap.add_argument("--golden", required=True, help="the golden anchor file ({cwe_id: description})")
-    ap.add_argument("--input", required=True, help="the issue reports (a test_ / validation_ file of the reader)")
+    ap = front.parser("python -m memvul_amd.bank", "The anchor bank of the golden file as a whole: union decision, sole claims, overlaps, greedy order.")
     ap.add_argument("--thres", type=float, default=0.5, help="the decision threshold of every anchor")
     ap.add_argument("--thres-file", default=None, metavar="FILE.json", help="{anchor: threshold}: per-anchor thresholds (e.g. the best_thres of memvul_amd.claims); others keep --thres")
     ap.add_argument("--top", type=int, default=20, help="how many overlapping pairs to list")
     ap.add_argument("--w-pos", type=int, default=1)
     ap.add_argument("--w-neg", type=int, default=1)
     ap.add_argument("--max-rounds", type=int, default=None)
-    ap.add_argument("--out", default=None, help="write the JSON document here instead of standard output")
-    ap.add_argument("--batch", type=int, default=512)
-    ap.add_argument("--device", type=int, default=0)
+    front.add_output(ap, "JSON document")
     args = ap.parse_args(argv)
     if not np.isfinite(args.thres):
         ap.error(f"--thres {args.thres}: a finite number")
@@ -272,13 +264,8 @@ def main(argv=None, engine_factory=None, index_factory=None) -> int:
             ap.error(f"{name} {w}: 0 .. 2^20")
     if args.top < 0 or (args.max_rounds is not None and args.max_rounds < 0):
         ap.error("--top and --max-rounds: not negative")
-    sd, config, same_idx = _audit._read_archive(args.archive)
-    if config is None:
-        ap.error("--archive must be an archive (config.json, vocabulary/, weights): the readers come from its config")
-    from . import archive as _archive
-
-    reader = _archive._build_reader(config.get("validation_dataset_reader")) or _archive._build_reader(config.get("dataset_reader"))
-    labels = list(reader.read_dataset(args.golden).keys())
+    corpus = front.read_corpus(ap, args)
+    labels = corpus.labels
     thres = np.full(len(labels), args.thres, np.float64)
     if args.thres_file is not None:
         with open(args.thres_file) as f:
@@ -290,31 +277,9 @@ def main(argv=None, engine_factory=None, index_factory=None) -> int:
             if not isinstance(t, (int, float)) or not np.isfinite(t):
                 ap.error(f"--thres-file: {a}: a finite number")
             thres[labels.index(a)] = float(t)
-    ids, lens, aids, alens = _audit._read_inputs(config, args.golden, args.input)
-    arrays = reader.read_arrays(args.input)
-    positive = np.asarray(arrays["same"], bool)
-    opts = dict(max_tokens=128 * 512, max_batch=max(512, args.batch), max_anchors=max(1024, len(alens)), same_idx=same_idx)
-    opts.update(_audit._engine_dims(sd))
-    eng = (engine_factory or binding.Engine)(args.device, **opts)
-    try:
-        eng.load_state_dict(sd)
-        for i in range(len(alens)):  # (every anchor at its own length, the bank in the file's order)
-            eng.anchor_append(np.ascontiguousarray(aids[i:i + 1, :max(int(alens[i]), 1)]), np.ascontiguousarray(alens[i:i + 1]))
-        eng.bucketed_sweep(ids[:, :max(int(lens.max()), 1)], lens, args.batch, keep=True)
-        index = BankAudit.from_sweep(eng, np.asarray(sd[KEY_MATCH_W], np.float32), same_idx, index_factory=index_factory, classes=positive)
-        try:
-            v = np.ascontiguousarray(eng.anchor_get(), dtype=np.float32)
-            doc = run_audit(index, labels, v, thres, positive, w_pos=args.w_pos, w_neg=args.w_neg, max_rounds=args.max_rounds, top=args.top)
-        finally:
-            index.close()
-    finally:
-        eng.close()
-    text = json.dumps(doc)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    else:
-        print(text)
+    with front.filled_index(corpus, args, BankAudit, engine_factory, index_factory, corpus.positive) as (index, v):
+        doc = run_audit(index, labels, v, thres, corpus.positive, w_pos=args.w_pos, w_neg=args.w_neg, max_rounds=args.max_rounds, top=args.top)
+    front.write_json(args.out, [doc])
     return 0
 
 

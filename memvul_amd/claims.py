@@ -14,9 +14,7 @@ P(same) of a pair is bit for bit what the engine's matcher gives for it, and a N
 writes one JSON line per anchor: {"anchor", "thres", "claimed", "positives", "reports": [{"Issue_Url", "row", "prob"}, ...]} and, with --grid, "grid" and "best_thres"."""
 from __future__ import annotations
 
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 from typing import Optional
@@ -30,7 +28,6 @@ LIB_PATH = os.path.join(_HERE, "lib", "libmemvul_claims.so")
 
 MAX_THRESHOLDS, MAX_VECTORS, MAX_ROWS, MAX_PAIRS = 64, 4096, 2 ** 31 - 2, 2 ** 28  # include/memvul_claims.h
 ERR_STATE = -5
-KEY_MATCH_W = "_projector.weight"
 
 _f32p, _vp = C.POINTER(C.c_float), C.c_void_p
 _SIGNATURES = {
@@ -243,20 +240,14 @@ def claims_of(index, labels, urls, vectors, thres, positive, first: int = 0, gri
 # ---- the command line ------------------------------------------------------------------------------------------------------------------------------------------
 
 def main(argv=None, engine_factory=None, index_factory=None) -> int:
-    from . import audit as _audit
-    from . import binding
+    from . import kept_sweep as front
 
-    ap = argparse.ArgumentParser(prog="python -m memvul_amd.claims", description="For every anchor of the golden file: the issue reports it claims at a threshold.")
-    ap.add_argument("--archive", required=True, help="model.tar.gz or its extracted directory")
-    ap.add_argument("--golden", required=True, help="the golden anchor file ({cwe_id: description})")
-    ap.add_argument("--input", required=True, help="the issue reports (a test_ / validation_ file of the reader)")
+    ap = front.parser("python -m memvul_amd.claims", "For every anchor of the golden file: the issue reports it claims at a threshold.")
     ap.add_argument("--thres", type=float, default=0.5, help="the decision threshold: a report is claimed when P(same) >= it")
     ap.add_argument("--grid", default=None, metavar="reference|LO:HI:STEP", help="also count the claims at every threshold of a grid and name the best by F1")
-    ap.add_argument("--anchors", default=None, metavar="LABEL[,LABEL...]", help="only these anchors (default: all of the golden file)")
+    front.add_anchors(ap)
     ap.add_argument("--counts-only", action="store_true", help="leave the reports out: counts alone")
-    ap.add_argument("--out", default=None, help="write the JSON lines here instead of standard output")
-    ap.add_argument("--batch", type=int, default=512)
-    ap.add_argument("--device", type=int, default=0)
+    front.add_output(ap, "JSON lines")
     args = ap.parse_args(argv)
     if not np.isfinite(args.thres):
         ap.error(f"--thres {args.thres}: a finite number")
@@ -266,45 +257,10 @@ def main(argv=None, engine_factory=None, index_factory=None) -> int:
             grid = parse_grid(args.grid)
         except ValueError as e:
             ap.error(f"--grid: {e}")
-    sd, config, same_idx = _audit._read_archive(args.archive)
-    if config is None:
-        ap.error("--archive must be an archive (config.json, vocabulary/, weights): the readers come from its config")
-    from . import archive as _archive
-
-    reader = _archive._build_reader(config.get("validation_dataset_reader")) or _archive._build_reader(config.get("dataset_reader"))
-    labels = list(reader.read_dataset(args.golden).keys())
-    ids, lens, aids, alens = _audit._read_inputs(config, args.golden, args.input)
-    arrays = reader.read_arrays(args.input)
-    urls, positive = arrays["urls"], np.asarray(arrays["same"], bool)
-    wanted = list(range(len(labels)))
-    if args.anchors is not None:
-        names = [a for a in args.anchors.split(",") if a]
-        missing = [a for a in names if a not in labels]
-        if missing:
-            ap.error("--anchors: not in the golden file: " + ",".join(missing))
-        wanted = [labels.index(a) for a in names]
-    opts = dict(max_tokens=128 * 512, max_batch=max(512, args.batch), max_anchors=max(1024, len(alens)), same_idx=same_idx)
-    opts.update(_audit._engine_dims(sd))
-    eng = (engine_factory or binding.Engine)(args.device, **opts)
-    try:
-        eng.load_state_dict(sd)
-        for i in range(len(alens)):  # (every anchor at its own length, the bank in the file's order)
-            eng.anchor_append(np.ascontiguousarray(aids[i:i + 1, :max(int(alens[i]), 1)]), np.ascontiguousarray(alens[i:i + 1]))
-        eng.bucketed_sweep(ids[:, :max(int(lens.max()), 1)], lens, args.batch, keep=True)
-        index = ClaimIndex.from_sweep(eng, np.asarray(sd[KEY_MATCH_W], np.float32), same_idx, index_factory=index_factory, classes=positive)
-        try:
-            v = np.ascontiguousarray(eng.anchor_get()[wanted], dtype=np.float32)
-            entries = claims_of(index, [labels[i] for i in wanted], urls, v, args.thres, positive, 0, grid, not args.counts_only)
-        finally:
-            index.close()
-    finally:
-        eng.close()
-    lines = [json.dumps(e) for e in entries]
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("".join(ln + "\n" for ln in lines))
-    else:
-        print("\n".join(lines))
+    corpus = front.read_corpus(ap, args)
+    with front.filled_index(corpus, args, ClaimIndex, engine_factory, index_factory, corpus.positive) as (index, v):
+        entries = claims_of(index, corpus.wanted_labels, corpus.urls, v, args.thres, corpus.positive, 0, grid, not args.counts_only)
+    front.write_json(args.out, entries)
     return 0
 
 

@@ -29,6 +29,7 @@ import numpy as np
 from .binding import Engine, compute_dtype_of, wanted_form, tokenize_policy
 from .custom_metric import SiameseMeasureV1
 from .data import Instance, collate
+from .kept_sweep import KEY_MATCH_W, KeptSweepState
 from .registry import HAVE_ALLENNLP, Model, TextFieldEmbedder, TokenEmbedder, Vocabulary, register_builtin
 
 logger = logging.getLogger(__name__)
@@ -161,6 +162,7 @@ class ModelMemory(Model):
         self._siamese_metric = SiameseMeasureV1(self._same_idx)
         self._engine_options = dict(engine_options or {})
         self._engine: Optional[Engine] = None
+        self._kept = KeptSweepState()  # (the last keeping sweep_arrays and the indexes over it)
 
     # ---- weights --------------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, Any], strict: bool = True):
@@ -200,8 +202,8 @@ class ModelMemory(Model):
         self._engine = Engine(self._device_index, vocab_size=vocab_size, layers=layers, max_pos=max_pos, type_vocab=type_vocab,
                               same_idx=self._same_idx, **opts)
         self._engine.load_state_dict(sd, cd)
-        self._matcher_weight = np.ascontiguousarray(sd["_projector.weight"], np.float32) if "_projector.weight" in sd else None  # (anchor_reports hands it to its index)
-        self._drop_report_index()
+        self._kept.drop()  # (a kept sweep was the old engine's)
+        self._kept.matcher_weight = np.ascontiguousarray(sd[KEY_MATCH_W], np.float32) if KEY_MATCH_W in sd else None  # (the indexes over a kept sweep take it)
         # torch's contract (AllenNLP's Model._load unpacks it): every tensor the engine needs was found by mv_load_tensor /
         # mv_finalize_weights (they fail otherwise); keys it has no use for — the BertModel's own pooler copy, position_ids — are
         # not "unexpected" to a model that declares no parameters of its own
@@ -362,14 +364,13 @@ class ModelMemory(Model):
             raise NotImplementedError("sweep_arrays() serves the test / unlabel branch (model_memory.py:133-147)")
         last = len(arrays["lens"]) if last is None else last
         lens = np.ascontiguousarray(arrays["lens"][first:last], np.int32)
-        self._kept_rows = None
-        self._drop_report_index()  # (it indexed the sweep this one replaces)
+        self._kept.drop()  # (the sweep this one replaces, and what indexed it)
         if len(lens) == 0:
             return np.zeros((0, 2), np.float32), np.zeros((0,), np.int32), None
         ids = arrays["ids"][first:last, :int(lens.max())]
         if keep or topk:  # (an engine that is never asked to keep anything is called exactly as before)
             best, best_idx, p_same = self.engine.bucketed_sweep(ids, lens, batch_size, with_probs=with_probs, keep=keep, topk=topk)
-            self._kept_rows = (first, last) if keep else None
+            self._kept.rows = (first, last) if keep else None
         else:
             best, best_idx, p_same = self.engine.bucketed_sweep(ids, lens, batch_size, with_probs=with_probs)
         self._score_arrays(arrays, first, last, best)
@@ -385,46 +386,32 @@ class ModelMemory(Model):
         """The rows of the last ``sweep_arrays(..., keep=True)`` scored against the anchor bank as it is NOW (forward_gold_instances, model_memory.py:105-115,
         appended to or rebuilt it since) by the matcher alone (l.135-147) — the encoder does not run.  Returns what ``sweep_arrays`` returns and updates the
         metric accumulators the same way."""
-        last = len(arrays["lens"]) if last is None else last
-        if getattr(self, "_kept_rows", None) != (first, last):
-            raise RuntimeError("rematch_arrays(): no kept sweep of these rows — call sweep_arrays(arrays, first, last, keep=True) first (the resident corpus keeps "
-                               "its embeddings only when asked to)")
+        last = self._kept_last("rematch_arrays", arrays, first, last)
         best, best_idx, p_same = self.engine.rematch_sweep(with_probs=with_probs)
         self._score_arrays(arrays, first, last, best)
         return best, best_idx, p_same
 
-    def _drop_report_index(self):
-        """The indexes over the kept sweep (anchor_reports', anchor_claims', anchor_bank_audit's) and the host copy of its embeddings they are filled from."""
-        index, self._report_index = getattr(self, "_report_index", None), None
-        if index is not None:
-            index.close()
-        index, self._claim_index = getattr(self, "_claim_index", None), None
-        if index is not None:
-            index.close()
-        index, self._bank_index = getattr(self, "_bank_index", None), None
-        if index is not None:
-            index.close()
-        self._kept_embed = None
+    def _kept_last(self, who: str, arrays: Dict[str, Any], first: int, last: Optional[int]) -> int:
+        """``last`` resolved, after the refusal unless rows ``first:last`` are the last keeping sweep's."""
+        last = len(arrays["lens"]) if last is None else last
+        self._kept.require(who, first, last)
+        return last
 
-    def _kept_source(self):
-        """What ``from_sweep`` of either index reads the kept embeddings from: the engine, with its download remembered on the host until BOTH indexes are filled or
-        another sweep replaces this one — whichever index is asked for second is filled without a second download (2 KB per row of host memory meanwhile)."""
-        owner, engine = self, self.engine
+    def _kept_index(self, who: str, kind: str, index_class, index_factory, classes=None):
+        return self._kept.index(who, kind, index_class, self.engine, self._same_idx, index_factory, classes)
 
-        class _Kept:
-            device, P = engine.device, engine.P
-
-            def sweep_embeddings(self, first=0, count=None, chunk=65536):
-                if getattr(owner, "_kept_embed", None) is None:
-                    owner._kept_embed = engine.sweep_embeddings(0, None, chunk)
-                e = owner._kept_embed
-                return e[first:None if count is None else first + count]
-
-        return _Kept()
-
-    def _forget_kept_embed(self):
-        if getattr(self, "_report_index", None) is not None and getattr(self, "_claim_index", None) is not None:
-            self._kept_embed = None
+    def _vectors_and_labels(self, who: str, vectors, labels):
+        """The query vectors and their names: by default the bank as it is now under the golden labels; given vectors without labels are numbered."""
+        if vectors is None:
+            vectors = self.engine.anchor_get()
+            if labels is None:
+                labels = self._golden_labels
+        vectors = np.ascontiguousarray(vectors, np.float32)
+        if labels is None:
+            labels = [str(g) for g in range(len(vectors))]
+        if len(labels) != len(vectors):
+            raise ValueError(f"{who}(): {len(labels)} labels for {len(vectors)} vectors")
+        return vectors, list(labels)
 
     def anchor_reports(self, arrays: Dict[str, Any], k: int, first: int = 0, last: Optional[int] = None, vectors=None, labels: Optional[List[str]] = None,
                        index_factory=None) -> List[Dict[str, Any]]:
@@ -435,26 +422,10 @@ class ModelMemory(Model):
         dropped when another sweep replaces it; P(same) is bit for bit the matcher's."""
         from . import retrieve
 
-        last = len(arrays["lens"]) if last is None else last
-        if getattr(self, "_kept_rows", None) != (first, last):
-            raise RuntimeError("anchor_reports(): no kept sweep of these rows — call sweep_arrays(arrays, first, last, keep=True) first (the resident corpus keeps "
-                               "its embeddings only when asked to)")
-        if vectors is None:
-            vectors = self.engine.anchor_get()
-            if labels is None:
-                labels = self._golden_labels
-        vectors = np.ascontiguousarray(vectors, np.float32)
-        if labels is None:
-            labels = [str(g) for g in range(len(vectors))]
-        if len(labels) != len(vectors):
-            raise ValueError(f"anchor_reports(): {len(labels)} labels for {len(vectors)} vectors")
-        if getattr(self, "_report_index", None) is None:
-            if getattr(self, "_matcher_weight", None) is None:
-                raise RuntimeError("anchor_reports(): the state dict held no _projector.weight")
-            self._report_index = retrieve.ReportIndex.from_sweep(self._kept_source(), self._matcher_weight, self._same_idx, index_factory=index_factory)
-            self._forget_kept_embed()
-        p, rows = self._report_index.query(vectors, k)
-        return retrieve.format_reports(list(labels), arrays["urls"], p, rows, first)
+        self._kept_last("anchor_reports", arrays, first, last)
+        vectors, labels = self._vectors_and_labels("anchor_reports", vectors, labels)
+        p, rows = self._kept_index("anchor_reports", "reports", retrieve.ReportIndex, index_factory).query(vectors, k)
+        return retrieve.format_reports(labels, arrays["urls"], p, rows, first)
 
     def anchor_claims(self, arrays: Dict[str, Any], thres=0.5, first: int = 0, last: Optional[int] = None, vectors=None, labels: Optional[List[str]] = None,
                       grid=None, index_factory=None) -> List[Dict[str, Any]]:
@@ -467,26 +438,11 @@ class ModelMemory(Model):
         that is filled once per kept sweep — a further device copy of the embeddings, 2 KB per row — and dropped when another sweep replaces it."""
         from . import claims
 
-        last = len(arrays["lens"]) if last is None else last
-        if getattr(self, "_kept_rows", None) != (first, last):
-            raise RuntimeError("anchor_claims(): no kept sweep of these rows — call sweep_arrays(arrays, first, last, keep=True) first (the resident corpus keeps "
-                               "its embeddings only when asked to)")
-        if vectors is None:
-            vectors = self.engine.anchor_get()
-            if labels is None:
-                labels = self._golden_labels
-        vectors = np.ascontiguousarray(vectors, np.float32)
-        if labels is None:
-            labels = [str(g) for g in range(len(vectors))]
-        if len(labels) != len(vectors):
-            raise ValueError(f"anchor_claims(): {len(labels)} labels for {len(vectors)} vectors")
+        last = self._kept_last("anchor_claims", arrays, first, last)
+        vectors, labels = self._vectors_and_labels("anchor_claims", vectors, labels)
         positive = np.ascontiguousarray(np.asarray(arrays["same"][first:last], bool))
-        if getattr(self, "_claim_index", None) is None:
-            if getattr(self, "_matcher_weight", None) is None:
-                raise RuntimeError("anchor_claims(): the state dict held no _projector.weight")
-            self._claim_index = claims.ClaimIndex.from_sweep(self._kept_source(), self._matcher_weight, self._same_idx, index_factory=index_factory, classes=positive)
-            self._forget_kept_embed()
-        return claims.claims_of(self._claim_index, list(labels), arrays["urls"], vectors, thres, positive, first, grid)
+        index = self._kept_index("anchor_claims", "claims", claims.ClaimIndex, index_factory, positive)
+        return claims.claims_of(index, labels, arrays["urls"], vectors, thres, positive, first, grid)
 
     def anchor_bank_audit(self, arrays: Dict[str, Any], thres=0.5, first: int = 0, last: Optional[int] = None, candidates=None,
                           candidate_labels: Optional[List[str]] = None, w_pos: int = 1, w_neg: int = 1, max_rounds: Optional[int] = None, candidate_thres=None,
@@ -500,10 +456,7 @@ class ModelMemory(Model):
         over an index that is filled once per kept sweep — from the same download as the other two indexes while that is still held — and dropped with them."""
         from . import bank
 
-        last = len(arrays["lens"]) if last is None else last
-        if getattr(self, "_kept_rows", None) != (first, last):
-            raise RuntimeError("anchor_bank_audit(): no kept sweep of these rows — call sweep_arrays(arrays, first, last, keep=True) first (the resident corpus keeps "
-                               "its embeddings only when asked to)")
+        last = self._kept_last("anchor_bank_audit", arrays, first, last)
         vectors = np.ascontiguousarray(self.engine.anchor_get(), np.float32)
         labels = list(self._golden_labels)
         if len(labels) != len(vectors):
@@ -513,12 +466,8 @@ class ModelMemory(Model):
         if not np.isfinite(np.asarray(thres, np.float64)).all():
             raise ValueError("anchor_bank_audit(): a threshold is not finite")
         positive = np.ascontiguousarray(np.asarray(arrays["same"][first:last], bool))
-        if getattr(self, "_bank_index", None) is None:
-            if getattr(self, "_matcher_weight", None) is None:
-                raise RuntimeError("anchor_bank_audit(): the state dict held no _projector.weight")
-            self._bank_index = bank.BankAudit.from_sweep(self._kept_source(), self._matcher_weight, self._same_idx, index_factory=index_factory, classes=positive)
-            self._forget_kept_embed()
-        return bank.run_audit(self._bank_index, labels, vectors, thres, positive, candidates, candidate_labels, candidate_thres, w_pos, w_neg, max_rounds, top)
+        index = self._kept_index("anchor_bank_audit", "bank", bank.BankAudit, index_factory, positive)
+        return bank.run_audit(index, labels, vectors, thres, positive, candidates, candidate_labels, candidate_thres, w_pos, w_neg, max_rounds, top)
 
     def format_records_json(self, labels: List[str], urls: List[str], p_same: np.ndarray) -> str:
         """``json.dumps(make_output_human_readable(...))`` of one batch, byte for byte, built from arrays: the line

@@ -10,9 +10,7 @@ a pair is bit for bit what the engine's matcher gives for it.  As everywhere in 
 writes one JSON line per anchor: {"anchor": label, "reports": [{"Issue_Url", "row", "prob"}, ...]}."""
 from __future__ import annotations
 
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 from typing import Optional
@@ -25,7 +23,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmemvul_retrieve.so")
 
 MAX_K, MAX_QUERIES, MAX_ROWS, MAX_PSAME = 64, 4096, 2 ** 31 - 2, 2 ** 28  # include/memvul_retrieve.h
-KEY_MATCH_W = "_projector.weight"
 
 _f32p, _vp = C.POINTER(C.c_float), C.c_void_p
 _SIGNATURES = {
@@ -98,59 +95,19 @@ def format_reports(labels, urls, p: np.ndarray, rows: np.ndarray, first: int = 0
 # ---- the command line ------------------------------------------------------------------------------------------------------------------------------------------
 
 def main(argv=None, engine_factory=None, index_factory=None) -> int:
-    from . import audit as _audit
-    from . import binding
+    from . import kept_sweep as front
 
-    ap = argparse.ArgumentParser(prog="python -m memvul_amd.retrieve", description="For every anchor of the golden file: the k issue reports it attracts most.")
-    ap.add_argument("--archive", required=True, help="model.tar.gz or its extracted directory")
-    ap.add_argument("--golden", required=True, help="the golden anchor file ({cwe_id: description})")
-    ap.add_argument("--input", required=True, help="the issue reports (a test_ / validation_ file of the reader)")
+    ap = front.parser("python -m memvul_amd.retrieve", "For every anchor of the golden file: the k issue reports it attracts most.")
     ap.add_argument("--k", type=int, default=20, help="reports per anchor (1 .. 64)")
-    ap.add_argument("--anchors", default=None, metavar="LABEL[,LABEL...]", help="only these anchors (default: all of the golden file)")
-    ap.add_argument("--out", default=None, help="write the JSON lines here instead of standard output")
-    ap.add_argument("--batch", type=int, default=512)
-    ap.add_argument("--device", type=int, default=0)
+    front.add_anchors(ap)
+    front.add_output(ap, "JSON lines")
     args = ap.parse_args(argv)
     if not 1 <= args.k <= MAX_K:
         ap.error(f"--k {args.k}: 1 .. {MAX_K}")
-    sd, config, same_idx = _audit._read_archive(args.archive)
-    if config is None:
-        ap.error("--archive must be an archive (config.json, vocabulary/, weights): the readers come from its config")
-    from . import archive as _archive
-
-    reader = _archive._build_reader(config.get("validation_dataset_reader")) or _archive._build_reader(config.get("dataset_reader"))
-    labels = list(reader.read_dataset(args.golden).keys())
-    ids, lens, aids, alens = _audit._read_inputs(config, args.golden, args.input)
-    urls = reader.read_arrays(args.input)["urls"]
-    wanted = list(range(len(labels)))
-    if args.anchors is not None:
-        names = [a for a in args.anchors.split(",") if a]
-        missing = [a for a in names if a not in labels]
-        if missing:
-            ap.error("--anchors: not in the golden file: " + ",".join(missing))
-        wanted = [labels.index(a) for a in names]
-    opts = dict(max_tokens=128 * 512, max_batch=max(512, args.batch), max_anchors=max(1024, len(alens)), same_idx=same_idx)
-    opts.update(_audit._engine_dims(sd))
-    eng = (engine_factory or binding.Engine)(args.device, **opts)
-    try:
-        eng.load_state_dict(sd)
-        for i in range(len(alens)):  # (every anchor at its own length, the bank in the file's order)
-            eng.anchor_append(np.ascontiguousarray(aids[i:i + 1, :max(int(alens[i]), 1)]), np.ascontiguousarray(alens[i:i + 1]))
-        eng.bucketed_sweep(ids[:, :max(int(lens.max()), 1)], lens, args.batch, keep=True)
-        index = ReportIndex.from_sweep(eng, np.asarray(sd[KEY_MATCH_W], np.float32), same_idx, index_factory=index_factory)
-        try:
-            v = np.ascontiguousarray(eng.anchor_get()[wanted], dtype=np.float32)
-            p, rows = index.query(v, min(args.k, MAX_K))
-        finally:
-            index.close()
-    finally:
-        eng.close()
-    lines = [json.dumps(e) for e in format_reports([labels[i] for i in wanted], urls, p, rows)]
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("".join(ln + "\n" for ln in lines))
-    else:
-        print("\n".join(lines))
+    corpus = front.read_corpus(ap, args)
+    with front.filled_index(corpus, args, ReportIndex, engine_factory, index_factory) as (index, v):
+        p, rows = index.query(v, min(args.k, MAX_K))
+    front.write_json(args.out, format_reports(corpus.wanted_labels, corpus.urls, p, rows))
     return 0
 
 

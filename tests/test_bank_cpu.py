@@ -11,12 +11,12 @@ import subprocess
 import numpy as np
 import pytest
 
-from memvul_amd import bank, binding, build, claims, model_memory, retrieve
+from memvul_amd import bank, binding, build, claims, retrieve
 
 import bank_kit as kit
+import kept_index_kit as kk
 import plumbing_util as pu
-import test_report_index_cpu as ri
-from test_claims_cpu import _CountingEngine, _NumpyClaims, standin_model  # noqa: F401  (the stand-in model with a counted download)
+from kept_index_kit import _CountingEngine, _KeepingEngine, _NumpyBank, _NumpyClaims, _NumpyIndex, _inputs, standin_model  # noqa: F401  (standin_model is a fixture)
 from test_f32_form_cpu import _llvm_tool
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -78,7 +78,7 @@ def test_build_all_leaves_five_fresh_libraries_and_returns_two_paths(libs):
 
 
 def test_the_kernels_are_the_recorded_ones(libs):
-    ri.check_kernels_are_the_recorded_ones(build.LIB_PATH_BANK, "bank")
+    kk.check_kernels_are_the_recorded_ones(build.LIB_PATH_BANK, "bank")
 
 
 def test_the_module_prints_the_new_path_too():
@@ -87,9 +87,9 @@ def test_the_module_prints_the_new_path_too():
 
 
 def test_the_other_libraries_do_not_know_the_new_files(libs, monkeypatch):
-    new, _ = ri.own_and_shared("bank")
+    new, _ = kk.own_and_shared("bank")
     assert build.SIDE_LIBS["bank"] == (build.BANK_LIB_NAME, build.BANK_SOURCES, build.BANK_HEADERS)
-    ri.check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
+    kk.check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
     assert sorted(os.path.basename(p) for p in new) == ["bank.hip", "bank_cover.h", "memvul_bank.h"]
     opened = []
     real_open = open
@@ -275,71 +275,34 @@ def test_audit_of_by_hand():
 
 # ---- validation before any library call --------------------------------------------------------------------------------------------------------------------------------
 
-class _StubLib:
-    """Records every call; holds `n` rows."""
+class _StubLib(kk.StubLib):
+    PREFIX = "mvb_"
+    rounds = 0
 
-    def __init__(self):
-        self.log, self.n, self.th, self.rounds = [], 0, None, 0
-
-    def mvb_create(self, device, P, w, same_idx, out):
-        self.log.append(("create", device, P, same_idx))
-        C.cast(out, C.POINTER(C.c_void_p))[0] = 1
-        return 0
-
-    def mvb_destroy(self, h):
-        self.log.append(("destroy",))
-
-    def mvb_last_error(self, h):
-        return b"stub"
-
-    def mvb_add(self, h, e, n):
-        self.log.append(("add", n))
-        self.n += n
-        return 0
-
-    def mvb_reset(self, h):
-        self.log.append(("reset",))
-        self.n = 0
-        return 0
-
-    def mvb_count(self, h):
-        return self.n
-
-    def mvb_set_classes(self, h, c, first, n):
-        self.log.append(("classes", first, n))
-        return 0
-
-    def mvb_mark(self, h, v, Q, th, first, count):
-        self.th = np.ctypeslib.as_array(C.cast(th, C.POINTER(C.c_float)), (Q,)).copy()
+    def mark(self, h, v, Q, th, first, count):
+        self._thresholds(th, Q)
         self.log.append(("mark", Q, first, count))
         return 0
 
-    def mvb_totals(self, h, out):
+    def totals(self, h, out):
         self.log.append(("totals",))
         return 0
 
-    def mvb_multiplicity(self, h, hist, sole, mult, sole_of):
+    def multiplicity(self, h, hist, sole, mult, sole_of):
         self.log.append(("multiplicity", mult is not None, sole_of is not None))
         return 0
 
-    def mvb_overlap(self, h, out):
+    def overlap(self, h, out):
         self.log.append(("overlap",))
         return 0
 
-    def mvb_greedy(self, h, w_pos, w_neg, fixed, max_rounds, rounds, order, gained):
+    def greedy(self, h, w_pos, w_neg, fixed, max_rounds, rounds, order, gained):
         self.log.append(("greedy", w_pos, w_neg, fixed is not None, max_rounds))
         C.cast(rounds, C.POINTER(C.c_int))[0] = self.rounds
         return 0
 
-    def mvb_kernel_ms(self, h, ms):
-        return -1
 
-    def mvb_test_plan(self, h, a, b, c):
-        self.log.append(("plan", a, b, c))
-        return 0
-
-
-W512 = np.zeros((2, 3 * 512), np.float32)
+W512 = kk.W512
 
 
 def test_bad_arguments_raise_before_any_call():
@@ -411,46 +374,6 @@ def test_bad_arguments_raise_before_any_call():
 
 # ---- ModelMemory.anchor_bank_audit and the command line on the stand-in -------------------------------------------------------------------------------------------------
 
-class _NumpyBank:
-    """index_factory of the CPU tests: the oracle's P(same) met with the definitions of bank_kit."""
-    made = []
-
-    def __init__(self, device, P, w, same_idx):
-        self.w, self.same_idx, self.u, self.cls, self.closed, self.B, self.marks = np.asarray(w), same_idx, np.zeros((0, P), np.float32), np.zeros(0, np.uint8), False, None, 0
-        _NumpyBank.made.append(self)
-
-    def add(self, e):
-        self.u = np.concatenate([self.u, e])
-        self.cls = np.concatenate([self.cls, np.zeros(len(e), np.uint8)])
-
-    def set_classes(self, cls, first=0):
-        assert cls.dtype == np.uint8
-        self.cls[first:first + len(cls)] = cls
-
-    def mark(self, v, thres, first=0, count=None):
-        from oracle import memvul_oracle as orc
-
-        _, p, _, _ = orc.match(self.u, np.asarray(v, np.float32), self.w, self.same_idx)
-        self.B = kit.marking(p[:, :, self.same_idx].astype(np.float32), claims.up32(np.broadcast_to(thres, (len(v),))))
-        self.marks += 1
-
-    def totals(self):
-        return kit.totals(self.B, self.cls)
-
-    def multiplicity(self, per_row=False):
-        out = kit.multiplicity(self.B, self.cls)
-        return out if per_row else out[:2]
-
-    def overlap(self):
-        return kit.overlap(self.B, self.cls)
-
-    def greedy(self, w_pos=1, w_neg=1, fixed=None, max_rounds=None):
-        return kit.greedy(self.B, self.cls, w_pos, w_neg, fixed, max_rounds)[:2]
-
-    def close(self):
-        self.closed = True
-
-
 def _want_doc(ps, same, thres, labels, w_pos=1, w_neg=1):
     B = ps.astype(np.float64) >= np.asarray(thres, np.float64)[None, :]  # the reference's comparison: float(p32) >= t
     pred = B.any(1)
@@ -460,10 +383,6 @@ def _want_doc(ps, same, thres, labels, w_pos=1, w_neg=1):
 
 def test_anchor_bank_audit_on_the_standin(standin_model):
     model, arrays, fx = standin_model
-    _NumpyBank.made = []
-    with pytest.raises(RuntimeError, match="anchor_bank_audit\\(\\): no kept sweep of these rows — call sweep_arrays\\(arrays, first, last, keep=True\\) first"):
-        model.anchor_bank_audit(arrays, 0.5, index_factory=_NumpyBank)
-    assert _NumpyBank.made == []
     _, _, ps = model.sweep_arrays(arrays, batch_size=8, with_probs=True, keep=True)
     ps = ps.astype(np.float32)
     same = np.asarray(arrays["same"], bool)
@@ -495,8 +414,8 @@ def test_anchor_bank_audit_on_the_standin(standin_model):
     # one download serves the three indexes
     assert _CountingEngine.downloads == 1
     model.anchor_claims(arrays, 0.5, index_factory=_NumpyClaims)
-    model.anchor_reports(arrays, 3, index_factory=ri._NumpyIndex)
-    assert _CountingEngine.downloads == 1 and model._kept_embed is None
+    model.anchor_reports(arrays, 3, index_factory=_NumpyIndex)
+    assert _CountingEngine.downloads == 1 and model._kept.embed is None
     # candidates: the bank is fixed, the candidates are ranked by what they add
     cand = np.ascontiguousarray(model.engine.anchor_get()[[2, 0]] * np.float32(0.5))
     lo = float(np.percentile(ps, 40))
@@ -516,11 +435,9 @@ def test_anchor_bank_audit_on_the_standin(standin_model):
     for bad in (dict(thres=[0.5, 0.5]), dict(thres=float("nan")), dict(candidates=cand, candidate_labels=["one"])):
         with pytest.raises(ValueError):
             model.anchor_bank_audit(arrays, index_factory=_NumpyBank, **{"thres": thres, **bad})
-    with pytest.raises(RuntimeError, match="keep=True"):
-        model.anchor_bank_audit(arrays, thres, 0, 10, index_factory=_NumpyBank)  # other rows than the kept sweep's
     # a new sweep drops the index with the other two
     model.sweep_arrays(arrays, 4, 20, batch_size=8, with_probs=True, keep=True)
-    assert ix.closed and model._bank_index is None
+    assert ix.closed and model._kept.indexes["bank"] is None
     doc3 = model.anchor_bank_audit(arrays, thres, 4, 20, index_factory=_NumpyBank)
     assert len(_NumpyBank.made) == 2 and _NumpyBank.made[1].u.shape == (16, 512) and np.array_equal(_NumpyBank.made[1].cls, same[4:20].astype(np.uint8))
     assert doc3["rows"] == 16 and doc3["positives"] == int(same[4:20].sum())
@@ -529,23 +446,23 @@ def test_anchor_bank_audit_on_the_standin(standin_model):
 def test_the_command_line_writes_one_json_document(capsys, tmp_path):
     root, arch, golden, test_path, w, dims = pu.make_fixture(n_irs=12, n_anchors=4, layers=2)
     try:
-        ri._KeepingEngine.created, _NumpyBank.made = [], []
+        _KeepingEngine.created, _NumpyBank.made = [], []
         out = tmp_path / "bank.json"
         std = ["--archive", arch, "--golden", golden, "--input", test_path]
-        rc = bank.main(std + ["--thres", "0.0", "--out", str(out)], engine_factory=ri._KeepingEngine, index_factory=_NumpyBank)
+        rc = bank.main(std + ["--thres", "0.0", "--out", str(out)], engine_factory=_KeepingEngine, index_factory=_NumpyBank)
         doc = json.load(open(out))
         assert rc == 0 and capsys.readouterr().out.strip() == "" and _NumpyBank.made[0].closed
         assert doc["rows"] == 12 and doc["union"]["FN"] == 0 and doc["union"]["TN"] == 0 and [a["anchor"] for a in doc["anchors"]] == [f"CWE-{100 + i}" for i in range(4)]
         assert all(sum(a["claimed"]) == 12 and a["sole"] == [0, 0] for a in doc["anchors"]) and all(o["jaccard"] == 1.0 for o in doc["overlaps"]) and len(doc["overlaps"]) == 6
-        eng = ri._KeepingEngine.created[0]
-        ids, lens, urls = ri._inputs(arch, golden, test_path)
+        eng = _KeepingEngine.created[0]
+        ids, lens, _ = _inputs(arch, golden, test_path)
         ps = eng.forward(ids, lens)["probs"][:, :, 0].astype(np.float32)
         same = _NumpyBank.made[0].cls.astype(bool)
         per = {"CWE-101": float(np.percentile(ps[:, 1], 60)), "CWE-103": float(np.percentile(ps[:, 3], 30))}
         tf = tmp_path / "thres.json"
         tf.write_text(json.dumps(per))
         mid = float(np.median(ps))
-        rc = bank.main(std + ["--thres", repr(mid), "--thres-file", str(tf), "--top", "2", "--w-pos", "3", "--max-rounds", "2"], engine_factory=ri._KeepingEngine,
+        rc = bank.main(std + ["--thres", repr(mid), "--thres-file", str(tf), "--top", "2", "--w-pos", "3", "--max-rounds", "2"], engine_factory=_KeepingEngine,
                        index_factory=_NumpyBank)
         doc = json.loads(capsys.readouterr().out)
         thres = [mid, per["CWE-101"], mid, per["CWE-103"]]
@@ -556,7 +473,7 @@ def test_the_command_line_writes_one_json_document(capsys, tmp_path):
         tf.write_text(json.dumps({"CWE-999": 0.5}))
         for bad in (["--thres", "nan"], ["--w-pos", "-1"], ["--w-neg", str(2 ** 20 + 1)], ["--top", "-1"], ["--thres-file", str(tf)]):
             with pytest.raises(SystemExit):
-                bank.main(std + bad, engine_factory=ri._KeepingEngine, index_factory=_NumpyBank)
+                bank.main(std + bad, engine_factory=_KeepingEngine, index_factory=_NumpyBank)
     finally:
         shutil.rmtree(root, ignore_errors=True)
 

@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import bank_kit as kit  # noqa: E402
 import claims_kit  # noqa: E402
-from test_report_index_gpu import L2, WK, WK768, _Vocab, _engine_matrix  # noqa: E402
+from kept_index_kit import L2, WK, WK768, _engine_matrix, bare_model  # noqa: E402
 
 N_512, Q_512, N_768, Q_768 = 4099, 37, 1000, 124
 ABOVE_ONE = np.nextafter(np.float32(1), np.float32(2))
@@ -409,8 +409,6 @@ def test_the_held_marking_and_the_refusals(gu, c512):
 # ---- 6: end to end -------------------------------------------------------------------------------------------------------------------------------------------------------
 
 def test_end_to_end_from_a_kept_sweep(gu, c512):
-    from memvul_amd.model_memory import ModelMemory
-
     eng = c512["eng"]
     dims, _ = gu.weights_for(L2, WK)
     n = 200
@@ -420,9 +418,7 @@ def test_end_to_end_from_a_kept_sweep(gu, c512):
         warnings.simplefilter("ignore")
         eng.anchor_reset()
         eng.anchor_append(*synth.make_ids(5, 64, dims.vocab_size, seed=synth.SEED + 78, ragged=True, min_len=16))
-        m = ModelMemory.__new__(ModelMemory)
-        m.__dict__.update(_engine=eng, vocab=_Vocab(), _label_namespace="labels", _same_idx=0, _matcher_weight=c512["Wm"], _golden_labels=[f"CWE-{i}" for i in range(5)],
-                          _counts=lambda best, lab: None, _siamese_metric=type("M", (), {"add_arrays": lambda self, a, b: None})())
+        m = bare_model(eng, c512["Wm"], 5)
         arrays = {"type": "test", "ids": ids, "lens": lens, "same": same, "urls": [f"https://example.invalid/issues/{i}" for i in range(n)]}
         m.sweep_arrays(arrays, batch_size=64, with_probs=True, keep=True)
         ps = m.rematch_arrays(arrays, with_probs=True)[2]
@@ -439,10 +435,10 @@ def test_end_to_end_from_a_kept_sweep(gu, c512):
             assert a["sole"] == [int((only & ~same).sum()), int((only & same).sum())]
         order, gained, _ = kit.greedy(B, same.astype(np.uint8), 2, 1)
         assert [x["index"] for x in doc["greedy"]] == order.tolist() and [[x["new_pos"], x["new_neg"]] for x in doc["greedy"]] == gained.tolist()
-        index = m._bank_index
+        index = m._kept.indexes["bank"]
         cand = np.ascontiguousarray(eng.anchor_get()[[1, 0, 2]] * np.float32(0.75))  # (stand-ins for the embeddings of fresh descriptions)
         doc2 = m.anchor_bank_audit(arrays, thres, candidates=cand, candidate_thres=thres[0], w_pos=2, w_neg=1)
-        assert m._bank_index is index and doc2["union"] == doc["union"] and len(doc2["candidates"]) == 3
+        assert m._kept.indexes["bank"] is index and doc2["union"] == doc["union"] and len(doc2["candidates"]) == 3
         assert all(0 <= x["index"] < 3 and x["anchor"] == f"candidate {x['index']}" for x in doc2["greedy"])
-        m._drop_report_index()
-        assert m._bank_index is None
+        m._kept.drop()
+        assert m._kept.indexes["bank"] is None

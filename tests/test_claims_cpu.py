@@ -12,11 +12,12 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-from memvul_amd import binding, build, claims, model_memory, retrieve
+from memvul_amd import binding, build, claims, retrieve
 
 import claims_kit as kit
+import kept_index_kit as kk
 import plumbing_util as pu
-import test_report_index_cpu as ri
+from kept_index_kit import _CountingEngine, _KeepingEngine, _NumpyClaims, _NumpyIndex, _inputs, standin_model  # noqa: F401  (standin_model is a fixture)
 from test_f32_form_cpu import _llvm_tool
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,13 +70,13 @@ def test_build_all_still_returns_two_paths_and_leaves_the_new_library_fresh(libs
 
 
 def test_the_kernels_are_the_recorded_ones(libs):
-    ri.check_kernels_are_the_recorded_ones(build.LIB_PATH_CLAIMS, "claims")
+    kk.check_kernels_are_the_recorded_ones(build.LIB_PATH_CLAIMS, "claims")
 
 
 def test_the_other_libraries_do_not_know_the_new_files(libs, monkeypatch):
-    new, _ = ri.own_and_shared("claims")
+    new, _ = kk.own_and_shared("claims")
     assert build.SIDE_LIBS["claims"] == (build.CLAIMS_LIB_NAME, build.CLAIMS_SOURCES, build.CLAIMS_HEADERS)
-    ri.check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
+    kk.check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
     assert sorted(os.path.basename(p) for p in new) == ["claim_sweep.h", "claims.hip", "memvul_claims.h"]
     opened = []
     real_open = open
@@ -238,66 +239,28 @@ def test_the_reference_grid():
 
 # ---- validation before any library call --------------------------------------------------------------------------------------------------------------------------------
 
-class _StubLib:
-    """Records every call; holds `n` rows."""
+class _StubLib(kk.StubLib):
+    PREFIX = "mvc_"
 
-    def __init__(self):
-        self.log, self.n, self.th = [], 0, None
-
-    def mvc_create(self, device, P, w, same_idx, out):
-        self.log.append(("create", device, P, same_idx))
-        C.cast(out, C.POINTER(C.c_void_p))[0] = 1
-        return 0
-
-    def mvc_destroy(self, h):
-        self.log.append(("destroy",))
-
-    def mvc_last_error(self, h):
-        return b"stub"
-
-    def mvc_add(self, h, e, n):
-        self.log.append(("add", n))
-        self.n += n
-        return 0
-
-    def mvc_reset(self, h):
-        self.log.append(("reset",))
-        self.n = 0
-        return 0
-
-    def mvc_count(self, h):
-        return self.n
-
-    def mvc_set_classes(self, h, c, first, n):
-        self.log.append(("classes", first, n))
-        return 0
-
-    def mvc_counts(self, h, v, Q, th, T, first, count, out):
-        self.th = np.ctypeslib.as_array(C.cast(th, C.POINTER(C.c_float)), (T,)).copy()
+    def counts(self, h, v, Q, th, T, first, count, out):
+        self._thresholds(th, T)
         self.log.append(("counts", Q, T, first, count))
         return 0
 
-    def mvc_select(self, h, v, Q, th, first, count, off):
-        self.th = np.ctypeslib.as_array(C.cast(th, C.POINTER(C.c_float)), (Q,)).copy()
+    def select(self, h, v, Q, th, first, count, off):
+        self._thresholds(th, Q)
         self.log.append(("select", Q, first, count))
         o = C.cast(off, C.POINTER(C.c_int64))
         for i in range(Q + 1):
             o[i] = 0
         return 0
 
-    def mvc_fetch(self, h, r, p):
+    def fetch(self, h, r, p):
         self.log.append(("fetch",))
         return 0
 
-    def mvc_kernel_ms(self, h, ms):
-        return -1
 
-    def mvc_test_plan(self, h, a, b):
-        self.log.append(("plan", a, b))
-        return 0
-
-
-W512 = np.zeros((2, 3 * 512), np.float32)
+W512 = kk.W512
 
 
 def test_bad_arguments_raise_before_any_call():
@@ -371,68 +334,6 @@ def test_bad_arguments_raise_before_any_call():
 
 # ---- ModelMemory.anchor_claims and the command line on the stand-in -----------------------------------------------------------------------------------------------------
 
-class _CountingEngine(ri._KeepingEngine):
-    """The keeping stand-in, counting the downloads of the kept embeddings."""
-    downloads = 0
-
-    def sweep_embeddings(self, first=0, count=None, chunk=65536):
-        out = super().sweep_embeddings(first, count, chunk)
-        _CountingEngine.downloads += 1
-        return out
-
-
-class _NumpyClaims:
-    """index_factory of the CPU tests: the oracle's P(same) met with the rule of claims_kit."""
-    made = []
-
-    def __init__(self, device, P, w, same_idx):
-        self.w, self.same_idx, self.u, self.cls, self.closed = np.asarray(w), same_idx, np.zeros((0, P), np.float32), np.zeros(0, np.uint8), False
-        _NumpyClaims.made.append(self)
-
-    def add(self, e):
-        self.u = np.concatenate([self.u, e])
-        self.cls = np.concatenate([self.cls, np.zeros(len(e), np.uint8)])
-
-    def set_classes(self, cls, first=0):
-        assert cls.dtype == np.uint8
-        self.cls[first:first + len(cls)] = cls
-
-    def _p(self, v):
-        from oracle import memvul_oracle as orc
-
-        _, p, _, _ = orc.match(self.u, np.asarray(v, np.float32), self.w, self.same_idx)
-        return p[:, :, self.same_idx].astype(np.float32)
-
-    def counts(self, v, thresholds, first=0, count=None):
-        return kit.reference_counts(self._p(v), self.cls, claims.up32(thresholds))
-
-    def select(self, v, thres, first=0, count=None, order="prob"):
-        off, rows, p = kit.reference_select(self._p(v), claims.up32(np.broadcast_to(thres, (len(v),))))
-        return (off,) + (tuple(kit.by_prob(off, rows, p)) if order == "prob" else (rows, p))
-
-    def close(self):
-        self.closed = True
-
-
-@pytest.fixture()
-def standin_model(monkeypatch):
-    from memvul_amd.archive import load_archive
-
-    fx = pu.make_fixture(n_irs=23, n_anchors=4, layers=2)
-    root, arch, golden, test_path, w, dims = fx
-    monkeypatch.setattr(model_memory, "Engine", _CountingEngine)
-    archive = load_archive(arch, cuda_device=0, overrides=pu.TEST_CONFIG, engine_options=dict(max_tokens=16 * 256, max_batch=16, max_anchors=16))
-    model = archive.model
-    model.eval()
-    model._golden_instances_embeddings = None
-    model._golden_instances_labels = None
-    model.forward_on_instances(list(archive.validation_dataset_reader.read(golden)))
-    arrays = archive.dataset_reader.read_arrays(test_path)
-    _NumpyClaims.made, ri._NumpyIndex.made, _CountingEngine.downloads = [], [], 0
-    yield model, arrays, fx
-    shutil.rmtree(root, ignore_errors=True)
-
-
 def _want_entries(ps, same, thres, urls, first=0):
     out = []
     for g in range(ps.shape[1]):
@@ -444,12 +345,6 @@ def _want_entries(ps, same, thres, urls, first=0):
 
 def test_anchor_claims_on_the_standin(standin_model):
     model, arrays, fx = standin_model
-    with pytest.raises(RuntimeError, match="keep=True"):
-        model.anchor_claims(arrays, 0.5, index_factory=_NumpyClaims)
-    model.sweep_arrays(arrays, batch_size=8, with_probs=True)  # not a keeping sweep
-    with pytest.raises(RuntimeError, match="anchor_claims\\(\\): no kept sweep of these rows — call sweep_arrays\\(arrays, first, last, keep=True\\) first"):
-        model.anchor_claims(arrays, 0.5, index_factory=_NumpyClaims)
-    assert _NumpyClaims.made == []
     _, _, ps = model.sweep_arrays(arrays, batch_size=8, with_probs=True, keep=True)
     ps = ps.astype(np.float32)
     same = np.asarray(arrays["same"], bool)
@@ -466,10 +361,10 @@ def test_anchor_claims_on_the_standin(standin_model):
     json.dumps(out)
     ix = _NumpyClaims.made[0]
     assert len(_NumpyClaims.made) == 1 and np.array_equal(ix.w, fx[4]["_projector.weight"]) and ix.u.shape == (23, 512) and np.array_equal(ix.cls, same.astype(np.uint8))
-    # both indexes from one download; the host copy is let go once both are filled
-    assert _CountingEngine.downloads == 1 and model._kept_embed is not None
-    model.anchor_reports(arrays, 5, index_factory=ri._NumpyIndex)
-    assert _CountingEngine.downloads == 1 and len(ri._NumpyIndex.made) == 1 and ri._NumpyIndex.made[0].u.shape == (23, 512) and model._kept_embed is None
+    # the claim index and the report index from one download; the host copy is let go once those two are filled
+    assert _CountingEngine.downloads == 1 and model._kept.embed is not None
+    model.anchor_reports(arrays, 5, index_factory=_NumpyIndex)
+    assert _CountingEngine.downloads == 1 and len(_NumpyIndex.made) == 1 and _NumpyIndex.made[0].u.shape == (23, 512) and model._kept.embed is None
     # one threshold per vector, given vectors and labels, a grid
     v = model.engine.anchor_get()[[2, 0]]
     th2 = [float(np.percentile(ps[:, 2], 80)), float(np.percentile(ps[:, 0], 20))]
@@ -488,16 +383,14 @@ def test_anchor_claims_on_the_standin(standin_model):
         assert e["best_thres"] in grid
     assert [e["anchor"] for e in model.anchor_claims(arrays, 0.5, vectors=v, index_factory=_NumpyClaims)] == ["0", "1"]
     assert len(model.anchor_claims(arrays, grid="reference", index_factory=_NumpyClaims)[0]["grid"]) == 40
-    for bad in (dict(vectors=v, labels=["one"]), dict(vectors=v, thres=[0.5, 0.5, 0.5]), dict(grid="nonsense"), dict(grid=[0.5] * 65), dict(thres=float("nan"))):
+    for bad in (dict(vectors=v, thres=[0.5, 0.5, 0.5]), dict(grid="nonsense"), dict(grid=[0.5] * 65), dict(thres=float("nan"))):
         with pytest.raises(ValueError):
             model.anchor_claims(arrays, index_factory=_NumpyClaims, **bad)
-    with pytest.raises(RuntimeError, match="keep=True"):
-        model.anchor_claims(arrays, 0.5, 0, 10, index_factory=_NumpyClaims)  # other rows than the kept sweep's
-    # a new sweep drops both indexes: of rows 4 .. 20 now, numbered as in `arrays`, classes of those rows
+    # a new sweep drops every index: of rows 4 .. 20 now, numbered as in `arrays`, classes of those rows
     first_index = _NumpyClaims.made[0]
     _, _, ps = model.sweep_arrays(arrays, 4, 20, batch_size=8, with_probs=True, keep=True)
     ps = ps.astype(np.float32)
-    assert first_index.closed and ri._NumpyIndex.made[0].closed and model._kept_embed is None
+    assert first_index.closed and _NumpyIndex.made[0].closed and model._kept.embed is None
     out3 = model.anchor_claims(arrays, thres, 4, 20, index_factory=_NumpyClaims)
     assert len(_NumpyClaims.made) == 2 and _NumpyClaims.made[1].u.shape == (16, 512) and np.array_equal(_NumpyClaims.made[1].cls, same[4:20].astype(np.uint8))
     want3 = _want_entries(ps, same[4:20], [thres] * 4, arrays["urls"], first=4)
@@ -541,21 +434,18 @@ def test_best_thres_by_hand():
 def test_the_command_line_writes_one_json_line_per_anchor(capsys, tmp_path):
     root, arch, golden, test_path, w, dims = pu.make_fixture(n_irs=12, n_anchors=4, layers=2)
     try:
-        ri._KeepingEngine.created, _NumpyClaims.made = [], []
+        _KeepingEngine.created, _NumpyClaims.made = [], []
         out = tmp_path / "claims.jsonl"
         std = ["--archive", arch, "--golden", golden, "--input", test_path]
-        eng0 = ri._KeepingEngine  # the first run tells what P(same) is; the threshold is taken from it
+        eng0 = _KeepingEngine  # the first run tells what P(same) is; the threshold is taken from it
         rc = claims.main(std + ["--thres", "0.0", "--out", str(out)], engine_factory=eng0, index_factory=_NumpyClaims)
         lines = [json.loads(ln) for ln in open(out)]
         assert rc == 0 and [e["anchor"] for e in lines] == [f"CWE-{100 + i}" for i in range(4)] and all(e["claimed"] == 12 == len(e["reports"]) for e in lines)
         assert capsys.readouterr().out.strip() == "" and _NumpyClaims.made[0].closed
-        eng = ri._KeepingEngine.created[0]
-        ids, lens, urls = ri._inputs(arch, golden, test_path)
+        eng = _KeepingEngine.created[0]
+        ids, lens, arrs = _inputs(arch, golden, test_path)
         ps = eng.forward(ids, lens)["probs"][:, :, 0].astype(np.float32)
-        from memvul_amd import archive, audit
-
-        _, config, _ = audit._read_archive(arch)
-        same = np.asarray((archive._build_reader(config.get("validation_dataset_reader")) or archive._build_reader(config.get("dataset_reader"))).read_arrays(test_path)["same"], bool)
+        urls, same = arrs["urls"], np.asarray(arrs["same"], bool)
         assert np.array_equal(_NumpyClaims.made[0].cls, same.astype(np.uint8))
         thres = float(np.median(ps))
         rc = claims.main(std + ["--thres", repr(thres), "--grid", "0.2:0.85:0.05", "--anchors", "CWE-102,CWE-100"], engine_factory=eng0, index_factory=_NumpyClaims)

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import claims_kit as kit  # noqa: E402
-from test_report_index_gpu import L2, WK, WK768, _Vocab, _engine_matrix, _same_bytes  # noqa: E402
+from kept_index_kit import L2, WK, WK768, _engine_matrix, _same_bytes, bare_model  # noqa: E402
 
 N_PLAN, N_MAX, Q_MAX, Q_768, Q_PLAN = 4099, 1000, 33, 124, 7
 
@@ -510,8 +510,6 @@ def _best_by_the_references_rule(col, same, grid64):
 
 
 def test_end_to_end_from_a_kept_sweep(gu, c512):
-    from memvul_amd.model_memory import ModelMemory
-
     eng = c512["eng"]
     dims, _ = gu.weights_for(L2, WK)
     n = 200
@@ -522,16 +520,14 @@ def test_end_to_end_from_a_kept_sweep(gu, c512):
         warnings.simplefilter("ignore")
         eng.anchor_reset()
         eng.anchor_append(*synth.make_ids(5, 64, dims.vocab_size, seed=synth.SEED + 78, ragged=True, min_len=16))
-        m = ModelMemory.__new__(ModelMemory)
-        m.__dict__.update(_engine=eng, vocab=_Vocab(), _label_namespace="labels", _same_idx=0, _matcher_weight=c512["Wm"], _golden_labels=[f"CWE-{i}" for i in range(5)],
-                          _counts=lambda best, lab: None, _siamese_metric=type("M", (), {"add_arrays": lambda self, a, b: None})())
+        m = bare_model(eng, c512["Wm"], 5)
         arrays = {"type": "test", "ids": ids, "lens": lens, "same": same, "urls": [f"https://example.invalid/issues/{i}" for i in range(n)]}
         m.sweep_arrays(arrays, batch_size=64, with_probs=True, keep=True)
         for more in (0, 2):
             if more:  # the bank is edited, the corpus is not encoded again and the index is not refilled
                 eng.anchor_append(*synth.make_ids(more, 64, dims.vocab_size, seed=synth.SEED + 79, ragged=True, min_len=16))
                 m._golden_labels = [f"CWE-{i}" for i in range(5 + more)]
-            index = getattr(m, "_claim_index", None)
+            index = m._kept.indexes["claims"]
             ps = m.rematch_arrays(arrays, with_probs=True)[2]
             assert ps.dtype == np.float32 and ps.shape == (n, 5 + more)
             mid = float(np.median(ps))
@@ -541,7 +537,7 @@ def test_end_to_end_from_a_kept_sweep(gu, c512):
             gu.record("claims_end_to_end", anchors=5 + more, share_at_half=float((ps >= 0.5).mean()), share_at_median=share)
             for thres, grid in ((0.5, None), (mid, "reference"), ([mid] * (4 + more) + [0.0], None)):
                 out = m.anchor_claims(arrays, thres, grid=grid)
-                assert more == 0 or m._claim_index is index
+                assert more == 0 or m._kept.indexes["claims"] is index
                 assert [e["anchor"] for e in out] == m._golden_labels
                 for g, e in enumerate(out):
                     t = thres[g] if isinstance(thres, list) else thres
@@ -556,4 +552,4 @@ def test_end_to_end_from_a_kept_sweep(gu, c512):
                             pred = ps[:, g].astype(np.float64) >= x["thres"]
                             assert (x["claimed"], x["positives"]) == (int(pred.sum()), int((pred & same).sum()))
                         assert e["best_thres"] == _best_by_the_references_rule(ps[:, g], same, grid64)
-        m._drop_report_index()
+        m._kept.drop()

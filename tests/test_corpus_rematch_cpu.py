@@ -298,12 +298,14 @@ class _OldEngine:
 
 
 def _model(engine):
+    from memvul_amd.kept_sweep import KeptSweepState
     from memvul_amd.model_memory import ModelMemory
 
     m = ModelMemory.__new__(ModelMemory)
     counts = []
     d = m.__dict__
-    d.update(_engine=engine, vocab=_Vocab(), _label_namespace="labels", _same_idx=0, _siamese_metric=_Metric(), _counts=lambda best, lab: counts.append((best.copy(), lab.copy())))
+    d.update(_engine=engine, vocab=_Vocab(), _label_namespace="labels", _same_idx=0, _siamese_metric=_Metric(), _counts=lambda best, lab: counts.append((best.copy(), lab.copy())),
+             _kept=KeptSweepState())
     return m, counts
 
 

@@ -10,10 +10,12 @@ import subprocess
 import numpy as np
 import pytest
 
-from memvul_amd import build, model_memory, retrieve
+from memvul_amd import build, retrieve
 
+import kept_index_kit as kk
 import plumbing_util as pu
 import report_index_kit as kit
+from kept_index_kit import _KeepingEngine, _NumpyIndex, _inputs, standin_model  # noqa: F401  (standin_model is a fixture)
 import test_corpus_rematch_cpu as rm
 from test_f32_form_cpu import _llvm_tool
 
@@ -51,71 +53,6 @@ def test_no_cpp_exception_can_cross_the_boundary():
     assert src.count("catch (...) { return on_exception(") == len(heads)
 
 
-# ---- the two headers the three kept-corpus libraries share (csrc/kept_index.h, csrc/kept_terms.h) ------------------------------------------------------------------
-
-KEPT_SHARED = ("kept_index.h", "kept_terms.h")
-KEPT_OWN = {"retrieve": ("retrieve.hip", "report_topk.h"), "claims": ("claims.hip", "claim_sweep.h"), "bank": ("bank.hip", "bank_cover.h")}  # (source, kernel header)
-
-
-def opened_by_fingerprint(monkeypatch, sources=None, headers=None) -> set:
-    """The files build.source_fingerprint opens for a library (default: libmemvul_hip.so, either build)."""
-    opened = []
-    real_open = open
-
-    def spy(path, *a, **kw):
-        opened.append(os.path.abspath(path) if isinstance(path, str) else path)
-        return real_open(path, *a, **kw)
-
-    monkeypatch.setattr("builtins.open", spy)
-    build.source_fingerprint((), sources, headers)
-    monkeypatch.undo()
-    assert opened
-    return set(opened)
-
-
-def own_and_shared(key: str):
-    """The files of a kept-corpus library as build.py lists them: (its own, the two it shares), as paths."""
-    _, sources, headers = build.SIDE_LIBS[key]
-    files = [os.path.join(CSRC, s) for s in sources] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in headers]
-    shared = [p for p in files if os.path.basename(p) in KEPT_SHARED]
-    assert sorted(os.path.basename(p) for p in shared) == sorted(KEPT_SHARED), key
-    return [p for p in files if p not in shared], shared
-
-
-def check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch):
-    """Opened by exactly the three kept-corpus libraries' fingerprints — never by libmemvul_hip.so's or the tokeniser library's, whose stamps bench.py keys on — and
-    included by no file under csrc/ outside those libraries' own sources."""
-    shared = {os.path.join(CSRC, h) for h in KEPT_SHARED}
-    assert sorted(k for k, (_, _, headers) in build.SIDE_LIBS.items() if set(KEPT_SHARED) & set(headers)) == sorted(KEPT_OWN)
-    for key in KEPT_OWN:
-        assert shared <= opened_by_fingerprint(monkeypatch, *build.SIDE_LIBS[key][1:]), key
-    assert not shared & opened_by_fingerprint(monkeypatch)
-    assert not shared & opened_by_fingerprint(monkeypatch, build.TOK_SOURCES, build.TOK_HEADERS)
-    assert not set(KEPT_SHARED) & set(build.HEADERS + build.KERNEL_HEADERS + build.TOK_HEADERS + build.SOURCES + build.TOK_SOURCES)
-    theirs = {f for pair in KEPT_OWN.values() for f in pair} | set(KEPT_SHARED)
-    includes = {}
-    for name in os.listdir(CSRC):
-        text = open(os.path.join(CSRC, name)).read()
-        includes[name] = re.findall(r'#include\s+"([^"]+)"', text)
-        if name not in theirs:
-            assert not any(h in text for h in KEPT_SHARED), name
-    for source, header in KEPT_OWN.values():  # the host side goes into the .hip file, the device side into its kernel header, and neither shared header includes anything of this tree
-        assert "kept_index.h" in includes[source] and "kept_terms.h" not in includes[source], source
-        assert "kept_terms.h" in includes[header] and "kept_index.h" not in includes[header], header
-    assert includes["kept_index.h"] == [] and includes["kept_terms.h"] == []
-
-
-def check_kernels_are_the_recorded_ones(lib_path: str, flag: str):
-    """build.kernel_fingerprints of a side library against the map recorded under profiles/: a refactor of the shared headers must leave every kernel's bytes alone."""
-    recorded = os.path.join(ROOT, "profiles", f"kernel_fingerprints_{flag}.json")
-    with open(recorded) as f:
-        want = json.load(f)
-    got = build.kernel_fingerprints(lib_path)
-    changed = sorted(set(want) ^ set(got)) + sorted(k for k in set(want) & set(got) if want[k] != got[k])
-    assert not changed, (f"{len(changed)} symbols of {os.path.basename(lib_path)} differ from {recorded}: {changed[:4]}; if the kernels were meant to change, re-record with "
-                         f"`python scripts/kernel_fingerprints.py --{flag} --out profiles/kernel_fingerprints_{flag}.json`")
-
-
 # ---- 3, 4: the build --------------------------------------------------------------------------------------------------------------------------------------------
 
 def test_build_all_returns_two_paths_and_leaves_three_fresh_libraries(libs):
@@ -125,14 +62,14 @@ def test_build_all_returns_two_paths_and_leaves_three_fresh_libraries(libs):
 
 
 def test_the_kernels_are_the_recorded_ones(libs):
-    check_kernels_are_the_recorded_ones(build.LIB_PATH_RETRIEVE, "retrieve")
+    kk.check_kernels_are_the_recorded_ones(build.LIB_PATH_RETRIEVE, "retrieve")
 
 
 def test_the_main_library_does_not_know_the_new_files(libs, monkeypatch):
-    new, _ = own_and_shared("retrieve")
+    new, _ = kk.own_and_shared("retrieve")
     assert sorted(os.path.basename(p) for p in new) == ["memvul_retrieve.h", "report_topk.h", "retrieve.hip"]
     assert build.SIDE_LIBS["retrieve"] == (build.RETRIEVE_LIB_NAME, build.RETRIEVE_SOURCES, build.RETRIEVE_HEADERS)
-    check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
+    kk.check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
     opened = []
     real_open = open
 
@@ -236,53 +173,19 @@ def test_the_plan_model_sees_each_seeded_fault(tie_heavy, fault):
 
 # ---- 7: validation before any library call ------------------------------------------------------------------------------------------------------------------------
 
-class _StubLib:
-    """Records every call; holds `n` rows."""
+class _StubLib(kk.StubLib):
+    PREFIX = "mvr_"
 
-    def __init__(self):
-        self.log, self.n = [], 0
-
-    def mvr_create(self, device, P, w, same_idx, out):
-        self.log.append(("create", device, P, same_idx))
-        C.cast(out, C.POINTER(C.c_void_p))[0] = 1
-        return 0
-
-    def mvr_destroy(self, h):
-        self.log.append(("destroy",))
-
-    def mvr_last_error(self, h):
-        return b"stub"
-
-    def mvr_add(self, h, e, n):
-        self.log.append(("add", n))
-        self.n += n
-        return 0
-
-    def mvr_reset(self, h):
-        self.log.append(("reset",))
-        self.n = 0
-        return 0
-
-    def mvr_count(self, h):
-        return self.n
-
-    def mvr_query(self, h, v, Q, k, first, count, p, r):
+    def query(self, h, v, Q, k, first, count, p, r):
         self.log.append(("query", Q, k, first, count))
         return 0
 
-    def mvr_psame(self, h, v, Q, first, count, p):
+    def psame(self, h, v, Q, first, count, p):
         self.log.append(("psame", Q, first, count))
         return 0
 
-    def mvr_kernel_ms(self, h, ms):
-        return -1
 
-    def mvr_test_plan(self, h, a, b, c):
-        self.log.append(("plan", a, b, c))
-        return 0
-
-
-W512 = np.zeros((2, 3 * 512), np.float32)
+W512 = kk.W512
 
 
 def test_bad_arguments_raise_before_any_call():
@@ -385,76 +288,9 @@ def test_from_sweep_delivers_the_rows_in_the_original_order(monkeypatch):
 
 # ---- 8: ModelMemory.anchor_reports and the command line on the stand-in ------------------------------------------------------------------------------------------
 
-class _KeepingEngine(pu.OracleEngine):
-    """The oracle-backed stand-in plus what a keeping sweep needs."""
-    created = []
-
-    def __init__(self, device=0, **kw):
-        super().__init__(device, **kw)
-        self.device, self.kept = device, None
-        _KeepingEngine.created.append(self)
-
-    def bucketed_sweep(self, ids, lens, batch, with_probs=False, keep=False, topk=0):
-        self.kept = self.encode(ids, lens) if keep else None
-        return super().bucketed_sweep(ids, lens, batch, with_probs)
-
-    def sweep_embeddings(self, first=0, count=None, chunk=65536):
-        if self.kept is None:
-            raise RuntimeError("sweep_embeddings: the resident corpus keeps no embeddings — sweep it with bucketed_sweep(..., keep=True) first")
-        return self.kept[first:None if count is None else first + count]
-
-
-class _NumpyIndex:
-    """index_factory of the CPU tests: ranks the oracle's P(same) with reference_topk."""
-    made = []
-    weights = None
-
-    def __init__(self, device, P, w, same_idx):
-        self.w, self.same_idx, self.u, self.closed, self.queries = np.asarray(w), same_idx, np.zeros((0, P), np.float32), False, 0
-        _NumpyIndex.made.append(self)
-
-    def add(self, e):
-        self.u = np.concatenate([self.u, e])
-
-    def query(self, v, k, first=0, count=None):
-        from oracle import memvul_oracle as orc
-
-        self.queries += 1
-        _, p, _, _ = orc.match(self.u, np.asarray(v, np.float32), self.w, self.same_idx)
-        return kit.reference_topk(p[:, :, self.same_idx].astype(np.float32), k)
-
-    def close(self):
-        self.closed = True
-
-
-@pytest.fixture()
-def standin_model(monkeypatch):
-    from memvul_amd.archive import load_archive
-
-    fx = pu.make_fixture(n_irs=23, n_anchors=4, layers=2)
-    root, arch, golden, test_path, w, dims = fx
-    monkeypatch.setattr(model_memory, "Engine", _KeepingEngine)
-    archive = load_archive(arch, cuda_device=0, overrides=pu.TEST_CONFIG, engine_options=dict(max_tokens=16 * 256, max_batch=16, max_anchors=16))
-    model = archive.model
-    model.eval()
-    model._golden_instances_embeddings = None
-    model._golden_instances_labels = None
-    model.forward_on_instances(list(archive.validation_dataset_reader.read(golden)))
-    arrays = archive.dataset_reader.read_arrays(test_path)
-    _NumpyIndex.made = []
-    yield model, arrays, fx
-    shutil.rmtree(root, ignore_errors=True)
-
-
 def test_anchor_reports_on_the_standin(standin_model):
     model, arrays, fx = standin_model
     w = fx[4]
-    with pytest.raises(RuntimeError, match="keep=True"):
-        model.anchor_reports(arrays, 5, index_factory=_NumpyIndex)
-    model.sweep_arrays(arrays, batch_size=8, with_probs=True)  # not a keeping sweep
-    with pytest.raises(RuntimeError, match="keep=True"):
-        model.anchor_reports(arrays, 5, index_factory=_NumpyIndex)
-    assert _NumpyIndex.made == []
     _, _, ps = model.sweep_arrays(arrays, batch_size=8, with_probs=True, keep=True)
     out = model.anchor_reports(arrays, 5, index_factory=_NumpyIndex)
     assert [e["anchor"] for e in out] == model._golden_labels == [f"CWE-{100 + i}" for i in range(4)]
@@ -471,10 +307,6 @@ def test_anchor_reports_on_the_standin(standin_model):
     assert len(_NumpyIndex.made) == 1 and _NumpyIndex.made[0].queries == 2
     assert [e["anchor"] for e in out2] == ["fresh CVE", "another"] and [r["row"] for r in out2[0]["reports"]] == want_r[2, :3].tolist()
     assert [e["anchor"] for e in model.anchor_reports(arrays, 1, vectors=v, index_factory=_NumpyIndex)] == ["0", "1"]
-    with pytest.raises(ValueError):
-        model.anchor_reports(arrays, 3, vectors=v, labels=["one"], index_factory=_NumpyIndex)
-    with pytest.raises(RuntimeError, match="keep=True"):
-        model.anchor_reports(arrays, 3, 0, 10, index_factory=_NumpyIndex)  # other rows than the kept sweep's
     # k beyond the rows: the exhausted slots are left out
     assert [len(e["reports"]) for e in model.anchor_reports(arrays, 64, index_factory=_NumpyIndex)] == [23] * 4
     # a new sweep replaces the index: of rows 4 .. 20 now, numbered as in `arrays`
@@ -498,7 +330,8 @@ def test_the_command_line_writes_one_json_line_per_anchor(capsys, tmp_path):
         lines = [json.loads(ln) for ln in open(out)]
         assert rc == 0 and [e["anchor"] for e in lines] == [f"CWE-{100 + i}" for i in range(4)] and all(len(e["reports"]) == 3 for e in lines)
         eng = _KeepingEngine.created[0]
-        ids, lens, urls = _inputs(arch, golden, test_path)
+        ids, lens, arrs = _inputs(arch, golden, test_path)
+        urls = arrs["urls"]
         p = eng.forward(ids, lens)["probs"][:, :, 0]
         want_p, want_r = kit.reference_topk(p.astype(np.float32), 3)
         assert sorted(urls) == sorted(r["Issue_Url"] for r in json.load(open(test_path)))  # (the reader's order, which "row" counts in, is its own)
@@ -515,17 +348,6 @@ def test_the_command_line_writes_one_json_line_per_anchor(capsys, tmp_path):
             retrieve.main(["--archive", arch, "--golden", golden, "--input", test_path, "--k", "65"], engine_factory=_KeepingEngine, index_factory=_NumpyIndex)
     finally:
         shutil.rmtree(root, ignore_errors=True)
-
-
-def _inputs(arch, golden, test_path):
-    from memvul_amd import audit
-
-    from memvul_amd import archive
-
-    _, config, _ = audit._read_archive(arch)
-    ids, lens, _, _ = audit._read_inputs(config, golden, test_path)
-    reader = archive._build_reader(config.get("validation_dataset_reader")) or archive._build_reader(config.get("dataset_reader"))
-    return np.asarray(ids), np.asarray(lens), reader.read_arrays(test_path)["urls"]
 
 
 # ---- 9: no GPU, no index ------------------------------------------------------------------------------------------------------------------------------------------

@@ -17,10 +17,8 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import report_index_kit as kit  # noqa: E402
+from kept_index_kit import L2, WK, WK768, _engine_matrix, _same_bytes, bare_model  # noqa: E402
 
-L2 = dict(layers=2, vocab_size=2048)
-WK = dict(qk_scale=4.0, match_scale=6.0)
-WK768 = dict(qk_scale=4.0, match_scale=6.0, use_header=False)
 N_MAX, G_MAX, N_PLAN, G_PLAN = 1000, 257, 4099, 7
 
 
@@ -28,13 +26,6 @@ N_MAX, G_MAX, N_PLAN, G_PLAN = 1000, 257, 4099, 7
 def gu():
     import gpu_util
     return gpu_util
-
-
-def _engine_matrix(eng, U, V):
-    """probs [N, G, 2] of the engine's matcher for every (row of U, row of V)."""
-    eng.anchor_set(V)
-    mb = eng.cfg.max_batch
-    return np.concatenate([eng.match(np.ascontiguousarray(U[s0:s0 + mb]))["probs"] for s0 in range(0, len(U), mb)])
 
 
 def _case(gu, P):
@@ -72,18 +63,6 @@ def _index(c, same_idx, rows):
     ix = retrieve.ReportIndex(0, c["U"].shape[1], c["Wm"], same_idx)
     ix.add(np.ascontiguousarray(c["U"][:rows]))
     return ix
-
-
-def _same_bytes(got, want, what):
-    """Byte equality, with the figures printed first."""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    if got.tobytes() != want.tobytes():
-        bits = np.dtype("i4") if got.dtype == np.float32 else got.dtype
-        diff = got.view(bits) != want.view(bits)
-        ulp = np.abs(got.view(bits).astype(np.int64) - want.view(bits).astype(np.int64))
-        print(f"{what}: {int(diff.sum())} of {diff.size} values differ; largest bit-pattern distance {int(ulp.max())}; first at {np.argwhere(diff)[0].tolist()}")
-    assert got.tobytes() == want.tobytes(), what
 
 
 # ---- 1 -----------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -234,14 +213,7 @@ def test_the_query_vectors_do_not_see_each_other(gu, c512):
 
 # ---- 6 -----------------------------------------------------------------------------------------------------------------------------------------------------------
 
-class _Vocab:
-    def get_token_index(self, token, namespace=None):
-        return {"same": 0, "diff": 1}[token]
-
-
 def test_end_to_end_from_a_kept_sweep(gu, c512):
-    from memvul_amd.model_memory import ModelMemory
-
     eng = c512["eng"]
     dims, _ = gu.weights_for(L2, WK)
     n = 200
@@ -262,9 +234,7 @@ def test_end_to_end_from_a_kept_sweep(gu, c512):
                 assert tp.shape == (5 + more, 10) and np.array_equal(tr, want_r)
                 _same_bytes(tp, want_p, f"from_sweep, {5 + more} anchors")
         # the same through ModelMemory.anchor_reports
-        m = ModelMemory.__new__(ModelMemory)
-        m.__dict__.update(_engine=eng, vocab=_Vocab(), _label_namespace="labels", _same_idx=0, _matcher_weight=c512["Wm"], _golden_labels=[f"CWE-{i}" for i in range(7)],
-                          _counts=lambda best, lab: None, _siamese_metric=type("M", (), {"add_arrays": lambda self, a, b: None})())
+        m = bare_model(eng, c512["Wm"], 7)
         arrays = {"type": "test", "ids": ids, "lens": lens, "same": np.zeros(n, bool), "urls": [f"https://example.invalid/issues/{i}" for i in range(n)]}
         _, _, ps = m.sweep_arrays(arrays, batch_size=64, with_probs=True, keep=True)
         out = m.anchor_reports(arrays, 10)
@@ -273,7 +243,7 @@ def test_end_to_end_from_a_kept_sweep(gu, c512):
         for g, e in enumerate(out):
             assert [r["row"] for r in e["reports"]] == want_r[g].tolist() and [r["Issue_Url"] for r in e["reports"]] == [arrays["urls"][r] for r in want_r[g]]
             assert np.array([r["prob"] for r in e["reports"]], np.float32).tobytes() == want_p[g].tobytes()
-        m._drop_report_index()
+        m._kept.drop()
 
 
 # ---- 7 -----------------------------------------------------------------------------------------------------------------------------------------------------------
