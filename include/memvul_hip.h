@@ -381,8 +381,11 @@ const char* mv_kernel_class_name(int cls);
  * (Sp = S rounded up to a multiple of 64, above 256 to a multiple of 128; buffers hold the state of the LAST executed layer; Q carries
  * the folded 1/8.  The pass takes the path its size selects — persistent kernels or the small-pass kernels — with last-layer pruning
  * off and the final LayerNorm applied, so buffer 0 is the normalised output of layer n_layers.  MV_FORM_GUARDED is ignored here: the taps show the default
- * form, nothing is rescored.  An MV_F32 handle has buffers 0 and 10 only: its Q, K, V, context and intermediate are fp32 planes, and mv_debug_read of the
- * fp16 taps 1 - 9 returns MV_ERR_INVALID with a message that says so.)
+ * form, nothing is rescored.  An MV_F32 handle has buffers 0 and 10 and its own fp32 planes 35 - 37: its Q, K, V, context and intermediate are fp32 planes,
+ * and mv_debug_read of the fp16 taps 1 - 9 returns MV_ERR_INVALID with a message that says so.)
+ * The fp32 planes of the reference form, token order, product library and development build alike: 35 qkv32 fp32 [B*Sp][2304], Q (1/8 folded) | K | V, head h in
+ * columns 64 h .. 64 h + 63 of each block; 36 ctx32 fp32 [B*Sp][768], the attention context; 37 h32 fp32 [B*Sp][3072], the GELU output.  Each is written once per
+ * layer and holds the last executed layer's.  On a handle of another compute dtype they answer MV_ERR_STATE (the buffer does not exist in that dtype).
  * The raw planes of the persistent path, in the engine's own row order (rows 0 and 1 of a sequence hold its [CLS] and its LAST token; T = B*Sp tokens):
  * 11 x8, the stream's fp8 planes, bytes [T][2*768] = [lo8 | hi8] per row; 12 st_lo fp16 [2 B][768], 2^11 x the stream's low parts of the special rows, compact
  * [2 b + row]; 13 lnstats and 14 lnpart fp32 [T][3][2], per row and 256-column tile the (sum, sum of squares) of the stream at the layer's input / after the
@@ -395,7 +398,10 @@ const char* mv_kernel_class_name(int cls);
  * between a residual GEMM and the launch that writes the matching vstats leaves them with a stream and statistics that do not belong together).
  * After an ordinary mv_debug_encode they hold what the last layer and the final LayerNorm left (buffer 1 is then the NORMALISED stream); the development build's
  * MEMVUL_DEBUG_STOP=k ends the pass after the first k launch groups of its last layer, without the final LayerNorm, so that every plane is what that launch
- * wrote.  A buffer that does not exist in the handle's compute dtype (11, 12, 15 - 18, 20, 21: MV_F16X8; 19: MV_F16) answers MV_ERR_STATE.
+ * wrote.  A buffer that does not exist in the handle's compute dtype (11, 12, 15 - 18, 20, 21: MV_F16X8; 19: MV_F16; 35 - 37: MV_F32) answers MV_ERR_STATE.
+ * On an MV_F32 handle MEMVUL_DEBUG_STOP=k ends the pass inside its last layer after 1 the QKV GEMM, 2 attention, 3 the output-projection GEMM (buffer 0 = the raw
+ * x + ctx Wo^T + bo, before LayerNorm 1), 4 LayerNorm 1 and FFN-1 (buffer 0 the normalised stream, 37 the GELU output), 5 FFN-2 (buffer 0 raw, before LayerNorm 2);
+ * the pooler does not run, and with n_layers = 0 the embedding stays as it is.
  * The tail taps, development build with MEMVUL_DEBUG_TAIL=1 only (the product library answers "unknown buffer"): mv_debug_encode never prunes its last layer, so these
  * are filled by an ORDINARY pruned pass on workspace set 0 (mv_encode, mv_forward), which then copies the B real rows each launch of the pruned last layer's
  * [CLS] tail wrote into an arena of its own — the tail overwrites c32 and pooled in place.  22 c32 fp32 [B][768] and 23 c16 fp16 [B][768] as cls_gather_kernel

@@ -973,6 +973,9 @@ class Engine:
             22: ((B, 768), np.float32), 23: ((B, 768), np.float16), 24: ((B, 768), np.float32), 25: ((B, 768), np.float32 if self._precise else np.float16),
             26: ((B, 768), np.float32), 27: ((B, 768), np.float32), 28: ((B, 768), np.float16), 29: ((B, 3072), np.float32 if self._precise else np.float16),
             30: ((B, 768), np.float32), 31: ((B, 768), np.float32), 32: ((B, 768), np.float32), 33: ((B, self.P), np.float32), 34: ((3,), np.int32),
+            # the fp32 planes of the reference form (MV_F32 handles only): 35 Q (1/8 folded) | K | V, 36 the attention context, 37 the GELU output; token order
+            # (this compute dtype swaps no special rows)
+            35: ((B, Sp, 3 * 768), np.float32), 36: ((B, Sp, 768), np.float32), 37: ((B, Sp, 3072), np.float32),
         }
         shape, dt = shapes[buffer]
         out = np.empty(shape, dt)

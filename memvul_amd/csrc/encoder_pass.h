@@ -201,7 +201,10 @@ int launch_gemm_f32(mv_handle* h, hipStream_t stream, int cls, const float* A, c
 // One pass in the reference form: the small-pass structure (fp32 stream xres, explicit LayerNorm kernels, natural token order) with every GEMM and the
 // attention in fp32.  No last-layer pruning in this dtype (1/12 of the time of a form that is not run for throughput; one code path): after the last layer
 // xres holds the normalised stream of every token, which is also what the debug taps read.
-int encode_f32_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_lens, int B, int S_in, int n_layers, float* u_out, int pitch) {
+// stop (mv_debug_encode of the development build, mv_handle::dbg_stop; 0 = off): the pass ends inside its LAST layer — after 1 the QKV GEMM, 2 attention, 3 the
+// output-projection GEMM (xres = the raw x + ctx Wo^T + bo, before LayerNorm 1), 4 LayerNorm 1 and FFN-1, 5 FFN-2 (xres raw, before LayerNorm 2) — and the pooler
+// does not run.  qkv32, ctx32 and h32 are written once per layer, so stops 3, 4, 5 and the ordinary run expose every launch.  stop == 0 launches what it always did.
+int encode_f32_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_lens, int B, int S_in, int n_layers, float* u_out, int pitch, int stop = 0) {
   const mv_config& c = h->cfg;
   const int Sp = padded_len(S_in);
   const int64_t M = (int64_t)B * Sp, Mpad = round_up(M, 256);
@@ -223,19 +226,26 @@ int encode_f32_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* 
     return launch_check(h, "layernorm");
   };
   const int Mp = (int)Mpad, H = MV_HIDDEN, I = MV_INTER;
+  if (stop && n_layers == 0) return MV_OK;  // the embedding as it is
   for (int l = 0; l < n_layers; ++l) {
     const LayerW& w = h->L[l];
+    const int ls = l == n_layers - 1 ? stop : 0;  // the launch groups of this layer to run (0 = all)
     if (int rc = launch_gemm_f32<RF_ACT_NONE>(h, wk.stream, KC_GEMM_QKV, wk.xres, w.wqkv32, w.bqkv, nullptr, wk.qkv32, Mp, 3 * H, H)) return rc;
+    if (ls == 1) return MV_OK;
     {
       ProfScope ps(h, wk.stream, KC_ATTENTION);
       const int units = B * MV_HEADS * (Sp / 32);
       hipLaunchKernelGGL(attention_f32_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, wk.stream, (const float*)wk.qkv32, d_lens, wk.ctx32, Sp, units);
       if (int rc = launch_check(h, "attention_f32")) return rc;
     }
+    if (ls == 2) return MV_OK;
     if (int rc = launch_gemm_f32<RF_ACT_RES>(h, wk.stream, KC_GEMM_OUT, wk.ctx32, w.wo32, w.bo, wk.xres, wk.xres, Mp, H, H)) return rc;
+    if (ls == 3) return MV_OK;
     if (int rc = run_ln(w.ln1g, w.ln1b)) return rc;
     if (int rc = launch_gemm_f32<RF_ACT_GELU>(h, wk.stream, KC_GEMM_FFN1, wk.xres, w.w132, w.b1, nullptr, wk.h32, Mp, I, H)) return rc;
+    if (ls == 4) return MV_OK;
     if (int rc = launch_gemm_f32<RF_ACT_RES>(h, wk.stream, KC_GEMM_FFN2, wk.h32, w.w232, w.b2, wk.xres, wk.xres, Mp, H, I)) return rc;
+    if (ls == 5) return MV_OK;
     if (int rc = run_ln(w.ln2g, w.ln2b)) return rc;
   }
   if (u_out) {
@@ -519,8 +529,7 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
   if (pitch <= 0) pitch = S_in;
   // mv_debug_encode of the development build with its stop switch set (mv_handle::dbg_stop): the pass ends after that many launch groups of its last layer
   const int stop = full ? h->dbg_stop : 0;
-  if (stop && h->f32) return fail(h, MV_ERR_STATE, "mv_debug_encode: the stop inside a layer exists on the persistent path of MV_F16 / MV_F16X8 only");
-  if (h->f32) return encode_f32_dev(h, wk, d_ids, d_lens, B, S_in, n_layers, u_out, pitch);  // MV_F32: no forms, no monitors, no pruning
+  if (h->f32) return encode_f32_dev(h, wk, d_ids, d_lens, B, S_in, n_layers, u_out, pitch, stop);  // MV_F32: no forms, no monitors, no pruning; the stop ends its one path
   const mv_config& c = h->cfg;
   PassPlan p{};
   p.B = B; p.S_in = S_in; p.Sp = padded_len(S_in); p.pitch = pitch;

@@ -427,7 +427,8 @@ int read_switches(mv_handle* h) {
     if (!env_int("MEMVUL_NUM_CU", 1, h->num_cu, &h->num_cu)) return MV_ERR_INVALID;
     //   MEMVUL_DEBUG_STOP 1 .. 5: mv_debug_encode(ids, lens, n) runs n - 1 whole layers, then only the first k launch groups of layer n - 1 (1 the QKV projection with
     //                     its row term, 2 + attention, 3 + the output projection, 4 + FFN-1, 5 + FFN-2) and NO final LayerNorm (nor with n = 0): every workspace buffer
-    //                     keeps what the last launch left in it, for mv_debug_read (persistent path, MV_F16 / MV_F16X8)
+    //                     keeps what the last launch left in it, for mv_debug_read (persistent path, MV_F16 / MV_F16X8).  MV_F32: the same k on its one path
+    //                     (encoder_pass.h encode_f32_dev: 3 ends before LayerNorm 1, 4 after LayerNorm 1 and FFN-1, 5 before LayerNorm 2; no pooler)
     if (!env_int("MEMVUL_DEBUG_STOP", 1, 5, &h->dbg_stop)) return MV_ERR_INVALID;
     //   MEMVUL_DEBUG_TAIL 1: a pruned pass on workspace set 0 (mv_encode, mv_forward, ...) copies what each launch of its [CLS] tail wrote — the B real rows — into a
     //                     tap arena, device to device on the pass's own stream, for mv_debug_read 22 - 34 (encoder_pass.h tail_tap).  Copies only: no launch, argument or
@@ -974,7 +975,7 @@ int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes) try {
   const void* src = nullptr;
   int64_t avail = 0;
   if (h->f32 && buffer >= 1 && buffer <= 9)
-    return fail(h, MV_ERR_INVALID, "mv_debug_read: buffers 1 - 9 are the fp16 planes of MV_F16 / MV_F16X8; an MV_F32 handle has buffer 0 (hidden fp32) and 10 (embedding)");
+    return fail(h, MV_ERR_INVALID, "mv_debug_read: buffers 1 - 9 are the fp16 planes of MV_F16 / MV_F16X8; an MV_F32 handle has buffer 0 (hidden fp32), 10 (embedding) and its fp32 planes 35 - 37 (Q | K | V, context, GELU output)");
   switch (buffer) {
     case 0: src = wk.xres; avail = T * MV_HIDDEN * 4; break;
     case 1: src = wk.x16; avail = T * MV_HIDDEN * 2; break;
@@ -1000,6 +1001,10 @@ int mv_debug_read(mv_handle* h, int buffer, void* dst, int64_t bytes) try {
     case 19: src = wk.xlo; avail = Tp * MV_HIDDEN * 2; break;
     case 20: src = wk.cls_corr; avail = (int64_t)2 * h->dbg_B * MV_INTER * 4; break;
     case 21: src = wk.tile_both; avail = (int64_t)((T + 255) / 256) * 4; break;
+    // the fp32 planes of the reference form (MV_F32 only; allocated for no other compute dtype), token order
+    case 35: src = wk.qkv32; avail = T * 3 * MV_HIDDEN * 4; break;
+    case 36: src = wk.ctx32; avail = T * MV_HIDDEN * 4; break;
+    case 37: src = wk.h32; avail = T * MV_INTER * 4; break;
 #if defined(MEMVUL_DEV_SWITCHES)
     // the tail taps (include/memvul_hip.h 22 - 34; encoder_pass.h tail_tap): B rows each, of the last pruned pass on workspace set 0
     case 22: case 23: case 24: case 25: case 26: case 27: case 28: case 29: case 30: case 31: case 32: case 33: {

@@ -189,13 +189,15 @@ def test_gemm_against_float64(gu, M, N, K):
     """|C - C64| <= 2 g(K) (|A| |W|^T + |bias| + |res|) elementwise, g = 1.5e-7 for K = 768 and 3.5e-7 for K = 3072 (the fmaf chain's measured constants);
     GELU / residual epilogues compared after the same float64 epilogue (GELU is 1-Lipschitz up to 1.13: the bound on its argument, x 1.13, + 4 fp32 roundings
     of the result)."""
+    import f32_stage_kit as fsk  # (the bound lives there: tests/test_f32_stage_gpu.py holds the engine's own launches to it)
+
     eng = gu.engine_for(L2, WK, compute_dtype="f32")
     rng = np.random.default_rng(M + N + K)
     A = rng.standard_normal((M, K)).astype(np.float32)
     W = (rng.standard_normal((N, K)) * 0.05).astype(np.float32)
     bias = rng.standard_normal(N).astype(np.float32)
     res = rng.standard_normal((M, N)).astype(np.float32)
-    g = 1.5e-7 if K == 768 else 3.5e-7
+    g = fsk.gemm_g(K)
     A64, W64 = A.astype(np.float64), W.astype(np.float64)
     pre = A64 @ W64.T + bias
     mag = np.abs(A64) @ np.abs(W64).T + np.abs(bias)
@@ -203,12 +205,12 @@ def test_gemm_against_float64(gu, M, N, K):
     for act in ("bias", "gelu", "res"):
         C, ms = eng.test_gemm_f32(A, W, bias, res if act == "res" else None, act=act)
         if act == "bias":
-            want, bound = pre, 2 * g * mag
+            want, bound = pre, fsk.gemm_bound("bias", g, mag)
         elif act == "gelu":
             want = _gelu64(pre[:64])  # (the float64 erf is a Python loop: 64 rows of it)
-            C, bound = C[:64], 1.13 * 2 * g * mag[:64] + 4 * 6e-8 * np.abs(want)
+            C, bound = C[:64], fsk.gemm_bound("gelu", g, mag[:64], want=want)
         else:
-            want, bound = pre + res, 2 * g * (mag + np.abs(res))
+            want, bound = pre + res, fsk.gemm_bound("res", g, mag, res=res)
         worst[act] = float((np.abs(C - want) / bound).max())
         assert np.all(np.abs(C - want) <= bound), (act, worst)
     gu.record("f32_form_gemm", M=M, N=N, K=K, **{f"err_over_bound_{a}": v for a, v in worst.items()})
