@@ -1,5 +1,6 @@
-"""Build libmemvul_hip.so (product and development build) and the side libraries of SIDE_LIBS — libmemvul_tok_u8.so, libmemvul_retrieve.so, libmemvul_claims.so and
-libmemvul_bank.so — for gfx950, in-tree with hipcc.  The last three share csrc/kept_index.h and csrc/kept_terms.h, which no other library includes.  No torch involved."""
+"""Build libmemvul_hip.so (product and development build) and the side libraries of SIDE_LIBS — libmemvul_tok_u8.so, libmemvul_retrieve.so, libmemvul_claims.so,
+libmemvul_bank.so and libmemvul_rank.so — for gfx950, in-tree with hipcc.  The middle three share csrc/kept_index.h and csrc/kept_terms.h, which no other library
+includes (libmemvul_rank.so restates what it needs of them in its own two files).  No torch involved."""
 from __future__ import annotations
 
 from functools import partial
@@ -28,6 +29,7 @@ DEV_FLAGS = ("-DMEMVUL_DEV_SWITCHES", "-Wl,-Bsymbolic")
 #   retrieve  per-anchor retrieval over a kept corpus (csrc/retrieve.hip, csrc/report_topk.h, include/memvul_retrieve.h)
 #   claims    per-anchor claims over a kept corpus (csrc/claims.hip, csrc/claim_sweep.h, include/memvul_claims.h)
 #   bank      the anchor-bank audit over a kept corpus (csrc/bank.hip, csrc/bank_cover.h, include/memvul_bank.h)
+#   rank      per-anchor ranking quality over a kept corpus (csrc/rank.hip, csrc/rank_sort.h, include/memvul_rank.h); stands alone as well, and shares no header
 # The three kept-corpus libraries stand alone — nothing links against them and they link against nothing of this tree, so neither the source fingerprint nor the
 # kernel map of the libraries above moves with them — and share two headers, which only they include: csrc/kept_index.h (the host side of an index over a kept corpus)
 # and csrc/kept_terms.h (the device functions of the row and vector terms)
@@ -37,12 +39,14 @@ SIDE_LIBS = {
     "retrieve": ("libmemvul_retrieve.so", ["retrieve.hip"], ["report_topk.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_retrieve.h")]),
     "claims": ("libmemvul_claims.so", ["claims.hip"], ["claim_sweep.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_claims.h")]),
     "bank": ("libmemvul_bank.so", ["bank.hip"], ["bank_cover.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_bank.h")]),
+    "rank": ("libmemvul_rank.so", ["rank.hip"], ["rank_sort.h", os.path.join(ROOT, "include", "memvul_rank.h")]),
 }
 TOK_LIB_NAME, TOK_SOURCES, TOK_HEADERS = SIDE_LIBS["tok"]
 RETRIEVE_LIB_NAME, RETRIEVE_SOURCES, RETRIEVE_HEADERS = SIDE_LIBS["retrieve"]
 CLAIMS_LIB_NAME, CLAIMS_SOURCES, CLAIMS_HEADERS = SIDE_LIBS["claims"]
 BANK_LIB_NAME, BANK_SOURCES, BANK_HEADERS = SIDE_LIBS["bank"]
-LIB_PATH_TOK, LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS, LIB_PATH_BANK = (os.path.join(LIB_DIR, SIDE_LIBS[k][0]) for k in ("tok", "retrieve", "claims", "bank"))
+RANK_LIB_NAME, RANK_SOURCES, RANK_HEADERS = SIDE_LIBS["rank"]
+LIB_PATH_TOK, LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS, LIB_PATH_BANK, LIB_PATH_RANK = (os.path.join(LIB_DIR, SIDE_LIBS[k][0]) for k in ("tok", "retrieve", "claims", "bank", "rank"))
 SOURCES = ["engine.hip"]
 KERNEL_HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", "wordpiece.h"]
 # the host code of the library: engine.hip includes each of these parts once, in this order
@@ -275,8 +279,8 @@ def build_side(key: str, force: bool = False, verbose: bool = True) -> str:
     return lib_path
 
 
-tok_is_stale, retrieve_is_stale, claims_is_stale, bank_is_stale = (partial(side_is_stale, k) for k in ("tok", "retrieve", "claims", "bank"))
-build_tok, build_retrieve, build_claims, build_bank = (partial(build_side, k) for k in ("tok", "retrieve", "claims", "bank"))
+tok_is_stale, retrieve_is_stale, claims_is_stale, bank_is_stale, rank_is_stale = (partial(side_is_stale, k) for k in ("tok", "retrieve", "claims", "bank", "rank"))
+build_tok, build_retrieve, build_claims, build_bank, build_rank = (partial(build_side, k) for k in ("tok", "retrieve", "claims", "bank", "rank"))
 
 
 def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool = False) -> str:
@@ -316,14 +320,14 @@ def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool =
 
 
 def build_all(force: bool = False, verbose: bool = True):
-    """Both builds, compiled side by side (two hipcc processes), after the library both link against; libmemvul_retrieve.so, libmemvul_claims.so and
-    libmemvul_bank.so, which stand alone, beside them.  Returns the paths of the two builds of libmemvul_hip.so (LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS and LIB_PATH_BANK
-    are where the other three lie)."""
+    """Both builds, compiled side by side (two hipcc processes), after the library both link against; libmemvul_retrieve.so, libmemvul_claims.so,
+    libmemvul_bank.so and libmemvul_rank.so, which stand alone, beside them.  Returns the paths of the two builds of libmemvul_hip.so (LIB_PATH_RETRIEVE,
+    LIB_PATH_CLAIMS, LIB_PATH_BANK and LIB_PATH_RANK are where the other four lie)."""
     from concurrent.futures import ThreadPoolExecutor
 
     build_tok(force, verbose)
-    with ThreadPoolExecutor(5) as ex:
-        sides = [ex.submit(build_side, key, force, verbose) for key in ("retrieve", "claims", "bank")]
+    with ThreadPoolExecutor(6) as ex:
+        sides = [ex.submit(build_side, key, force, verbose) for key in ("retrieve", "claims", "bank", "rank")]
         futs = [ex.submit(build, force, verbose, (), d) for d in (False, True)]
         for side in sides:
             side.result()
@@ -331,4 +335,4 @@ def build_all(force: bool = False, verbose: bool = True):
 
 
 if __name__ == "__main__":
-    print("\n".join(build_all(force="--force" in sys.argv) + [LIB_PATH_TOK, LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS, LIB_PATH_BANK]))
+    print("\n".join(build_all(force="--force" in sys.argv) + [LIB_PATH_TOK, LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS, LIB_PATH_BANK, LIB_PATH_RANK]))

@@ -469,6 +469,22 @@ class ModelMemory(Model):
         index = self._kept_index("anchor_bank_audit", "bank", bank.BankAudit, index_factory, positive)
         return bank.run_audit(index, labels, vectors, thres, positive, candidates, candidate_labels, candidate_thres, w_pos, w_neg, max_rounds, top)
 
+    def anchor_ranking(self, arrays: Dict[str, Any], first: int = 0, last: Optional[int] = None, vectors=None, labels: Optional[List[str]] = None, bank: bool = True,
+                       index_factory=None) -> List[Dict[str, Any]]:
+        """How well every anchor RANKS the rows of the last ``sweep_arrays(..., keep=True)`` against ``arrays["same"]`` — the three numbers the reference judges
+        the matcher by (custom_metric.py:86-90), per anchor: for every anchor of the bank as it is NOW — or for every row of ``vectors`` (fp32 [Q, P]), named by
+        ``labels`` — ``{"anchor", "n_pos", "n_neg", "n_nan", "auc", "ap", "best_thres", "best_f1", "best_claimed", "best_positives"}``: the exact ROC-AUC (ties
+        at one half), sklearn's average precision, and the threshold that maximises F1 over EVERY distinct score (a tie to the highest).  bank: one more entry,
+        ``"anchor": "bank"``, for a report's maximum over the vectors — what the reference's own auc / ap measure.  Runs on the GPU (rank.RankIndex;
+        ``index_factory(device, proj_dim, matcher_weight, same_idx)`` builds it) over an index that is filled once per kept sweep and dropped with the others."""
+        from . import rank
+
+        last = self._kept_last("anchor_ranking", arrays, first, last)
+        vectors, labels = self._vectors_and_labels("anchor_ranking", vectors, labels)
+        positive = np.ascontiguousarray(np.asarray(arrays["same"][first:last], bool))
+        index = self._kept.ranking_index("anchor_ranking", rank.RankIndex, self.engine, self._same_idx, index_factory, positive)
+        return rank.ranking_of(index, labels, vectors, bank=bank)
+
     def format_records_json(self, labels: List[str], urls: List[str], p_same: np.ndarray) -> str:
         """``json.dumps(make_output_human_readable(...))`` of one batch, byte for byte, built from arrays: the line
         predict_memory.py:111 writes per batch ({"Issue_Url", "label", "predict": {cwe: P(same)}} per issue report)."""

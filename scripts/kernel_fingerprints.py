@@ -1,12 +1,12 @@
 """Per-kernel fingerprints of the library's device code (memvul_amd/build.py kernel_fingerprints): print them, write them, or compare them with a
 recorded map.
 
-  python scripts/kernel_fingerprints.py [--dev | --tok | --retrieve | --claims | --bank] [--lib FILE.so] [--out FILE.json] [--against FILE.json]
+  python scripts/kernel_fingerprints.py [--dev | --tok | --retrieve | --claims | --bank | --rank] [--lib FILE.so] [--out FILE.json] [--against FILE.json]
 
 --against lists the symbols that were added, removed or changed and exits 1 if there are any: a host-only edit of engine.hip or of its parts must report none, for the
 product and for the development build (profiles/kernel_fingerprints*.json hold the maps of the tree as committed; --tok: libmemvul_tok_u8.so, the UTF-8 tokenise
 kernel's own library, profiles/kernel_fingerprints_tok.json; --retrieve: libmemvul_retrieve.so, per-anchor retrieval; --claims: libmemvul_claims.so, per-anchor claims;
---bank: libmemvul_bank.so, the anchor-bank audit)."""
+--bank: libmemvul_bank.so, the anchor-bank audit; --rank: libmemvul_rank.so, per-anchor ranking quality, profiles/kernel_fingerprints_rank.json)."""
 import argparse
 import json
 import os
@@ -31,6 +31,7 @@ def main(argv=None) -> int:
     ap.add_argument("--retrieve", action="store_true", help="the per-anchor retrieval library (libmemvul_retrieve.so)")
     ap.add_argument("--claims", action="store_true", help="the per-anchor claims library (libmemvul_claims.so)")
     ap.add_argument("--bank", action="store_true", help="the anchor-bank audit library (libmemvul_bank.so)")
+    ap.add_argument("--rank", action="store_true", help="the per-anchor ranking library (libmemvul_rank.so)")
     ap.add_argument("--lib", help="another library file")
     ap.add_argument("--against", help="a map written by --out: compare, exit 1 on any difference")
     ap.add_argument("--out", help="write the map here instead of printing it")
