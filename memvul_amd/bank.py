@@ -27,7 +27,7 @@ from typing import Optional
 import numpy as np
 
 from .claims import _thresholds, up32  # noqa: F401  (the same rule for thresholds: float64 rounded UP to fp32, fp32 taken as it is)
-from .kept_index import ClassedKeptIndex, _check_array, _int, _ptr, load_side_library  # noqa: F401  (the kept-corpus index the three libraries share)
+from .kept_index import ClassedKeptIndex, _check_array, _int, _ptr, load_side_library  # noqa: F401  (the kept-corpus index the four libraries share)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmemvul_bank.so")

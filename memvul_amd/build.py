@@ -1,6 +1,6 @@
 """Build libmemvul_hip.so (product and development build) and the side libraries of SIDE_LIBS — libmemvul_tok_u8.so, libmemvul_retrieve.so, libmemvul_claims.so,
-libmemvul_bank.so and libmemvul_rank.so — for gfx950, in-tree with hipcc.  The middle three share csrc/kept_index.h and csrc/kept_terms.h, which no other library
-includes (libmemvul_rank.so restates what it needs of them in its own two files).  No torch involved."""
+libmemvul_bank.so and libmemvul_rank.so — for gfx950, in-tree with hipcc.  The last four share csrc/kept_index.h and csrc/kept_terms.h, which no other library
+includes.  No torch involved."""
 from __future__ import annotations
 
 from functools import partial
@@ -29,8 +29,8 @@ DEV_FLAGS = ("-DMEMVUL_DEV_SWITCHES", "-Wl,-Bsymbolic")
 #   retrieve  per-anchor retrieval over a kept corpus (csrc/retrieve.hip, csrc/report_topk.h, include/memvul_retrieve.h)
 #   claims    per-anchor claims over a kept corpus (csrc/claims.hip, csrc/claim_sweep.h, include/memvul_claims.h)
 #   bank      the anchor-bank audit over a kept corpus (csrc/bank.hip, csrc/bank_cover.h, include/memvul_bank.h)
-#   rank      per-anchor ranking quality over a kept corpus (csrc/rank.hip, csrc/rank_sort.h, include/memvul_rank.h); stands alone as well, and shares no header
-# The three kept-corpus libraries stand alone — nothing links against them and they link against nothing of this tree, so neither the source fingerprint nor the
+#   rank      per-anchor ranking quality over a kept corpus (csrc/rank.hip, csrc/rank_sort.h, include/memvul_rank.h)
+# The four kept-corpus libraries stand alone — nothing links against them and they link against nothing of this tree, so neither the source fingerprint nor the
 # kernel map of the libraries above moves with them — and share two headers, which only they include: csrc/kept_index.h (the host side of an index over a kept corpus)
 # and csrc/kept_terms.h (the device functions of the row and vector terms)
 KEPT_HEADERS = ["kept_index.h", "kept_terms.h"]
@@ -39,7 +39,7 @@ SIDE_LIBS = {
     "retrieve": ("libmemvul_retrieve.so", ["retrieve.hip"], ["report_topk.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_retrieve.h")]),
     "claims": ("libmemvul_claims.so", ["claims.hip"], ["claim_sweep.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_claims.h")]),
     "bank": ("libmemvul_bank.so", ["bank.hip"], ["bank_cover.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_bank.h")]),
-    "rank": ("libmemvul_rank.so", ["rank.hip"], ["rank_sort.h", os.path.join(ROOT, "include", "memvul_rank.h")]),
+    "rank": ("libmemvul_rank.so", ["rank.hip"], ["rank_sort.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_rank.h")]),
 }
 TOK_LIB_NAME, TOK_SOURCES, TOK_HEADERS = SIDE_LIBS["tok"]
 RETRIEVE_LIB_NAME, RETRIEVE_SOURCES, RETRIEVE_HEADERS = SIDE_LIBS["retrieve"]

@@ -3,7 +3,7 @@
 // first row): B[q][n] = P(same)[n, q] >= thres[q] in IEEE fp32 (a NaN claims nothing).  Only integers leave the device.
 //
 // P(same)[n, g] is, bit for bit, the fp32 value the engine's matcher produces for the pair: kept_terms.h states its arithmetic, sa_n and bv_g included, once for the
-// three kept-corpus libraries (this library includes no header of another library of this tree, whose kernels it would otherwise instantiate).
+// four kept-corpus libraries (this library includes no header of another library of this tree, whose kernels it would otherwise instantiate).
 //
 // Plan (bank.hip drives it):
 //   bank_row_term_kernel      sa_n, once per row when the row is added: one wave per row

@@ -2,7 +2,7 @@
 // threshold — the reference's decision rule (prob >= thres), not a rank — and, per vector and threshold, how many rows of each class it claims.
 //
 // The result is defined bit for bit: P(same)[n, g] is the fp32 value the engine's matcher (match_topk.h) produces for that pair.  kept_terms.h states its arithmetic,
-// sa_n and bv_g included, once for the three kept-corpus libraries;
+// sa_n and bv_g included, once for the four kept-corpus libraries;
 // a pair is CLAIMED iff P(same) >= t in IEEE fp32: a NaN claims nothing (the per-anchor top-k library ranks a NaN first; here it is never listed and never counted).
 //
 // Plan (claims.hip drives it):

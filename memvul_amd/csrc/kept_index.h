@@ -1,8 +1,9 @@
-// The index over a kept corpus that libmemvul_retrieve.so, libmemvul_claims.so and libmemvul_bank.so share: the rows and their row terms on the device, the error
-// plumbing of the C boundary, and the calls that are the same in all three (create, add, set_classes, the range check, the vectors' upload, kernel_ms).  Host code
-// only; retrieve.hip, claims.hip and bank.hip include it and derive their index from KeptIndex, adding their own workspace and held state.
+// The index over a kept corpus that libmemvul_retrieve.so, libmemvul_claims.so, libmemvul_bank.so and libmemvul_rank.so share: the rows and their row terms on the
+// device, the error plumbing of the C boundary, and the calls that are the same in all four (create, add, set_classes, the range check, the vectors' upload; kernel_ms
+// for the three that time a call by event pairs).  Host code only; retrieve.hip, claims.hip, bank.hip and rank.hip include it and derive their index from KeptIndex,
+// adding their own workspace and held state.
 //
-// Everything here has INTERNAL linkage (one anonymous namespace, no inline function with vague linkage): a process loads the three libraries side by side, and a
+// Everything here has INTERNAL linkage (one anonymous namespace, no inline function with vague linkage): a process loads the four libraries side by side, and a
 // symbol the dynamic linker could bind across them would tie one library's host code to another's (build.py's note on -Bsymbolic records what that cost once).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,7 +19,7 @@
 
 namespace {
 
-// the return codes and limits the three public headers share; each library asserts its own macros against them
+// the return codes and limits the four public headers share; each library asserts its own macros against them
 constexpr int KEPT_OK = 0, KEPT_ERR_ARG = -1, KEPT_ERR_HIP = -2, KEPT_ERR_NOMEM = -3, KEPT_ERR_INTERNAL = -4, KEPT_ERR_STATE = -5;
 constexpr int KEPT_MAX_VECTORS = 4096;
 constexpr int64_t KEPT_MAX_ROWS = 2147483646ll;
@@ -37,7 +38,7 @@ struct KeptKernels {
 struct KeptIndex {
   const KeptKernels* kernels;
   const bool has_cls;                 // the rows carry a class byte (the retrieval index allocates none)
-  const int nev;                      // events created: two per pair
+  const int nev;                      // events created: two per pair (none for the ranking index, whose stage clock keeps its own)
   int device = 0, P = 0, same_idx = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // ev[0..1] bracket the launches of a call, ev[2..3] those of a call's second phase

@@ -1,5 +1,5 @@
-// The per-row and per-vector terms of P(same) over a kept corpus, stated once for the kernel headers of the three kept-corpus libraries (per-anchor retrieval,
-// per-anchor claims, the anchor-bank audit).
+// The per-row and per-vector terms of P(same) over a kept corpus, stated once for the kernel headers of the four kept-corpus libraries (per-anchor retrieval,
+// per-anchor claims, the anchor-bank audit, per-anchor ranking quality).
 //
 // P(same)[n, g] is defined bit for bit: it is the fp32 value the engine's matcher (match_topk.h) produces for the pair (row n, vector g).  That value depends on the
 // pair alone, so its arithmetic is restated here (NOT included: match_topk.h's inline launchers would instantiate the engine's kernels into these libraries):

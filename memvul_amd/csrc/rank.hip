@@ -1,36 +1,29 @@
 // libmemvul_rank.so: per-anchor ranking quality over a kept corpus (include/memvul_rank.h; kernels and plan: rank_sort.h).  A library of its own, which no other
-// library of this tree links against and which includes no file of theirs: their kernel sets, their source fingerprints and their lists of entries all stay as
-// they are.  The host side of an index over a kept corpus (the rows and their row terms on the device, the error plumbing of the C boundary, create / add /
-// set_classes / kernel_ms) is therefore restated here.  Everything but the entries has INTERNAL linkage: a process loads the side libraries next to each other.
+// library of this tree links against: their kernel sets, their source fingerprints and their lists of entries all stay as they are.  The index over the kept
+// corpus is kept_index.h's; what stands here is the library's own: the plan, the sort and the statistics, the stages' clock and the held curve.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <limits>
-#include <new>
-#include <stdexcept>
-#include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/memvul_rank.h"
 #include "rank_sort.h"
+#include "kept_index.h"
 
-struct mvk_index {
-  int device = 0, P = 0, same_idx = 0;
-  hipStream_t stream = nullptr;
-  std::vector<hipEvent_t> ev;         // the stage boundaries of a call, in order; created as needed, kept
+KEPT_ASSERT_ABI(MVK, MVK_MAX_VECTORS);
+static_assert(MVK_ERR_STATE == KEPT_ERR_STATE, "the public header and kept_index.h disagree");
+
+namespace {
+const KeptKernels kRankKernels = {rank_weight_delta_kernel, {rank_row_term_kernel<512>, rank_row_term_kernel<768>}, {rank_vector_prep_kernel<512>, rank_vector_prep_kernel<768>}};
+}
+
+struct mvk_index : KeptIndex {
+  mvk_index() : KeptIndex(&kRankKernels, true, 0) {}  // (no event of the base: the stages' clock below keeps its own, and `timed` is 0 or 1)
+  std::vector<hipEvent_t> ev_clock;   // the stage boundaries of a call, in order; created as needed, kept
   std::vector<int> ev_stage;          // the stage that ends at each event of the last call (-1: none)
   float ms[4] = {0.f, 0.f, 0.f, 0.f}; // the last call: whole, score, sort, statistics
-  bool timed = false;
-  float *U = nullptr, *sa = nullptr;  // rows [cap][P], row terms [cap]
-  uint8_t* cls = nullptr;             // [cap]
-  int64_t n = 0, cap = 0;
-  float* wd = nullptr;                // [3][P] class-difference weights
   // workspace (grows, never shrinks)
-  float *vdev = nullptr, *vT = nullptr, *bv = nullptr;  // the vectors [Q][P]; one group transposed [P][Qs]; its bv [Qs]
-  size_t vdev_n = 0, vT_n = 0, bv_n = 0;
   uint32_t *keys_a = nullptr, *keys_b = nullptr, *hist = nullptr, *bank = nullptr;  // [group][count] twice; [group][ntiles][256]; [count]
   size_t keys_a_n = 0, keys_b_n = 0, hist_n = 0, bank_n = 0;
   RankTileSum* sums = nullptr;        // [group][ntiles]
@@ -52,103 +45,17 @@ struct mvk_index {
   size_t c_thres_n = 0, c_tp_n = 0, c_fp_n = 0;
   int plan_tile_rows = 0, plan_vector_group = 0;  // mvk_test_plan; 0 = the library's own choice
   int64_t plan_work_cap = 0;
-  std::string err;
 };
 
 namespace {
-
-thread_local std::string g_err;  // errors with no index to hang them on (create)
-
-struct Refusal : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-struct StateError : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-int fail(mvk_index* h, int code, const std::string& msg) {
-  (h ? h->err : g_err) = msg;
-  return code;
-}
-
-int on_exception(mvk_index* h) noexcept {
-  try {
-    try {
-      throw;
-    } catch (const Refusal& e) {
-      return fail(h, MVK_ERR_ARG, e.what());
-    } catch (const StateError& e) {
-      return fail(h, MVK_ERR_STATE, e.what());
-    } catch (const std::bad_alloc&) {
-      return fail(h, MVK_ERR_NOMEM, "out of host memory");
-    } catch (const std::exception& e) {
-      return fail(h, MVK_ERR_HIP, e.what());
-    } catch (...) {
-      return fail(h, MVK_ERR_INTERNAL, "unknown C++ exception");
-    }
-  } catch (...) {  // (the message itself could not be stored)
-    return MVK_ERR_INTERNAL;
-  }
-}
-
-void hipchk(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(X) hipchk((X), #X)
-
-void launched(const char* what) { hipchk(hipGetLastError(), what); }
-
-void need(bool ok, const std::string& msg) {
-  if (!ok) throw Refusal(msg);
-}
-
-template <typename T>
-void grow(T*& p, size_t& have, size_t want) {  // (contents are not kept)
-  if (want <= have) return;
-  if (p) HIPCHK(hipFree(p));
-  p = nullptr;
-  have = 0;
-  HIPCHK(hipMalloc((void**)&p, want * sizeof(T)));
-  have = want;
-}
-
-void reserve_rows(mvk_index* h, int64_t want) {
-  if (want <= h->cap) return;
-  const int64_t cap = std::max<int64_t>(want, std::min<int64_t>(h->cap + h->cap / 2, MVK_MAX_ROWS));
-  float *U = nullptr, *sa = nullptr;
-  uint8_t* cls = nullptr;
-  hipError_t e = hipMalloc((void**)&U, (size_t)cap * h->P * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&sa, (size_t)cap * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&cls, (size_t)cap);
-  if (e == hipSuccess && h->n) {
-    e = hipMemcpyAsync(U, h->U, (size_t)h->n * h->P * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sa, h->sa, (size_t)h->n * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cls, h->cls, (size_t)h->n, hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  }
-  if (e != hipSuccess) {
-    for (void* p : {(void*)U, (void*)sa, (void*)cls})
-      if (p) (void)hipFree(p);
-    hipchk(e, "growing the rows' buffers");
-  }
-  for (void* p : {(void*)h->U, (void*)h->sa, (void*)h->cls})
-    if (p) (void)hipFree(p);
-  h->U = U;
-  h->sa = sa;
-  h->cls = cls;
-  h->cap = cap;
-}
 
 void drop_curve(mvk_index* h) {
   h->held = false;
   h->points = 0;
 }
 
-void check_range(const mvk_index* h, const float* v, int Q, int64_t first, int64_t count) {
-  need(v != nullptr, "the vectors are NULL");
-  need(Q >= 1 && Q <= MVK_MAX_VECTORS, "Q = " + std::to_string(Q) + ": 1 <= Q <= 4096");
-  need(first >= 0 && count >= 0 && first <= h->n && count <= h->n - first,
-       "rows [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) + ") are not within the " + std::to_string(h->n) + " rows of the index");
+void check_rank_range(const mvk_index* h, const float* v, int Q, int64_t first, int64_t count) {
+  check_range(h, "vectors", v, Q, first, count);
   need(count <= MVK_MAX_RANK_ROWS, "count = " + std::to_string(count) + ": one call ranks at most 2^26 rows (MVK_MAX_RANK_ROWS)");
 }
 
@@ -210,29 +117,29 @@ struct Clock {
   mvk_index* h;
   size_t used = 0;
   explicit Clock(mvk_index* h_) : h(h_) {
-    h->timed = false;
+    h->timed = 0;
     h->ev_stage.clear();
     tick(0);
   }
   void tick(int stage) {
-    if (used == h->ev.size()) {
+    if (used == h->ev_clock.size()) {
       hipEvent_t e = nullptr;
       HIPCHK(hipEventCreate(&e));
-      h->ev.push_back(e);
+      h->ev_clock.push_back(e);
     }
-    HIPCHK(hipEventRecord(h->ev[used++], h->stream));
+    HIPCHK(hipEventRecord(h->ev_clock[used++], h->stream));
     h->ev_stage.push_back(stage);
   }
   void done() {  // the stream is idle
     float ms[4] = {0.f, 0.f, 0.f, 0.f};
     for (size_t i = 1; i < used; ++i) {
       float t = 0.f;
-      HIPCHK(hipEventElapsedTime(&t, h->ev[i - 1], h->ev[i]));
+      HIPCHK(hipEventElapsedTime(&t, h->ev_clock[i - 1], h->ev_clock[i]));
       ms[h->ev_stage[i]] += t;
     }
     ms[0] = ms[1] + ms[2] + ms[3];
     std::copy(ms, ms + 4, h->ms);
-    h->timed = true;
+    h->timed = 1;
   }
 };
 
@@ -248,9 +155,7 @@ void by_tile(int tile, Launch launch) {
 // the group's vectors [q0, q0 + nq) transposed and their bv, then keys_a [nq][count] of rows [first, first + count)
 void score_group(mvk_index* h, int q0, int nq, int64_t first, int64_t count) {
   const int Qs = (nq + RK_QT - 1) / RK_QT * RK_QT;
-  if (h->P == 512) hipLaunchKernelGGL(rank_vector_prep_kernel<512>, dim3((Qs + 63) / 64), dim3(64), 0, h->stream, h->vdev + (size_t)q0 * h->P, h->wd, h->vT, h->bv, nq, Qs);
-  else hipLaunchKernelGGL(rank_vector_prep_kernel<768>, dim3((Qs + 63) / 64), dim3(64), 0, h->stream, h->vdev + (size_t)q0 * h->P, h->wd, h->vT, h->bv, nq, Qs);
-  launched("rank_vector_prep_kernel");
+  kept_vector_prep(h, q0, nq, Qs);
   RankScoreArgs a{};
   a.first = first; a.count = count; a.nblocks = (count + RK_BR - 1) / RK_BR; a.nq = nq; a.Qs = Qs; a.same_idx = h->same_idx; a.cls = h->cls; a.keys = h->keys_a;
   const dim3 grid((unsigned)(Qs / RK_QT), (unsigned)std::min<int64_t>(a.nblocks, RK_GRID_Y), (unsigned)((a.nblocks + RK_GRID_Y - 1) / RK_GRID_Y));
@@ -314,11 +219,6 @@ void stats_keys(mvk_index* h, const Plan& pl, const uint32_t* keys, int nq, int6
   launched("rank_finish_kernel");
 }
 
-void upload_vectors(mvk_index* h, const float* v, int Q) {
-  grow(h->vdev, h->vdev_n, (size_t)Q * h->P);
-  HIPCHK(hipMemcpyAsync(h->vdev, v, (size_t)Q * h->P * sizeof(float), hipMemcpyHostToDevice, h->stream));
-}
-
 }  // namespace
 
 extern "C" {
@@ -326,68 +226,23 @@ extern "C" {
 const char* mvk_last_error(mvk_index* h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 int mvk_create(int device, int proj_dim, const float* Wm, int same_idx, mvk_index** out) try {
-  need(out != nullptr, "out is NULL");
-  *out = nullptr;
-  need(proj_dim == 512 || proj_dim == 768, "proj_dim = " + std::to_string(proj_dim) + ": the matcher runs on 512 or 768 features");
-  need(same_idx == 0 || same_idx == 1, "same_idx = " + std::to_string(same_idx) + ": 0 or 1");
-  need(Wm != nullptr, "the matcher weight is NULL");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw std::runtime_error("no HIP device: the ranking index has no CPU fallback");
-  need(device >= 0 && device < ndev, "device " + std::to_string(device) + " of " + std::to_string(ndev));
-  HIPCHK(hipSetDevice(device));
-  mvk_index* h = new mvk_index();
-  h->device = device; h->P = proj_dim; h->same_idx = same_idx;
-  try {
-    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    float* wm = nullptr;
-    HIPCHK(hipMalloc((void**)&h->wd, (size_t)3 * h->P * sizeof(float)));
-    HIPCHK(hipMalloc((void**)&wm, (size_t)6 * h->P * sizeof(float)));
-    hipError_t e = hipMemcpyAsync(wm, Wm, (size_t)6 * h->P * sizeof(float), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(rank_weight_delta_kernel, dim3((3 * h->P + 255) / 256), dim3(256), 0, h->stream, wm, h->wd, h->P);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(wm);
-    hipchk(e, "uploading the matcher weight");
-  } catch (...) {
-    mvk_destroy(h);
-    throw;
-  }
-  *out = h;
+  kept_create("ranking index", mvk_destroy, device, proj_dim, Wm, same_idx, out);
   return MVK_OK;
 } catch (...) { return on_exception(nullptr); }
 
 void mvk_destroy(mvk_index* h) {
   if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->U, (void*)h->sa, (void*)h->cls, (void*)h->wd, (void*)h->vdev, (void*)h->vT, (void*)h->bv, (void*)h->keys_a, (void*)h->keys_b, (void*)h->hist,
-                  (void*)h->bank, (void*)h->sums, (void*)h->carry, (void*)h->totals, (void*)h->p_u2, (void*)h->p_ap, (void*)h->p_best, (void*)h->o_n, (void*)h->o_u2,
-                  (void*)h->o_best, (void*)h->o_ap, (void*)h->o_thres, (void*)h->c_thres, (void*)h->c_tp, (void*)h->c_fp})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : h->ev)
+  kept_destroy_common(h, {h->keys_a, h->keys_b, h->hist, h->bank, h->sums, h->carry, h->totals, h->p_u2, h->p_ap, h->p_best, h->o_n, h->o_u2, h->o_best, h->o_ap, h->o_thres,
+                          h->c_thres, h->c_tp, h->c_fp});
+  for (hipEvent_t e : h->ev_clock)  // (the stream they were recorded on is drained and gone)
     if (e) (void)hipEventDestroy(e);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
 
 int mvk_add(mvk_index* h, const float* embed, int64_t n) try {
   if (!h) return fail(nullptr, MVK_ERR_ARG, "index is NULL");
   drop_curve(h);
-  need(n >= 0, "n = " + std::to_string(n) + " rows");
-  need(n <= MVK_MAX_ROWS - h->n, "the index would hold more than 2^31 - 2 rows");
-  if (n == 0) return MVK_OK;
-  need(embed != nullptr, "the embeddings are NULL");
-  HIPCHK(hipSetDevice(h->device));
-  reserve_rows(h, h->n + n);
-  HIPCHK(hipMemcpyAsync(h->U + (size_t)h->n * h->P, embed, (size_t)n * h->P * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemsetAsync(h->cls + h->n, 0, (size_t)n, h->stream));
-  if (h->P == 512) hipLaunchKernelGGL(rank_row_term_kernel<512>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->stream, h->U, h->wd, h->sa, (long long)h->n, (long long)n);
-  else hipLaunchKernelGGL(rank_row_term_kernel<768>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->stream, h->U, h->wd, h->sa, (long long)h->n, (long long)n);
-  launched("rank_row_term_kernel");
-  HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's buffer is free again, and the rows count only once they are there)
-  h->n += n;
+  kept_add(h, embed, n);
   return MVK_OK;
 } catch (...) { return on_exception(h); }
 
@@ -403,22 +258,15 @@ int64_t mvk_count(mvk_index* h) { return h ? h->n : 0; }
 int mvk_set_classes(mvk_index* h, const uint8_t* cls, int64_t first, int64_t n) try {
   if (!h) return fail(nullptr, MVK_ERR_ARG, "index is NULL");
   drop_curve(h);
-  need(first >= 0 && n >= 0 && first <= h->n && n <= h->n - first,
-       "rows [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are not within the " + std::to_string(h->n) + " rows of the index");
-  if (n == 0) return MVK_OK;
-  need(cls != nullptr, "the classes are NULL");
-  for (int64_t i = 0; i < n; ++i) need(cls[i] <= 1, "cls[" + std::to_string(i) + "] = " + std::to_string((int)cls[i]) + ": a class is 0 or 1");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemcpyAsync(h->cls + first, cls, (size_t)n, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  kept_set_classes(h, cls, first, n);
   return MVK_OK;
 } catch (...) { return on_exception(h); }
 
 int mvk_rank(mvk_index* h, const float* v, int Q, int bank, int64_t first, int64_t count, int64_t* n, int64_t* u2, double* ap, float* best_thres, int64_t* best) try {
   if (!h) return fail(nullptr, MVK_ERR_ARG, "index is NULL");
   drop_curve(h);
-  h->timed = false;
-  check_range(h, v, Q, first, count);
+  h->timed = 0;
+  check_rank_range(h, v, Q, first, count);
   need(n != nullptr && u2 != nullptr && ap != nullptr && best_thres != nullptr && best != nullptr, "an output buffer is NULL");
   const int S = Q + (bank ? 1 : 0);
   if (count == 0) {  // nothing to rank
@@ -432,7 +280,7 @@ int mvk_rank(mvk_index* h, const float* v, int Q, int bank, int64_t first, int64
   const Plan pl = plan_for(h, Q, bank != 0, count);
   HIPCHK(hipSetDevice(h->device));
   grow_for(h, pl, count, S, bank != 0);
-  upload_vectors(h, v, Q);
+  kept_upload_vectors(h, v, Q);
   Clock clock(h);
   for (int q0 = 0; q0 < Q; q0 += pl.group) {
     const int nq = std::min(pl.group, Q - q0);
@@ -473,8 +321,8 @@ int mvk_rank(mvk_index* h, const float* v, int Q, int bank, int64_t first, int64
 int mvk_curve(mvk_index* h, const float* v, int Q, int bank, int64_t first, int64_t count, int64_t* points) try {
   if (!h) return fail(nullptr, MVK_ERR_ARG, "index is NULL");
   drop_curve(h);
-  h->timed = false;
-  check_range(h, v, Q, first, count);
+  h->timed = 0;
+  check_rank_range(h, v, Q, first, count);
   need(bank || Q == 1, "Q = " + std::to_string(Q) + " without the bank score: a curve is that of ONE ranking");
   need(points != nullptr, "points is NULL");
   if (count == 0) {  // an empty curve is held
@@ -485,7 +333,7 @@ int mvk_curve(mvk_index* h, const float* v, int Q, int bank, int64_t first, int6
   const Plan pl = plan_for(h, Q, bank != 0, count);
   HIPCHK(hipSetDevice(h->device));
   grow_for(h, pl, count, 1, bank != 0);
-  upload_vectors(h, v, Q);
+  kept_upload_vectors(h, v, Q);
   Clock clock(h);
   for (int q0 = 0; q0 < Q; q0 += pl.group) {
     const int nq = std::min(pl.group, Q - q0);
@@ -543,7 +391,7 @@ int mvk_fetch(mvk_index* h, float* thres, int64_t* tp, int64_t* fp) try {
 int mvk_kernel_ms(mvk_index* h, float* ms) try {
   if (!h) return fail(nullptr, MVK_ERR_ARG, "index is NULL");
   need(ms != nullptr, "ms is NULL");
-  need(h->timed, "the last call launched no kernel");
+  need(h->timed > 0, "the last call launched no kernel");
   std::copy(h->ms, h->ms + 4, ms);
   return MVK_OK;
 } catch (...) { return on_exception(h); }

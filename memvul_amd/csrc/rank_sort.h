@@ -1,10 +1,9 @@
 // Per-anchor ranking quality: for every vector g (an anchor of the bank, or the embedding of a fresh CVE description) the exact ROC-AUC, the average precision and
 // the best-F1 cut of its P(same) over the rows of a kept corpus — rank statistics: a sort per vector, then scans.  include/memvul_rank.h states the definitions.
 //
-// The scores are defined bit for bit: P(same)[n, g] is the fp32 value the engine's matcher produces for that pair.  This library shares no text with the other
-// libraries over a kept corpus; it restates the arithmetic here, instruction order as in the per-anchor claims sweep, and a GPU test pins the bits to the engine:
-//   sa_n    = sum (W_a[0] - W_a[1]) . u_n   lane l takes features l + 64 j by fmaf, j ascending from 0; then the six-step DPP ladder of rk_wave_sum
-//   bv_g    = fma chain of (W_b[0] - W_b[1])[i] * v_g[i],           i ascending, from 0
+// The scores are defined bit for bit: P(same)[n, g] is the fp32 value the engine's matcher produces for that pair.  kept_terms.h states its arithmetic, sa_n and
+// bv_g included, once for the four kept-corpus libraries; the score kernel here restates the ending only, instruction order as in the per-anchor claims sweep,
+// and a GPU test pins the bits to the engine:
 //   dd_{n,g} = fma chain of (W_c[0] - W_c[1])[i] * |u_n[i] - v_g[i]|, i ascending, from 0      (the weight differences are formed in fp32 first)
 //   delta = (sa_n + bv_g) + dd;  e = expf(-|delta|);  inv = 1 / (1 + e);  P_0 = delta >= 0 ? inv : e inv;  P_1 the other;  P(same) = P_{same_idx}
 //
@@ -31,6 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kept_terms.h"
+
 #define RK_QT 16          // vectors per workgroup tile of the score kernel = chains per lane
 #define RK_MI 32          // features staged per step
 #define RK_BR 256         // rows per workgroup of the score kernel
@@ -44,19 +45,6 @@
 
 typedef float rk_f4 __attribute__((ext_vector_type(4)));
 
-// Wave-wide sum, the engine matcher's ladder: row_shr 1, 2, 4, 8, row_bcast 15, row_bcast 31, lane 63 read
-__device__ __forceinline__ float rk_wave_sum(float x) {
-#define RK_SUM_STEP(CTRL, ROWS) x += __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), CTRL, ROWS, 0xf, false));
-  RK_SUM_STEP(0x111, 0xf)
-  RK_SUM_STEP(0x112, 0xf)
-  RK_SUM_STEP(0x114, 0xf)
-  RK_SUM_STEP(0x118, 0xf)
-  RK_SUM_STEP(0x142, 0xa)
-  RK_SUM_STEP(0x143, 0xc)
-#undef RK_SUM_STEP
-  return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(x), 63));
-}
-
 // ---- the weight differences, formed in fp32 on the device the matcher runs on: wd [3][P] = W_m[0] - W_m[1] for the W_a, W_b and W_c thirds
 __global__ __launch_bounds__(256) void rank_weight_delta_kernel(const float* __restrict__ Wm, float* __restrict__ wd, int P) {
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -66,29 +54,13 @@ __global__ __launch_bounds__(256) void rank_weight_delta_kernel(const float* __r
 // ---- sa_n for rows [first, first + n): one wave per row, four rows per workgroup of 256
 template <int P>
 __global__ __launch_bounds__(256) void rank_row_term_kernel(const float* __restrict__ U, const float* __restrict__ wd, float* __restrict__ sa, long long first, long long n) {
-  const int lane = threadIdx.x & 63;
-  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= n) return;
-  const float* u = U + (size_t)(first + r) * P;
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < P / 64; ++j) s = fmaf(wd[lane + 64 * j], u[lane + 64 * j], s);
-  s = rk_wave_sum(s);
-  if (lane == 0) sa[first + r] = s;
+  ks_row_term<P>(U, wd, sa, first, n);
 }
 
 // ---- one group of nq vectors v [nq][P] -> vT [P][Qs] (zeros behind nq) and bv [Qs]; one thread per slot, workgroups of 64
 template <int P>
 __global__ __launch_bounds__(64) void rank_vector_prep_kernel(const float* __restrict__ v, const float* __restrict__ wd, float* __restrict__ vT, float* __restrict__ bv, int nq, int Qs) {
-  const int q = blockIdx.x * 64 + threadIdx.x;
-  if (q >= Qs) return;
-  float s = 0.f;
-  for (int i = 0; i < P; ++i) {
-    const float x = q < nq ? v[(size_t)q * P + i] : 0.f;
-    s = fmaf(wd[P + i], x, s);
-    vT[(size_t)i * Qs + q] = x;
-  }
-  bv[q] = s;
+  ks_vector_prep<P>(v, wd, vT, bv, nq, Qs);
 }
 
 struct RankScoreArgs {

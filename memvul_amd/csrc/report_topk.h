@@ -2,7 +2,7 @@
 // corpus — the TRANSPOSE of match_topk.h, which ranks anchors per row.  Here N (rows) >> Q (query vectors).
 //
 // The result is defined bit for bit: P(same)[n, g] is the fp32 value the engine's matcher (match_topk.h) produces for that pair.  kept_terms.h states its arithmetic,
-// sa_n and bv_g included, once for the three kept-corpus libraries.
+// sa_n and bv_g included, once for the four kept-corpus libraries.
 // ranking per g: (rt_key(P) descending, row ascending), rt_key(NaN) = 2.0.
 //
 // Plan (retrieve.hip drives it):

@@ -1,6 +1,6 @@
-"""The index over a kept corpus that per-anchor retrieval (retrieve.py), per-anchor claims (claims.py) and the anchor-bank audit (bank.py) share: the rows of a
-corpus on one GPU, appended as they arrive, and the calls that are the same in all three libraries (csrc/kept_index.h is the C++ side).  Each of the three derives
-its class from KeptIndex and adds only its questions."""
+"""The index over a kept corpus that per-anchor retrieval (retrieve.py), per-anchor claims (claims.py), the anchor-bank audit (bank.py) and per-anchor ranking
+quality (rank.py) share: the rows of a corpus on one GPU, appended as they arrive, and the calls that are the same in all four libraries (csrc/kept_index.h is the
+C++ side).  Each of the four derives its class from KeptIndex and adds only its questions."""
 from __future__ import annotations
 
 import ctypes as C

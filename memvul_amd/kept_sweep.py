@@ -12,7 +12,7 @@ import numpy as np
 
 from .synth import KEY_MATCH_W
 
-KINDS = ("reports", "claims", "bank")
+KINDS = ("reports", "claims", "bank", "ranking")
 
 
 class KeptSweepState:
@@ -20,15 +20,13 @@ class KeptSweepState:
     ``_projector.weight`` of the state dict or None, ``embed`` = the host copy of the kept embeddings or None, ``indexes`` = by kind, None until asked for.
 
     The host copy (2 KB per row): downloaded once, by the first index that is filled; dropped as soon as the report index and the claim index both exist, or with
-    the state (``drop``).  The bank audit uses the copy while it is there and never keeps it alive or releases it (filled after the other two, it downloads again
-    and that copy goes by the same rule at once).  ``ranking``, the index of per-anchor ranking quality (rank.RankIndex), lives beside ``indexes`` and follows the
-    bank audit's rule for the host copy."""
+    the state (``drop``).  The bank audit and the ranking index (rank.RankIndex) use the copy while it is there and never keep it alive or release it (filled after
+    the other two, they download again and that copy goes by the same rule at once)."""
 
     def __init__(self, matcher_weight=None):
         self.matcher_weight = matcher_weight
         self.rows = self.embed = self._engine = None
         self.indexes = dict.fromkeys(KINDS)
-        self.ranking = None
 
     def require(self, who: str, first: int, last: int):
         if self.rows != (first, last):
@@ -47,17 +45,6 @@ class KeptSweepState:
                 self.embed = None
         return self.indexes[kind]
 
-    def ranking_index(self, who: str, index_class, engine, same_idx: int, index_factory=None, classes=None):
-        """The ranking index over the kept sweep: filled at the first call, the same object afterwards."""
-        if self.ranking is None:
-            if self.matcher_weight is None:
-                raise RuntimeError(f"{who}(): the state dict held no {KEY_MATCH_W}")
-            self._engine = engine
-            self.ranking = index_class.from_sweep(self, self.matcher_weight, same_idx, index_factory=index_factory, classes=classes)
-            if self.indexes["reports"] is not None and self.indexes["claims"] is not None:  # (the bank audit's rule: only those two hold the copy)
-                self.embed = None
-        return self.ranking
-
     # -- what from_sweep asks of its ``engine`` argument
     device = property(lambda self: self._engine.device)
     P = property(lambda self: self._engine.P)
@@ -73,9 +60,6 @@ class KeptSweepState:
             index, self.indexes[kind] = self.indexes[kind], None
             if index is not None:
                 index.close()
-        index, self.ranking = self.ranking, None
-        if index is not None:
-            index.close()
         self.rows = self.embed = self._engine = None
 
 

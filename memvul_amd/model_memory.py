@@ -482,7 +482,7 @@ class ModelMemory(Model):
         last = self._kept_last("anchor_ranking", arrays, first, last)
         vectors, labels = self._vectors_and_labels("anchor_ranking", vectors, labels)
         positive = np.ascontiguousarray(np.asarray(arrays["same"][first:last], bool))
-        index = self._kept.ranking_index("anchor_ranking", rank.RankIndex, self.engine, self._same_idx, index_factory, positive)
+        index = self._kept_index("anchor_ranking", "ranking", rank.RankIndex, index_factory, positive)
         return rank.ranking_of(index, labels, vectors, bank=bank)
 
     def format_records_json(self, labels: List[str], urls: List[str], p_same: np.ndarray) -> str:

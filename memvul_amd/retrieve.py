@@ -17,7 +17,7 @@ from typing import Optional
 
 import numpy as np
 
-from .kept_index import KeptIndex, _check_array, _int, _ptr, load_side_library  # noqa: F401  (the kept-corpus index the three libraries share)
+from .kept_index import KeptIndex, _check_array, _int, _ptr, load_side_library  # noqa: F401  (the kept-corpus index the four libraries share)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmemvul_retrieve.so")

@@ -1,5 +1,5 @@
-"""What the tests of the three tools over a kept corpus share (retrieve / claims / bank, CPU and GPU files alike; nothing here needs a GPU at import): the recording
-stub library, the numpy stand-in indexes, the oracle-backed keeping engines and the model on them, the checks of the two shared headers, and the GPU files' names."""
+"""What the tests of the tools over a kept corpus share (retrieve / claims / bank, and for rank the checks of the shared headers; CPU and GPU files alike; nothing
+here needs a GPU at import): the recording stub library, the numpy stand-in indexes, the oracle-backed keeping engines and the model on them, the checks of the two shared headers, and the GPU files' names."""
 import ctypes as C
 import json
 import os
@@ -21,10 +21,11 @@ CSRC = os.path.join(ROOT, "memvul_amd", "csrc")
 W512 = np.zeros((2, 3 * 512), np.float32)
 
 
-# ---- the two headers the three kept-corpus libraries share (csrc/kept_index.h, csrc/kept_terms.h) ------------------------------------------------------------------
+# ---- the two headers the four kept-corpus libraries share (csrc/kept_index.h, csrc/kept_terms.h) ------------------------------------------------------------------
 
 KEPT_SHARED = ("kept_index.h", "kept_terms.h")
-KEPT_OWN = {"retrieve": ("retrieve.hip", "report_topk.h"), "claims": ("claims.hip", "claim_sweep.h"), "bank": ("bank.hip", "bank_cover.h")}  # (source, kernel header)
+KEPT_OWN = {"retrieve": ("retrieve.hip", "report_topk.h"), "claims": ("claims.hip", "claim_sweep.h"), "bank": ("bank.hip", "bank_cover.h"),
+            "rank": ("rank.hip", "rank_sort.h")}  # (source, kernel header)
 
 
 def opened_by_fingerprint(monkeypatch, sources=None, headers=None) -> set:
@@ -52,8 +53,8 @@ def own_and_shared(key: str):
     return [p for p in files if p not in shared], shared
 
 
-def check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch):
-    """Opened by exactly the three kept-corpus libraries' fingerprints — never by libmemvul_hip.so's or the tokeniser library's, whose stamps bench.py keys on — and
+def check_the_shared_headers_belong_to_the_four_kept_libraries(monkeypatch):
+    """Opened by exactly the four kept-corpus libraries' fingerprints — never by libmemvul_hip.so's or the tokeniser library's, whose stamps bench.py keys on — and
     included by no file under csrc/ outside those libraries' own sources."""
     shared = {os.path.join(CSRC, h) for h in KEPT_SHARED}
     assert sorted(k for k, (_, _, headers) in build.SIDE_LIBS.items() if set(KEPT_SHARED) & set(headers)) == sorted(KEPT_OWN)
@@ -73,6 +74,34 @@ def check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch):
         assert "kept_index.h" in includes[source] and "kept_terms.h" not in includes[source], source
         assert "kept_terms.h" in includes[header] and "kept_index.h" not in includes[header], header
     assert includes["kept_index.h"] == [] and includes["kept_terms.h"] == []
+
+
+PLUMBING = ("on_exception", "fail", "hipchk", "launched", "need", "grow", "reserve_rows", "struct Refusal", "struct StateError", "g_err")
+
+
+def _definitions(text: str, name: str) -> int:
+    """How often ``text`` DEFINES ``name`` (a use does not count): a struct with a base or a body, a variable declared with its type, or a function — a return type,
+    the name and a parameter list at the start of a line, closed by the brace of its body."""
+    text = re.sub(r"//[^\n]*", "", text)
+    if name.startswith("struct "):
+        return len(re.findall(rf"\b{name}\b\s*[:{{]", text))
+    if name == "g_err":
+        return len(re.findall(r"^[ \t]*(?:static\s+|thread_local\s+)*std::string\s+g_err\b", text, flags=re.M))
+    return len(re.findall(rf"^[ \t]*(?:template\s*<[^>]*>\s*)?(?:static\s+|inline\s+)*[A-Za-z_][\w:<>]*[\s*&]+{name}\s*\([^;{{}}]*\)\s*(?:noexcept\s*)?\{{", text, flags=re.M))
+
+
+def check_the_index_plumbing_is_defined_once():
+    """The error plumbing of the C boundary and the rows' growth are defined by kept_index.h, each exactly once, and by none of the four libraries' sources."""
+    shared = open(os.path.join(CSRC, "kept_index.h")).read()
+    for name in PLUMBING:
+        assert _definitions(shared, name) == 1, name
+        for source, _ in KEPT_OWN.values():
+            assert _definitions(open(os.path.join(CSRC, source)).read(), name) == 0, (source, name)
+    restated = ("thread_local std::string g_err;\nstruct Refusal : std::runtime_error {\n};\nstruct StateError : std::runtime_error {\n};\n"
+                "int fail(mvk_index* h, int code, const std::string& msg) {\n  return code;\n}\nint on_exception(mvk_index* h) noexcept {\n  return fail(h, 1, g_err);\n}\n"
+                "void hipchk(hipError_t e, const char* what) {\n}\nvoid launched(const char* what) { hipchk(hipGetLastError(), what); }\nvoid need(bool ok, const std::string& msg) {\n}\n"
+                "template <typename T>\nvoid grow(T*& p, size_t& have, size_t want) {  // (contents are not kept)\n}\nstatic void reserve_rows(mvk_index* h, int64_t want) {\n  need(true, g_err);\n}\n")
+    assert [_definitions(restated, name) for name in PLUMBING] == [1] * len(PLUMBING)  # (a library that restated them would be seen)
 
 
 def check_kernels_are_the_recorded_ones(lib_path: str, flag: str):

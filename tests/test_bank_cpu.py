@@ -89,7 +89,7 @@ def test_the_module_prints_the_new_path_too():
 def test_the_other_libraries_do_not_know_the_new_files(libs, monkeypatch):
     new, _ = kk.own_and_shared("bank")
     assert build.SIDE_LIBS["bank"] == (build.BANK_LIB_NAME, build.BANK_SOURCES, build.BANK_HEADERS)
-    kk.check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
+    kk.check_the_shared_headers_belong_to_the_four_kept_libraries(monkeypatch)
     assert sorted(os.path.basename(p) for p in new) == ["bank.hip", "bank_cover.h", "memvul_bank.h"]
     opened = []
     real_open = open

@@ -76,7 +76,8 @@ def test_the_kernels_are_the_recorded_ones(libs):
 def test_the_other_libraries_do_not_know_the_new_files(libs, monkeypatch):
     new, _ = kk.own_and_shared("claims")
     assert build.SIDE_LIBS["claims"] == (build.CLAIMS_LIB_NAME, build.CLAIMS_SOURCES, build.CLAIMS_HEADERS)
-    kk.check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
+    kk.check_the_shared_headers_belong_to_the_four_kept_libraries(monkeypatch)
+    kk.check_the_index_plumbing_is_defined_once()
     assert sorted(os.path.basename(p) for p in new) == ["claim_sweep.h", "claims.hip", "memvul_claims.h"]
     opened = []
     real_open = open

@@ -37,7 +37,7 @@ def test_the_shared_refusals(standin_model, kind):
     weight, model._kept.matcher_weight = model._kept.matcher_weight, None  # (what load_state_dict leaves when the state dict has no matcher)
     with pytest.raises(RuntimeError, match=re.escape(f"{who}(): the state dict held no _projector.weight")):
         ask()
-    assert factory.made == [] and model._kept.indexes == dict.fromkeys(("reports", "claims", "bank")) and model._kept.embed is None
+    assert factory.made == [] and model._kept.indexes == dict.fromkeys(("reports", "claims", "bank", "ranking")) and model._kept.embed is None
     model._kept.matcher_weight = weight
     ask()
     assert len(factory.made) == 1 and model._kept.indexes[kind] is factory.made[0]

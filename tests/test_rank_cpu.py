@@ -99,19 +99,20 @@ def _plain_name(mangled: str) -> str:
 def test_the_other_libraries_do_not_know_the_new_files(libs, monkeypatch):
     assert build.SIDE_LIBS["rank"] == (build.RANK_LIB_NAME, build.RANK_SOURCES, build.RANK_HEADERS)
     new = [os.path.join(CSRC, "rank.hip"), os.path.join(CSRC, "rank_sort.h"), os.path.join(ROOT, "include", "memvul_rank.h")]
-    assert kk.opened_by_fingerprint(monkeypatch, *build.SIDE_LIBS["rank"][1:]) == set(new)
-    kk.check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
+    assert kk.opened_by_fingerprint(monkeypatch, *build.SIDE_LIBS["rank"][1:]) == set(new) | {os.path.join(CSRC, h) for h in kk.KEPT_SHARED}
+    kk.check_the_shared_headers_belong_to_the_four_kept_libraries(monkeypatch)
+    kk.check_the_index_plumbing_is_defined_once()
     opened = kk.opened_by_fingerprint(monkeypatch)
     for other in ("tok", "retrieve", "claims", "bank"):
         opened |= kk.opened_by_fingerprint(monkeypatch, *build.SIDE_LIBS[other][1:])
     assert not opened & set(new)
-    for name in os.listdir(CSRC):  # nothing any other library is built from includes the new header, and the new files include none of theirs
+    for name in os.listdir(CSRC):  # nothing any other library is built from includes the new header, and the new files include none of theirs but the two shared ones
         if name not in ("rank.hip", "rank_sort.h"):
             text = open(os.path.join(CSRC, name)).read()
             assert "rank_sort.h" not in text and "memvul_rank.h" not in text, name
     src = open(os.path.join(CSRC, "rank.hip")).read() + open(os.path.join(CSRC, "rank_sort.h")).read()
-    assert re.findall(r'#include\s+"([^"]+)"', src) == ["../../include/memvul_rank.h", "rank_sort.h"]
-    for theirs in ("kept_index.h", "kept_terms.h", "claim_sweep.h", "bank_cover.h", "report_topk.h", "match_topk.h", "memvul_claims.h", "memvul_bank.h", "memvul_retrieve.h"):
+    assert sorted(re.findall(r'#include\s+"([^"]+)"', src)) == sorted(["../../include/memvul_rank.h", "rank_sort.h", "kept_index.h", "kept_terms.h"])
+    for theirs in ("claim_sweep.h", "bank_cover.h", "report_topk.h", "match_topk.h", "memvul_claims.h", "memvul_bank.h", "memvul_retrieve.h"):
         assert theirs not in src, theirs
     new_map = build.kernel_fingerprints(build.LIB_PATH_RANK)
     kernels = [k for k in new_map if k.endswith(".kd")]
@@ -429,7 +430,7 @@ def test_anchor_ranking_on_the_standin(standin_model):
     json.dumps(entries)
     assert len(_NumpyRank.made) == 1 and np.array_equal(ix.w, fx[4]["_projector.weight"]) and ix.u.shape == (23, 512) and np.array_equal(ix.cls, same.astype(np.uint8))
     # the index lives beside the three, which keep their keys; the same object serves the next call; one download serves all four
-    assert model._kept.ranking is ix and model._kept.indexes == dict.fromkeys(("reports", "claims", "bank")) and _CountingEngine.downloads == 1
+    assert model._kept.indexes == dict(reports=None, claims=None, bank=None, ranking=ix) and model._kept.indexes["ranking"] is ix and _CountingEngine.downloads == 1
     assert model._kept.embed is not None  # (this index never releases the host copy)
     two = np.ascontiguousarray(model.engine.anchor_get()[[2, 0]])
     no_bank = model.anchor_ranking(arrays, vectors=two, labels=["x", "y"], bank=False, index_factory=_NumpyRank)
@@ -442,14 +443,14 @@ def test_anchor_ranking_on_the_standin(standin_model):
         model.anchor_ranking(arrays, vectors=model.engine.anchor_get(), labels=["one"], index_factory=_NumpyRank)
     # a new sweep drops the index with the other three
     model.sweep_arrays(arrays, 4, 20, batch_size=8, with_probs=True, keep=True)
-    assert ix.closed and model._kept.ranking is None and set(model._kept.indexes) == {"reports", "claims", "bank"}
+    assert ix.closed and model._kept.indexes["ranking"] is None and set(model._kept.indexes) == {"reports", "claims", "bank", "ranking"}
     with pytest.raises(RuntimeError, match="no kept sweep"):
         model.anchor_ranking(arrays, index_factory=_NumpyRank)
     part = model.anchor_ranking(arrays, 4, 20, index_factory=_NumpyRank)
     assert len(_NumpyRank.made) == 2 and _NumpyRank.made[1].u.shape == (16, 512) and np.array_equal(_NumpyRank.made[1].cls, same[4:20].astype(np.uint8))
     _check_entries(part, pm[4:20], same[4:20], model._golden_labels)
     model._kept.drop()
-    assert _NumpyRank.made[1].closed and model._kept.ranking is None
+    assert _NumpyRank.made[1].closed and model._kept.indexes["ranking"] is None
 
 
 def test_the_command_line(capsys, tmp_path):

@@ -478,6 +478,60 @@ def test_strictness(gu, c512):
         assert 0 < ms["total"] < 1e4 and abs(ms["score"] + ms["sort"] + ms["statistics"] - ms["total"]) <= 1e-3 * ms["total"] and min(ms.values()) > 0
 
 
+def test_a_refusal_is_recorded_by_the_refusing_library_alone(gu, c512):
+    """The four kept-corpus libraries open side by side over the same rows: the error text kept_index.h holds (per index, and per thread for the NULL handle) is one
+    copy per library — a refusal by one changes no other's, for the open handle or for NULL — and the ranking index answers afterwards as before."""
+    from memvul_amd import bank, retrieve
+
+    N, Q = 65, 3
+    U, v, Wm = np.ascontiguousarray(c512["U"][:N]), np.ascontiguousarray(c512["V"][:Q]), c512["Wm"]
+    cls = _classes("contrast", c512, N, 0)
+    vp, wp = v.ctypes.data_as(C.c_void_p), Wm.ctypes.data_as(C.c_void_p)
+    with retrieve.ReportIndex(0, 512, Wm, 0) as rx, claims.ClaimIndex(0, 512, Wm, 0) as cx, bank.BankAudit(0, 512, Wm, 0) as bx, _index(c512, 0, N, cls) as kx:
+        others = (rx, cx, bx)
+        for ix in others:
+            ix.add(U)
+        for ix in (cx, bx):
+            ix.set_classes(cls)
+
+        def texts(ix):
+            return ix._fn("last_error")(ix._h), ix._fn("last_error")(None)
+
+        def refuse_create(ix, proj_dim):
+            h = C.c_void_p()
+            assert ix._fn("create")(0, proj_dim, wp, 0, C.byref(h)) != 0 and not h.value
+
+        # every library holds a text of its own first, under the open handle and under NULL: a copy shared across libraries would show up as another's text
+        for i, ix in enumerate(others + (kx,)):
+            assert ix._fn("add")(ix._h, None, -1 - i) != 0
+            refuse_create(ix, 200 + i)
+            assert texts(ix) == (f"n = {-1 - i} rows".encode(), f"proj_dim = {200 + i}: the matcher runs on 512 or 768 features".encode())
+        assert len({t for ix in others + (kx,) for t in texts(ix)}) == 8
+        before = kx.rank(v, bank=True)
+        held = [texts(ix) for ix in others]
+        out = [np.full(3 * (Q + 1), 7, np.int64), np.full(Q + 1, 7, np.int64), np.full(Q + 1, 7.0, np.float64), np.full(Q + 1, 7.0, np.float32), np.full(2 * (Q + 1), 7, np.int64)]
+        assert kx._fn("rank")(kx._h, vp, 0, 1, 0, N, *(a.ctypes.data_as(C.c_void_p) for a in out)) != 0 and all((a == 7).all() for a in out)
+        refuse_create(kx, 100)
+        ranks = texts(kx)
+        assert ranks == (b"Q = 0: 1 <= Q <= 4096", b"proj_dim = 100: the matcher runs on 512 or 768 features")
+        assert [texts(ix) for ix in others] == held
+        # and the reverse: a refused claims call
+        counts = np.full(Q * 2, 7, np.int64)
+        thres = np.full(1, 0.5, np.float32)
+        assert cx._fn("counts")(cx._h, vp, Q, thres.ctypes.data_as(C.c_void_p), 0, 0, N, counts.ctypes.data_as(C.c_void_p)) != 0 and (counts == 7).all()
+        refuse_create(cx, 300)
+        assert texts(cx) == (b"T = 0: 1 <= T <= 64", b"proj_dim = 300: the matcher runs on 512 or 768 features")
+        assert texts(kx) == ranks and texts(rx) == held[0] and texts(bx) == held[2]
+        after = kx.rank(v, bank=True)
+        assert sorted(before) == sorted(after)
+        for k in before:
+            if isinstance(before[k], np.ndarray):
+                _same_bytes(after[k], before[k], f"after the refusals: {k}")
+            else:
+                assert after[k] == before[k], k
+        assert len(kx) == len(rx) == len(cx) == len(bx) == N
+
+
 # ---- 5: end to end -------------------------------------------------------------------------------------------------------------------------------------------------------
 
 def test_end_to_end_from_a_kept_sweep(gu, c512):
@@ -521,10 +575,10 @@ def test_end_to_end_from_a_kept_sweep(gu, c512):
             else:  # the bank is edited, the corpus is not encoded again and the index is not refilled
                 eng.anchor_append(*two)
             m._golden_labels = [f"CWE-{i}" for i in range(ps.shape[1])]
-            index = m._kept.ranking
+            index = m._kept.indexes["ranking"]
             assert m.rematch_arrays(arrays, with_probs=True)[2].tobytes() == ps.tobytes()  # the witness is what the engine gives now
             out = m.anchor_ranking(arrays)
-            assert (more == 0 and index is None) or m._kept.ranking is index
+            assert (more == 0 and index is None) or m._kept.indexes["ranking"] is index
             assert [e["anchor"] for e in out] == m._golden_labels + ["bank"]
             for e, x in zip(out, exact):
                 tp, fp = x["best"]
@@ -532,6 +586,7 @@ def test_end_to_end_from_a_kept_sweep(gu, c512):
                 assert e["best_thres"] == float(x["best_thres"]) and (e["best_positives"], e["best_claimed"]) == (tp, tp + fp) and e["best_f1"] == 2 * tp / (tp + fp + x["n"][1])
                 assert abs(Fraction(e["ap"]) - x["ap"]) <= kit.ap_bound(x)
             gu.record("rank_end_to_end", anchors=len(out) - 1, auc=[e["auc"] for e in out], best_f1=[e["best_f1"] for e in out])
-        assert m._kept.indexes == dict.fromkeys(("reports", "claims", "bank"))
+        ranking = m._kept.indexes["ranking"]
+        assert ranking is not None and m._kept.indexes == dict(reports=None, claims=None, bank=None, ranking=ranking)
         m._kept.drop()
-        assert m._kept.ranking is None
+        assert m._kept.indexes == dict.fromkeys(("reports", "claims", "bank", "ranking"))

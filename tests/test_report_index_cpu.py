@@ -69,7 +69,7 @@ def test_the_main_library_does_not_know_the_new_files(libs, monkeypatch):
     new, _ = kk.own_and_shared("retrieve")
     assert sorted(os.path.basename(p) for p in new) == ["memvul_retrieve.h", "report_topk.h", "retrieve.hip"]
     assert build.SIDE_LIBS["retrieve"] == (build.RETRIEVE_LIB_NAME, build.RETRIEVE_SOURCES, build.RETRIEVE_HEADERS)
-    kk.check_the_shared_headers_belong_to_the_three_kept_libraries(monkeypatch)
+    kk.check_the_shared_headers_belong_to_the_four_kept_libraries(monkeypatch)
     opened = []
     real_open = open
 
