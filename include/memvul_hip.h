@@ -92,6 +92,9 @@ typedef struct mv_config {
  *   MEMVUL_FORM               default | safe | guarded: the form of MV_F16X8 the handle starts in (mv_set_form changes it later).  "safe" and "guarded" with
  *                             mv_finalize_weights(MV_F16) fail.
  *                             In the safe form MEMVUL_CLS_ASIDE, MEMVUL_CLS_ASIDE_MIN_LEN and MEMVUL_QKV_ASIDE have no effect (it is their most conservative setting).
+ * One more switch is read here that selects no numerics: MEMVUL_PP_FORM = fixed (default) | runtime.  MV_F16X8: the persistent GEMMs of a pass of padded length
+ * 256 / 512 in the [CLS]-row form with no short sequence take kernels that hold the form of the launch as compile-time constants (libmemvul_pp_fixed.so) and
+ * spill less; "runtime" keeps every launch on the kernels that read the form from their arguments.  The outputs are equal bit for bit.  Parsed strictly as well.
  * (The seventh switch of the product, MEMVUL_COMPUTE = precise | f16 | f32 (+ aliases), is read by the Python surface: memvul_amd/binding.py default_compute.)
  * (So are MEMVUL_ON_SINK = warn | safe and MEMVUL_SINK_CENSUS = 0 | 1 — binding.py on_sink_policy / sink_census_policy; the latter calls mv_sink_census_enable
  * after mv_finalize_weights — and MEMVUL_SINK_TOKENS = ID[,ID...] — binding.py sink_tokens_policy: mv_set_sink_tokens after mv_finalize_weights, guarded form only.)
@@ -308,6 +311,10 @@ int mv_corpus_topk(mv_handle* h, int64_t first, int64_t count, float* topk_p, in
  * wrapper warns once (binding.Engine).  NaN activations are not counted (the range test is a floating-point maximum, which skips them): they
  * propagate to the outputs as NaN, where they are visible.  No reference counterpart (the reference computes in fp32). */
 int mv_x8_saturation(mv_handle* h, int64_t* clamped, int reset);
+/* How many kernel launches of this handle took a fixed-form persistent GEMM (MEMVUL_PP_FORM above) since it was created, or since the last call with reset != 0;
+ * -1 for a null handle.  A host counter: no synchronisation.  For tests and A/B scripts (an equality test of the two forms proves nothing while this stays 0),
+ * hence outside the mv_ names of the product ABI. */
+int64_t mvpp_fixed_launches(mv_handle* h, int reset);
 
 /* MV_F16X8 only (0 / 0 in MV_F16).  The concentration monitor: what the default form's 1e-3 is measured for is diffuse attention and attention sinks on the two
  * delimiter tokens — the [CLS] and the [SEP] token of a sequence sit in its rows 0 and 1 (the "special rows": A-side correction terms in every GEMM, V as hi + lo;

@@ -220,6 +220,7 @@ _SIGNATURES = {
     "mv_tok_last_error": (C.c_char_p, [_vp]),
 }
 ABI_SYMBOLS = list(_SIGNATURES)
+PP_FORM_SIGNATURE = (C.c_int64, [_vp, C.c_int])  # mvpp_fixed_launches(handle, reset)
 
 
 _libs = {}
@@ -245,6 +246,8 @@ def load_library(path: Optional[str] = None, dev: bool = False):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
+    # the fixed-form launch counter (include/memvul_hip.h mvpp_fixed_launches): a figure for tests and A/B scripts, outside the mv_ names of ABI_SYMBOLS
+    lib.mvpp_fixed_launches.restype, lib.mvpp_fixed_launches.argtypes = PP_FORM_SIGNATURE
     # the three tiny getters the hot loop calls once per batch, bound a second time WITHOUT releasing the interpreter lock around the call (PyDLL): next to other
     # Python threads every release costs the scoring thread a wait for the lock that is far longer than these calls (profiles/r06_*_e2e_dropin.txt)
     quick = C.PyDLL(path)
@@ -489,6 +492,14 @@ class Engine:
         n = C.c_int64(0)
         self._check(self._lib.quick.mv_x8_saturation(self._h, C.byref(n), int(bool(reset))), "mv_x8_saturation")
         return int(n.value)
+
+    def pp_fixed_launches(self, reset: bool = False) -> int:
+        """MV_F16X8: kernel launches of this engine that took a fixed-form persistent GEMM (MEMVUL_PP_FORM=fixed, the default; libmemvul_pp_fixed.so) since it was
+        created / last reset; always 0 under MEMVUL_PP_FORM=runtime.  A host counter (mvpp_fixed_launches): it does not synchronise."""
+        n = int(self._lib.mvpp_fixed_launches(self._h, int(bool(reset))))
+        if n < 0:
+            raise RuntimeError("mvpp_fixed_launches: no handle")
+        return n
 
     def attention_concentration(self, reset: bool = False):
         """MV_F16X8: (max_collision, items_over, items_total) of mv_attention_concentration — the largest sum_{j >= 2} p[CLS row][j]^2 over every (sequence,

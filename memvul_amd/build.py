@@ -1,5 +1,5 @@
-"""Build libmemvul_hip.so (product and development build) and the side libraries of SIDE_LIBS — libmemvul_tok_u8.so, libmemvul_retrieve.so, libmemvul_claims.so,
-libmemvul_bank.so and libmemvul_rank.so — for gfx950, in-tree with hipcc.  The last four share csrc/kept_index.h and csrc/kept_terms.h, which no other library
+"""Build libmemvul_hip.so (product and development build) and the side libraries of SIDE_LIBS — libmemvul_tok_u8.so, libmemvul_pp_fixed.so, libmemvul_retrieve.so,
+libmemvul_claims.so, libmemvul_bank.so and libmemvul_rank.so — for gfx950, in-tree with hipcc.  The last four share csrc/kept_index.h and csrc/kept_terms.h, which no other library
 includes.  No torch involved."""
 from __future__ import annotations
 
@@ -26,6 +26,8 @@ DEV_FLAGS = ("-DMEMVUL_DEV_SWITCHES", "-Wl,-Bsymbolic")
 # the side libraries, each with sources, headers and a stamp of its own: key -> (library name, sources, headers).
 #   tok       the UTF-8 tokenise kernel and its launch function, a library and a code object of its own (csrc/wordpiece_u8.hip says why); the two libraries above link
 #             against it and find it beside themselves ($ORIGIN), so it is built before them
+#   pp        the fixed-form persistent GEMMs of MV_F16X8 and their launch function (csrc/gemm_pp_fixed.hip says why they are not kernels of libmemvul_hip.so); linked
+#             against and found like tok, so built before the two libraries above as well.  It is built from csrc/gemm_pp.h — a kernel edit there moves both maps
 #   retrieve  per-anchor retrieval over a kept corpus (csrc/retrieve.hip, csrc/report_topk.h, include/memvul_retrieve.h)
 #   claims    per-anchor claims over a kept corpus (csrc/claims.hip, csrc/claim_sweep.h, include/memvul_claims.h)
 #   bank      the anchor-bank audit over a kept corpus (csrc/bank.hip, csrc/bank_cover.h, include/memvul_bank.h)
@@ -36,19 +38,22 @@ DEV_FLAGS = ("-DMEMVUL_DEV_SWITCHES", "-Wl,-Bsymbolic")
 KEPT_HEADERS = ["kept_index.h", "kept_terms.h"]
 SIDE_LIBS = {
     "tok": ("libmemvul_tok_u8.so", ["wordpiece_u8.hip"], ["wordpiece.h"]),
+    "pp": ("libmemvul_pp_fixed.so", ["gemm_pp_fixed.hip"], ["gemm_pp_fixed.h", "gemm_pp.h", "gemm.h", "common.h"]),
     "retrieve": ("libmemvul_retrieve.so", ["retrieve.hip"], ["report_topk.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_retrieve.h")]),
     "claims": ("libmemvul_claims.so", ["claims.hip"], ["claim_sweep.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_claims.h")]),
     "bank": ("libmemvul_bank.so", ["bank.hip"], ["bank_cover.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_bank.h")]),
     "rank": ("libmemvul_rank.so", ["rank.hip"], ["rank_sort.h", *KEPT_HEADERS, os.path.join(ROOT, "include", "memvul_rank.h")]),
 }
 TOK_LIB_NAME, TOK_SOURCES, TOK_HEADERS = SIDE_LIBS["tok"]
+PP_LIB_NAME, PP_SOURCES, PP_HEADERS = SIDE_LIBS["pp"]
 RETRIEVE_LIB_NAME, RETRIEVE_SOURCES, RETRIEVE_HEADERS = SIDE_LIBS["retrieve"]
 CLAIMS_LIB_NAME, CLAIMS_SOURCES, CLAIMS_HEADERS = SIDE_LIBS["claims"]
 BANK_LIB_NAME, BANK_SOURCES, BANK_HEADERS = SIDE_LIBS["bank"]
 RANK_LIB_NAME, RANK_SOURCES, RANK_HEADERS = SIDE_LIBS["rank"]
 LIB_PATH_TOK, LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS, LIB_PATH_BANK, LIB_PATH_RANK = (os.path.join(LIB_DIR, SIDE_LIBS[k][0]) for k in ("tok", "retrieve", "claims", "bank", "rank"))
+LIB_PATH_PP = os.path.join(LIB_DIR, PP_LIB_NAME)
 SOURCES = ["engine.hip"]
-KERNEL_HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", "wordpiece.h"]
+KERNEL_HEADERS = ["common.h", "gemm.h", "gemm_pp.h", "gemm_pp_fixed.h", "attention.h", "attention_v2.h", "misc_kernels.h", "match_topk.h", "ref_f32.h", "sink_census.h", "route.h", "wordpiece.h"]
 # the host code of the library: engine.hip includes each of these parts once, in this order
 HOST_PARTS = ["host_base.h", "weights.h", "workspace.h", "encoder_pass.h", "batch_flow.h", "corpus.h", "comm.h", "records_format.h", "tokenizer_object.h"]
 HEADERS = KERNEL_HEADERS + HOST_PARTS + [os.path.join(ROOT, "include", "memvul_hip.h")]
@@ -281,12 +286,14 @@ def build_side(key: str, force: bool = False, verbose: bool = True) -> str:
 
 tok_is_stale, retrieve_is_stale, claims_is_stale, bank_is_stale, rank_is_stale = (partial(side_is_stale, k) for k in ("tok", "retrieve", "claims", "bank", "rank"))
 build_tok, build_retrieve, build_claims, build_bank, build_rank = (partial(build_side, k) for k in ("tok", "retrieve", "claims", "bank", "rank"))
+pp_is_stale, build_pp = partial(side_is_stale, "pp"), partial(build_side, "pp")
 
 
 def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool = False) -> str:
-    """Compile the HIP library for gfx950; returns the .so path.  dev: the -DMEMVUL_DEV_SWITCHES build (libmemvul_hip_dev.so).  libmemvul_tok_u8.so, which
-    both link against, is brought up to date first."""
+    """Compile the HIP library for gfx950; returns the .so path.  dev: the -DMEMVUL_DEV_SWITCHES build (libmemvul_hip_dev.so).  libmemvul_tok_u8.so and
+    libmemvul_pp_fixed.so, which both link against, are brought up to date first."""
     tok = build_tok(False, verbose)  # (forced by build_all, once for both)
+    build_pp(False, verbose)
     if not force and not is_stale(extra_flags, dev):
         return _paths(dev)[0]
     lib_path, stamp_path = _paths(dev)
@@ -297,7 +304,7 @@ def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool =
         hipcc_path(), f"--offload-arch={ARCH}", *FLAGS,  # -Wno-unused-value: hipError_t of calls checked by launch_check
         *extra_flags,
         *[os.path.join(CSRC, s) for s in SOURCES],
-        "-L" + os.path.dirname(tok), "-l:" + TOK_LIB_NAME, "-Wl,-rpath,$ORIGIN",  # (found beside this library wherever the tree lies)
+        "-L" + os.path.dirname(tok), "-l:" + TOK_LIB_NAME, "-l:" + PP_LIB_NAME, "-Wl,-rpath,$ORIGIN",  # (found beside this library wherever the tree lies)
         "-o", lib_path + ".tmp",
     ]
     if verbose:
@@ -320,12 +327,13 @@ def build(force: bool = False, verbose: bool = True, extra_flags=(), dev: bool =
 
 
 def build_all(force: bool = False, verbose: bool = True):
-    """Both builds, compiled side by side (two hipcc processes), after the library both link against; libmemvul_retrieve.so, libmemvul_claims.so,
+    """Both builds, compiled side by side (two hipcc processes), after the two libraries both link against; libmemvul_retrieve.so, libmemvul_claims.so,
     libmemvul_bank.so and libmemvul_rank.so, which stand alone, beside them.  Returns the paths of the two builds of libmemvul_hip.so (LIB_PATH_RETRIEVE,
     LIB_PATH_CLAIMS, LIB_PATH_BANK and LIB_PATH_RANK are where the other four lie)."""
     from concurrent.futures import ThreadPoolExecutor
 
     build_tok(force, verbose)
+    build_pp(force, verbose)
     with ThreadPoolExecutor(6) as ex:
         sides = [ex.submit(build_side, key, force, verbose) for key in ("retrieve", "claims", "bank", "rank")]
         futs = [ex.submit(build, force, verbose, (), d) for d in (False, True)]
@@ -335,4 +343,4 @@ def build_all(force: bool = False, verbose: bool = True):
 
 
 if __name__ == "__main__":
-    print("\n".join(build_all(force="--force" in sys.argv) + [LIB_PATH_TOK, LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS, LIB_PATH_BANK, LIB_PATH_RANK]))
+    print("\n".join(build_all(force="--force" in sys.argv) + [LIB_PATH_TOK, LIB_PATH_PP, LIB_PATH_RETRIEVE, LIB_PATH_CLAIMS, LIB_PATH_BANK, LIB_PATH_RANK]))

@@ -41,8 +41,10 @@ template <int PPEPI, int X8>
 constexpr auto pp_kernel = gemm_pp_kernel<PPEPI, PPEPI != PP_RESLN3, X8>;  // (RAW: every kind but the residual one)
 template <int PPEPI>
 constexpr int pp_lds = PPEPI != PP_RESLN3 ? PP_LDS_BYTES_RAW : PP_LDS_BYTES;
+// fixed: the launch belongs to a pass of the fixed form (pp_fixed_form below) and goes to the kernels of libmemvul_pp_fixed.so (gemm_pp_fixed.hip), which take the
+// form's fields as constants and do not read them from `a`; what the pass cannot know is checked here — the raster the launch gets and the N those kernels fix
 template <int PPEPI>
-int launch_pp(mv_handle* h, hipStream_t stream, int cls, GemmArgs a) {
+int launch_pp(mv_handle* h, hipStream_t stream, int cls, GemmArgs a, bool fixed = false) {
   if (a.M % 256 || a.N % 256 || a.K % 128 || a.K < 256 || a.N > MV_INTER)
     return fail(h, MV_ERR_INVALID, "gemm_pp: M,N % 256, K % 128, K >= 256, N <= 3072 required");  // K >= 256: the RAW kernels stage the
                                                                                               // next tile's statistics at K-tile 2
@@ -59,6 +61,13 @@ int launch_pp(mv_handle* h, hipStream_t stream, int cls, GemmArgs a) {
   ProfScope ps(h, stream, cls);
   if (a.A8) {
     if (!a.W8 || (PPEPI != PP_QK && !a.out8)) return fail(h, MV_ERR_STATE, "internal: MV_F16X8 GEMM without its fp8 planes");
+    if (fixed && a.raster_mode == 0 && (PPEPI == PP_QK || a.N == (PPEPI == PP_GELU ? MV_INTER : MV_HIDDEN))) {
+      const int e = pp_fixed_launch(PPEPI, &a, grid, pp_lds<PPEPI>, stream);
+      if (e < 0) return fail(h, MV_ERR_STATE, "internal: no fixed-form gemm_pp kernel for this launch");
+      if (e != (int)hipSuccess) return fail(h, MV_ERR_HIP, std::string("launch gemm_pp (fixed form): ") + hipGetErrorString((hipError_t)e));
+      ++h->pp_fixed_launches;
+      return MV_OK;
+    }
     hipLaunchKernelGGL((pp_kernel<PPEPI, 1>), dim3(grid), dim3(512), pp_lds<PPEPI>, stream, a);
   } else {
     hipLaunchKernelGGL((pp_kernel<PPEPI, 0>), dim3(grid), dim3(512), pp_lds<PPEPI>, stream, a);
@@ -82,6 +91,13 @@ bool pp_selected(const mv_handle* h, int64_t M) {
   if (h->gemm_tile == 128) return false;
   return h->gemm_tile == 512 || h->precise || (M / 256) * (MV_HIDDEN / 256) >= 256;
 }
+
+// form choice: the persistent GEMMs of this pass take the fixed-form kernels (gemm_pp_fixed.hip) — every form field those kernels hold as a constant has, in this
+// pass, the value they fix.  The [CLS]-row form on one-sequence tiles (padded length 256 / 512) with no sequence below cls_min_len as the HOST knows the
+// lengths (min_len; 0 = unknown: no tile flag would be set, so no tile is short), one plane, not the safe form, and no QKV block that sweeps its A-side term.
+// MEMVUL_PP_FORM=runtime (mv_handle::pp_fixed) keeps every launch on the run-time kernels: the two forms compute the same bits
+struct PassPlan;
+bool pp_fixed_form(const mv_handle* h, const PassPlan& p, int min_len);  // (defined below PassPlan)
 
 // the mid-size / skinny GEMMs of a pass that does not fill the chip (and of the [CLS] tail)
 template <int EPI>
@@ -287,7 +303,12 @@ struct PassPlan {
   bool special;
   bool two_plane;  // Q, K, V^T as hi + lo planes (two_plane_pass: launch_attention asks the same predicate)
   int qkv_mask;    // GemmArgs::x8_aside_mask of the QKV projection
+  bool fixed;      // the persistent GEMMs take the fixed-form kernels (pp_fixed_form)
 };
+
+bool pp_fixed_form(const mv_handle* h, const PassPlan& p, int min_len) {
+  return h->pp_fixed && p.big && p.x8 && p.cls_as && p.one_seq_tiles && min_len >= h->cls_min_len && !p.two_plane && !p.safe && p.qkv_mask == 0;
+}
 
 // what every GEMM of the layer stack is given, whatever its kind
 GemmArgs pass_gemm(const mv_handle* h, const Work& wk, const PassPlan& p) {
@@ -330,7 +351,7 @@ int launch_qkv(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w, bool 
     if ((p.qkv_mask & blocks) != blocks) { if (int rc = row_term(h, wk, p, wk.st_lo, g)) return rc; }
     g.vlo_sp = special_v_lo(wk, p);
   }
-  return launch_pp<PP_QK>(h, wk.stream, cls, g);
+  return launch_pp<PP_QK>(h, wk.stream, cls, g, p.fixed);
 }
 
 // The fields of the two residual GEMMs of the persistent path (K4, K6: N = 768, in place on the raw stream): + bias + LayerNorm(residual) with gamma / beta of
@@ -352,7 +373,7 @@ int launch_out_proj(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w, 
   residual_fields(wk, p, g, wk.lnstats, wk.lnpart, pend_g, pend_b);
   if (p.x8) { g.A8 = wk.ctx8; g.W8 = w.wo8; g.x8_scale = w.sc_o; }
   if (p.cls_as) { if (int rc = row_term(h, wk, p, wk.cls_lo, g)) return rc; }  // (the context's special low parts: launch_attention)
-  return launch_pp<PP_RESLN3>(h, wk.stream, KC_GEMM_OUT, g);
+  return launch_pp<PP_RESLN3>(h, wk.stream, KC_GEMM_OUT, g, p.fixed);
 }
 
 // K5: FFN-1 + exact-erf GELU
@@ -367,7 +388,7 @@ int launch_ffn1(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w) {
     g.out8_hi_only = 1;       // h8 is FFN-2's A8: hi8 alone
     g.sp_lo_out = wk.cls_lo;  // the GELU output's special low parts: FFN-2's row term
   }
-  return launch_pp<PP_GELU>(h, wk.stream, KC_GEMM_FFN1, g);
+  return launch_pp<PP_GELU>(h, wk.stream, KC_GEMM_FFN1, g, p.fixed);
 }
 
 // K6: FFN-2 + bias + LayerNorm(residual); persistent path: + vstats of the new rows (wk.lnstats: the next layer's input)
@@ -378,7 +399,7 @@ int launch_ffn2(mv_handle* h, Work& wk, const PassPlan& p, const LayerW& w) {
   residual_fields(wk, p, g, wk.lnpart, wk.lnstats, w.ln1g, w.ln1b);
   if (p.x8) { g.A8 = wk.h8; g.W8 = w.w28; g.x8_scale = w.sc_2; }
   if (p.cls_as) { if (int rc = row_term(h, wk, p, wk.cls_lo, g)) return rc; }
-  return launch_pp<PP_RESLN3>(h, wk.stream, KC_GEMM_FFN2, g);
+  return launch_pp<PP_RESLN3>(h, wk.stream, KC_GEMM_FFN2, g, p.fixed);
 }
 
 int run_ln(mv_handle* h, Work& wk, float* x32, half_t* x16, int rows, const float* g, const float* b) {
@@ -550,6 +571,7 @@ int encode_dev(mv_handle* h, Work& wk, const int32_t* d_ids, const int32_t* d_le
   p.special = p.big && p.x8;
   p.two_plane = two_plane_pass(h, p.x8, p.safe, p.Sp);
   p.qkv_mask = p.safe ? 7 : h->qkv_aside_mask;
+  p.fixed = pp_fixed_form(h, p, min_len);
   const int M = (int)p.M, Sp = p.Sp, ntile = (int)(p.Mpad / 256);
   if (p.cls_as && p.one_seq_tiles) {
     hipLaunchKernelGGL(cls_tile_flags_kernel, dim3((unsigned)((ntile + 255) / 256)), dim3(256), 0, wk.stream, d_lens, B, Sp, h->cls_min_len, ntile,

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "gemm.h"
 #include "gemm_pp.h"
+#include "gemm_pp_fixed.h"
 #include "attention.h"
 #include "attention_v2.h"
 #include "misc_kernels.h"
@@ -312,6 +313,11 @@ struct mv_handle {
                            // within 7 % of each other, scripts/r06_qkv_model.py; GPU, 60 draws: +3 % error for +2.7 % issue reports/s, profiles/r06_m_*).  Rounds 4 - 6a: Q ("q").
                            // env MEMVUL_QKV_ASIDE = a subset of "qkv", "" or "none" ("qkv" = round 3's form)
 
+  bool pp_fixed = true;    // MV_F16X8, env MEMVUL_PP_FORM=fixed (default) | runtime: the persistent GEMMs of a long pass in the [CLS]-row form take the fixed-form
+                           // kernels of libmemvul_pp_fixed.so (encoder_pass.h pp_fixed_form; gemm_pp_fixed.hip) — the same bits from kernels that spill less;
+                           // runtime = every launch on the kernels of this library, as before
+  int64_t pp_fixed_launches = 0;  // launches of this handle that took a fixed-form kernel (mvpp_fixed_launches)
+
   int form = MV_FORM_DEFAULT;  // MV_F16X8, mv_set_form / env MEMVUL_FORM: MV_FORM_SAFE = the form that holds 1e-3 with an attention sink on an ORDINARY token too — both
                            // first-order terms in every row of every GEMM (no [CLS]-row form, no row terms), the A-side term in all three QKV blocks, and Q, K, V, P as
                            // hi + lo fp16 planes through attention at EVERY padded length (attention_v2.h VLO, NCH > 1 above 128) and through the pruned last layer's
@@ -407,6 +413,14 @@ int read_switches(mv_handle* h) {
     else if (!strcmp(e, "guarded")) h->form = MV_FORM_GUARDED;
     else {
       g_create_error = std::string("MEMVUL_FORM=\"") + e + "\": expected \"default\", \"safe\" or \"guarded\"";
+      return MV_ERR_INVALID;
+    }
+  }
+  if (const char* e = getenv("MEMVUL_PP_FORM")) {  // which kernels the persistent GEMMs of a long pass take (mv_handle::pp_fixed): the bits do not depend on it
+    if (!strcmp(e, "fixed")) h->pp_fixed = true;
+    else if (!strcmp(e, "runtime")) h->pp_fixed = false;
+    else {
+      g_create_error = std::string("MEMVUL_PP_FORM=\"") + e + "\": expected \"fixed\" or \"runtime\"";
       return MV_ERR_INVALID;
     }
   }
@@ -511,6 +525,7 @@ int mv_create(int device, const mv_config* cfg, mv_handle** out) try {
   // dynamic LDS above 64 KiB needs an explicit opt-in — per device, so here and not behind a process-wide flag: every kernel of the two lists the launchers read
   for (const GemmLdsOptIn& k : GEMM_LDS_OPT_INS) hipFuncSetAttribute((const void*)k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
   for (const AttnVariant& v : ATTN_VARIANTS) hipFuncSetAttribute((const void*)v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds);
+  (void)pp_fixed_lds_opt_in();  // the fixed-form persistent GEMMs: kernels of libmemvul_pp_fixed.so, which opts its own list in
   (void)hipGetLastError();
 
   h->cap_tokens = round_up(cfg->max_tokens, 256) + 256;
@@ -875,6 +890,15 @@ int mv_last_row_forms(mv_handle* h, uint8_t* forms, int n) try {
   std::memcpy(forms, h->last_forms.data(), (size_t)n);
   return MV_OK;
 } catch (...) { return on_exception(h); }
+
+// launches of this handle that took a fixed-form persistent GEMM (encoder_pass.h launch_pp) since it was created or last reset; a host counter, no synchronisation.
+// Outside the mv_ names: a figure for tests and A/B scripts, not an entry of the product ABI
+int64_t mvpp_fixed_launches(mv_handle* h, int reset) {
+  if (!h) return -1;
+  const int64_t n = h->pp_fixed_launches;
+  if (reset) h->pp_fixed_launches = 0;
+  return n;
+}
 
 int mv_x8_saturation(mv_handle* h, int64_t* clamped, int reset) try {
   if (!h || !clamped) return fail(h, MV_ERR_INVALID, "mv_x8_saturation: bad argument");

@@ -71,6 +71,45 @@
 enum { PP_QK = 1, PP_GELU = 3, PP_RESLN3 = 8 };
 constexpr int PP_F = 4;  // half-tiles kept in flight across each barrier
 
+// The FORM of a launch: where the kernel takes the fields from that say which of its variants a launch runs.  The run-time form (the default, below) reads every one
+// of them from GemmArgs, so one kernel serves every pass — and holds them all in SGPRs across the main loop, which is why the X8 kernels spill.  A translation unit
+// that defines PP_KERNEL_NAME and some of these accessors BEFORE it includes this file gets the same kernel under another name with those fields as constants
+// (gemm_pp_fixed.hip: the long passes of the [CLS]-row form, where the host knows them all before the launch).  Macros, not a template parameter: the run-time
+// kernels must keep their symbol names and compile to the bytes they had (profiles/kernel_fingerprints.json), and a token-for-token substitution cannot move them.
+// Inside the kernel EPI, RAW and X8 are in scope, so an overriding accessor may depend on the kernel kind.
+#ifndef PP_KERNEL_NAME
+#define PP_KERNEL_NAME gemm_pp_kernel
+#endif
+#ifndef PP_SHORT_TILE  // (a, tm): row tile tm holds a sequence too short for the [CLS]-row form (GemmArgs::tile_both; the flag goes through sload_i32)
+#define PP_SHORT_TILE(a, tm) ((a).tile_both && sload_i32((a).tile_both + (tm)) != 0)
+#endif
+#ifndef PP_X8_TERMS
+#define PP_X8_TERMS(a) ((a).x8_terms)
+#endif
+#ifndef PP_ASIDE_MASK
+#define PP_ASIDE_MASK(a) ((a).x8_aside_mask)
+#endif
+#ifndef PP_OUT8_HI_ONLY
+#define PP_OUT8_HI_ONLY(a) ((a).out8_hi_only)
+#endif
+#ifndef PP_VT_LO  // the second planes of a two-plane pass: set together, or not at all
+#define PP_VT_LO(a) ((a).vt_lo)
+#define PP_Q_LO(a) ((a).q_lo)
+#define PP_K_LO(a) ((a).k_lo)
+#endif
+#ifndef PP_RASTER_MODE
+#define PP_RASTER_MODE(a) ((a).raster_mode)
+#endif
+#ifndef PP_S
+#define PP_S(a) ((a).S)
+#endif
+#ifndef PP_N
+#define PP_N(a) ((a).N)
+#endif
+#ifndef PP_EXTRA_TPARAMS  // further template parameters of the renamed kernel (", int FS"), for accessors that take a value per instantiation; none here
+#define PP_EXTRA_TPARAMS
+#endif
+
 #define PP_LDS_A 0           // [par][a][wr][64 rows][128 B]
 #define PP_LDS_B 65536       // [par][b][wc][32 rows][128 B]
 #define PP_LDS_BIAS 131072   // PP_RESLN3: bias | gamma | beta, 3 x 768 fp32
@@ -228,7 +267,7 @@ __device__ __forceinline__ int sload_i32(const int* p) {
 // so a workgroup — and with the XCD remap a whole XCD's contiguous run of 32 positions — meets the SAME tile_m in ngroups consecutive
 // iterations: its A panels can stay in that XCD's L2 across the whole N sweep while the W panels of the groups pass through.
 __device__ __forceinline__ void raster_pp(const GemmArgs& a, int L, int G, int tm_count, int tn_count, int& tile_m, int& tile_n) {
-  if (a.raster_mode == 1) {
+  if (PP_RASTER_MODE(a) == 1) {
     const int ngroups = tn_count / a.GN;
     const int w = L / G, r = L - w * G;
     const int b = w / ngroups, g = w - b * ngroups;
@@ -240,8 +279,8 @@ __device__ __forceinline__ void raster_pp(const GemmArgs& a, int L, int G, int t
   }
 }
 
-template <int EPI, int RAW = 0, int X8 = 0>
-__global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
+template <int EPI, int RAW = 0, int X8 = 0 PP_EXTRA_TPARAMS>
+__global__ __launch_bounds__(512, 2) void PP_KERNEL_NAME(GemmArgs a) {
   static_assert(EPI == PP_QK || EPI == PP_GELU || EPI == PP_RESLN3, "kernel kinds of the encoder layer");
   static_assert(RAW == (EPI != PP_RESLN3), "PP_QK / PP_GELU consume the raw stream (virtual LayerNorm), PP_RESLN3 produces it");
   constexpr bool IS_RES = (EPI == PP_RESLN3);
@@ -254,7 +293,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
   const int hi = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  const int K = a.K, nk0 = K >> 6;                 // K-tiles of one sweep
+  const int K = a.K, nk0 = K >> 6;                // K-tiles of one sweep
   constexpr int nseg = X8 ? 2 : 1;                  // X8: the fp16 sweep, then the fp8 correction sweep
   // K-tiles of the fp8 sweep of a tile: K / 64 for both first-order terms (virtual K = 2 K), K / 128 when only the weight-side term
   // A_hi8 W_lo8 is swept (the SECOND halves of both operand rows, byte offset K).  a.x8_terms: 0 / 2 = both terms everywhere,
@@ -267,16 +306,16 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
   // a.tile_both (engine.hip cls_aside): per 256-row tile, non-zero = a sequence in it is too short for the [CLS]-row form (the other rows' A-side
   // rounding reaches the [CLS] row averaged over the keys): such a tile sweeps BOTH terms where x8_terms asks for the weight-side one only, takes
   // nothing from cls_corr and keeps its lo8 planes — i.e. it runs the default form bit for bit, whatever the rest of the pass does.
-  auto short_tile = [&](int tm) -> bool { return a.tile_both && sload_i32(a.tile_both + tm) != 0; };
+  auto short_tile = [&](int tm) -> bool { return PP_SHORT_TILE(a, tm); };
   auto both_terms = [&](int tm, int tn) -> bool {
-    if (a.x8_terms == 1) return short_tile(tm);
-    if (a.x8_terms != 3) return true;
+    if (PP_X8_TERMS(a) == 1) return short_tile(tm);
+    if (PP_X8_TERMS(a) != 3) return true;
     const int which = (tn * 256 + a.col0) / MV_HIDDEN;  // 0 = Q, 1 = K, 2 = V
-    return (a.x8_aside_mask >> which) & 1;
+    return (PP_ASIDE_MASK(a) >> which) & 1;
   };
   int i_nk8 = X8 ? nk0 : 0;    // of the tile being STAGED (issue cursor)
   size_t i_off8 = 0;
-  const int tm_count = a.M >> 8, tn_count = a.N >> 8;
+  const int tm_count = a.M >> 8, tn_count = PP_N(a) >> 8;
   const int ntiles = tm_count * tn_count;
   const int G = gridDim.x;
   const int bslot = xcd_remap(blockIdx.x, G);
@@ -284,7 +323,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
   // ---- bias -> LDS (once per workgroup; RAW kernels: per tile, issue_stats)
   if constexpr (!RAW) {
     float* lb = (float*)(smem + PP_LDS_BIAS);
-    for (int n = tid; n < a.N; n += 512) lb[n] = a.bias ? a.bias[n] : 0.f;
+    for (int n = tid; n < PP_N(a); n += 512) lb[n] = a.bias ? a.bias[n] : 0.f;
     for (int n = tid; n < MV_HIDDEN; n += 512) {  // N == 768: gamma at [768, 1536), beta at [1536, 2304) of the same image
       lb[MV_HIDDEN + n] = a.lng[n];
       lb[2 * MV_HIDDEN + n] = a.lnb[n];
@@ -426,8 +465,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
     size_t sp_off = 0;
     if constexpr (X8) {
       if ((i & 1) == 0) {
-        const int row0 = mw0 + 32 * i, b = row0 / a.S;
-        sp_c = row0 < a.Mreal && b * a.S == row0 && crow < 2;
+        const int row0 = mw0 + 32 * i, b = row0 / PP_S(a);
+        sp_c = row0 < a.Mreal && b * PP_S(a) == row0 && crow < 2;
         sp_off = (size_t)(2 * b + crow) * MV_HIDDEN;
       }
     }
@@ -593,7 +632,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
     const int nw = (tile_n << 8) + wc * 64;   // first output column of this wave
     bool tile_short = false;                  // cls_aside: this row tile's sequence keeps the default form (read once per tile)
     if constexpr (X8) tile_short = short_tile(tile_m);
-    const bool tile_both_terms = X8 && (a.x8_terms == 1 ? tile_short : both_terms(tile_m, tile_n));
+    const bool tile_both_terms = X8 && (PP_X8_TERMS(a) == 1 ? tile_short : both_terms(tile_m, tile_n));
 
     // ---- accumulator init: zero (RAW) or bias + LayerNorm(residual).  The images are read with inline-asm ds_reads: hipcc would put
     // `s_waitcnt vmcnt(0)` in front of a compiler-visible LDS load here (LDS-DMA in flight) and drain the operand pipeline once per tile.
@@ -632,8 +671,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
           for (int i = 0; i < 4; ++i) {
             bool sp_c = false;
             if ((i & 1) == 0) {
-              const int row0 = mw + 32 * i, sb0 = row0 / a.S;
-              sp_c = row0 < a.Mreal && sb0 * a.S == row0 && (lane >> 2) < 2;
+              const int row0 = mw + 32 * i, sb0 = row0 / PP_S(a);
+              sp_c = row0 < a.Mreal && sb0 * PP_S(a) == row0 && (lane >> 2) < 2;
             }
 #pragma unroll
             for (int j = 0; j < 2; ++j)
@@ -748,15 +787,15 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
         if (a.cls_corr || a.sp_lo_out || a.vlo_sp) {
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
-            const int row = mw + 64 * j, b = row / a.S;  // wave-uniform
-            if (row < a.Mreal && b * a.S == row) cls_b[j] = b;
+            const int row = mw + 64 * j, b = row / PP_S(a);  // wave-uniform
+            if (row < a.Mreal && b * PP_S(a) == row) cls_b[j] = b;
           }
         }
         if (a.cls_corr && !tile_both_terms) {  // (a tile whose sweep carried both terms has it already)
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             if (cls_b[j] >= 0 && m16 < 2) {
-              const float* cp = a.cls_corr + (size_t)(2 * cls_b[j] + m16) * a.N + nw + 4 * q4;
+              const float* cp = a.cls_corr + (size_t)(2 * cls_b[j] + m16) * PP_N(a) + nw + 4 * q4;
               floatx4 c[4];  // all four loads in flight before the first use: ONE exposed memory latency per tile that holds such a row
 #pragma unroll
               for (int cb = 0; cb < 4; ++cb) c[cb] = *(const floatx4*)(cp + 16 * cb);
@@ -844,8 +883,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
         const uint32_t tb0 = scr + q4 * 256 + (m16 & 7) * 2;
         const uint32_t tt0 = tb0 + ((((uint32_t)(m16 >> 3)) ^ (uint32_t)q4) << 4), tt1 = tb0 + (((2u + (uint32_t)(m16 >> 3)) ^ (uint32_t)q4) << 4);
         if constexpr (EPI == PP_GELU || IS_RES) {
-          obase = a.out16 + (size_t)(mw + crow) * a.N + nw + 8 * cchunk;
-          rstride = a.N; istride = (size_t)32 * a.N; jstride = 32;
+          obase = a.out16 + (size_t)(mw + crow) * PP_N(a) + nw + 8 * cchunk;
+          rstride = PP_N(a); istride = (size_t)32 * PP_N(a); jstride = 32;
         } else {  // PP_QK: one head per wave; S % 64 == 0 so a 128-row block may span two batch rows
           // columns [0,768) -> Q, [768,1536) -> K, [1536,2304) -> V^T (a merged launch); col0 = 768: K (and V) only
           const int colg = nw + a.col0;
@@ -853,13 +892,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
           const int head = (colg - which * MV_HIDDEN) >> 6;
           vtile = which == 2;
           if (vtile) {  // image rows = head dims, image columns = tokens (scr_f16x2_t)
-            obase = a.vt + ((size_t)head * MV_HEAD_DIM + crow) * a.S + 8 * cchunk;
-            rstride = a.S; istride = 0; jstride = (size_t)32 * a.S;
-            if (a.vt_lo) lo_delta = a.vt_lo - a.vt;
+            obase = a.vt + ((size_t)head * MV_HEAD_DIM + crow) * PP_S(a) + 8 * cchunk;
+            rstride = PP_S(a); istride = 0; jstride = (size_t)32 * PP_S(a);
+            if (PP_VT_LO(a)) lo_delta = PP_VT_LO(a) - a.vt;
           } else {
-            obase = (which ? a.k : a.q) + (size_t)head * a.S * MV_HEAD_DIM + (size_t)crow * MV_HEAD_DIM + 8 * cchunk;
+            obase = (which ? a.k : a.q) + (size_t)head * PP_S(a) * MV_HEAD_DIM + (size_t)crow * MV_HEAD_DIM + 8 * cchunk;
             rstride = MV_HEAD_DIM; istride = 0; jstride = 32;  // the batch-row part is added per i below
-            if (a.vt_lo) lo_delta = which ? a.k_lo - a.k : a.q_lo - a.q;
+            if (PP_VT_LO(a)) lo_delta = which ? PP_K_LO(a) - a.k : PP_Q_LO(a) - a.q;
           }
         }
         // RAW: bias' of this lane's columns (per-tile LDS image: one float4 per column block) and rstd of its eight token rows
@@ -888,9 +927,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
           half_t* ob = obase + i * istride;
           if constexpr (EPI == PP_QK) {
             live = mb < a.Mreal;
-            const int b = mb / a.S, s0 = mb - b * a.S;
-            if (!vtile) ob = obase + ((size_t)b * MV_HEADS * a.S + s0) * MV_HEAD_DIM;
-            else ob = obase + (size_t)b * MV_HEADS * MV_HEAD_DIM * a.S + s0;
+            const int b = mb / PP_S(a), s0 = mb - b * PP_S(a);
+            if (!vtile) ob = obase + ((size_t)b * MV_HEADS * PP_S(a) + s0) * MV_HEAD_DIM;
+            else ob = obase + (size_t)b * MV_HEADS * MV_HEAD_DIM * PP_S(a) + s0;
           }
           u32x2 d[2][4];  // [j][k = 2 tbl + cbl]
           u32x4 o[4];
@@ -946,7 +985,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
             // fp16 storage of Q, K, V and P, which attention averages over the keys, so short sequences feel it most (profiles/r05_f_length_envelope.txt);
             // the attention kernel of these passes adds the first-order terms K_lo Q_hi + K_hi Q_lo and V_lo P_hi + V_hi P_lo (attention_v2.h VLO).
             // Same values as the first pass, recomputed.
-            if (a.vt_lo) {
+            if (PP_VT_LO(a)) {
 #pragma unroll
               for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -996,13 +1035,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
             uint32_t dl[8], dh[8];  // [4 tbl + 2 j + cbl]: the dword of token 16 tbl + m16, columns 32 j + 16 cbl + 4 q4 .. + 3
             float vmax8 = 0.f;      // max |value| of the block (saturation accounting, common.h)
             const uint32_t w8 = ub8 + (sf << 4);
-            uint8_t* o8 = a.out8 + (size_t)(mb + crow) * (2 * a.N) + nw + 16 * cchunk;
+            uint8_t* o8 = a.out8 + (size_t)(mb + crow) * (2 * PP_N(a)) + nw + 16 * cchunk;
             // GemmArgs::out8_hi_only (engine.hip cls_aside: the consumer sweeps the weight-side term only): no lo8 plane
             bool hi_only = false;
-            if constexpr (X8) hi_only = a.out8_hi_only && !tile_short;
+            if constexpr (X8) hi_only = PP_OUT8_HI_ONLY(a) && !tile_short;
             // the special rows' low parts, compact (GemmArgs::sp_lo_out): token block 2 i of an even block row holds rows mw + 32 i + m16
             if (a.sp_lo_out && (i & 1) == 0 && cls_b[i >> 1] >= 0 && m16 < 2) {
-              half_t* sp = a.sp_lo_out + (size_t)(2 * cls_b[i >> 1] + m16) * a.N + nw + 4 * q4;
+              half_t* sp = a.sp_lo_out + (size_t)(2 * cls_b[i >> 1] + m16) * PP_N(a) + nw + 4 * q4;
 #pragma unroll
               for (int cb = 0; cb < 4; ++cb) {
                 half4_t l;
@@ -1047,14 +1086,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmArgs a) {
             }
             if (hi_only) {
               scr_f8x1(w8, w8 ^ 16u, w8 ^ 32u, w8 ^ 48u, dh, scr_c, o);
-              *(u32x4*)(o8 + a.N) = o[0];
-              *(u32x4*)(o8 + a.N + (size_t)16 * (2 * a.N)) = o[1];
+              *(u32x4*)(o8 + PP_N(a)) = o[0];
+              *(u32x4*)(o8 + PP_N(a) + (size_t)16 * (2 * PP_N(a))) = o[1];
             } else {
               scr_f8x2(w8, w8 ^ 16u, w8 ^ 32u, w8 ^ 48u, dl, dh, scr_c, o);
               *(u32x4*)o8 = o[0];
-              *(u32x4*)(o8 + (size_t)16 * (2 * a.N)) = o[1];
-              *(u32x4*)(o8 + a.N) = o[2];
-              *(u32x4*)(o8 + a.N + (size_t)16 * (2 * a.N)) = o[3];
+              *(u32x4*)(o8 + (size_t)16 * (2 * PP_N(a))) = o[1];
+              *(u32x4*)(o8 + PP_N(a)) = o[2];
+              *(u32x4*)(o8 + PP_N(a) + (size_t)16 * (2 * PP_N(a))) = o[3];
             }
           }
           if constexpr (IS_RES) {  // block row i is out: request block row i of the NEXT tile's residual into its registers

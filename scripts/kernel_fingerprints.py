@@ -1,7 +1,7 @@
 """Per-kernel fingerprints of the library's device code (memvul_amd/build.py kernel_fingerprints): print them, write them, or compare them with a
 recorded map.
 
-  python scripts/kernel_fingerprints.py [--dev | --tok | --retrieve | --claims | --bank | --rank] [--lib FILE.so] [--out FILE.json] [--against FILE.json]
+  python scripts/kernel_fingerprints.py [--dev | --tok | --pp | --retrieve | --claims | --bank | --rank] [--lib FILE.so] [--out FILE.json] [--against FILE.json]
 
 --against lists the symbols that were added, removed or changed and exits 1 if there are any: a host-only edit of engine.hip or of its parts must report none, for the
 product and for the development build (profiles/kernel_fingerprints*.json hold the maps of the tree as committed; --tok: libmemvul_tok_u8.so, the UTF-8 tokenise
@@ -28,6 +28,7 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--dev", action="store_true", help="the development build (libmemvul_hip_dev.so)")
     ap.add_argument("--tok", action="store_true", help="the UTF-8 tokenise kernel's library (libmemvul_tok_u8.so)")
+    ap.add_argument("--pp", action="store_true", help="the fixed-form persistent GEMMs' library (libmemvul_pp_fixed.so; profiles/kernel_fingerprints_pp.json)")
     ap.add_argument("--retrieve", action="store_true", help="the per-anchor retrieval library (libmemvul_retrieve.so)")
     ap.add_argument("--claims", action="store_true", help="the per-anchor claims library (libmemvul_claims.so)")
     ap.add_argument("--bank", action="store_true", help="the anchor-bank audit library (libmemvul_bank.so)")
